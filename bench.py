@@ -2,6 +2,13 @@
 """Benchmark of the per-frame ocean path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg1|cfg2|cfg4|cfg5]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`,
+`ms_per_step`).  --full adds every measurement that takes runs of its own: the per-kernel HIP-event
+region and the roofline, the operator IFFT stage (in and beyond the Infinity Cache), the update loop,
+the beyond-cache frame and the CPU baseline.  --dump-outputs DIR writes the textures of the last
+timed step as DIR/<name>.npy (write_outputs).
 
 cfg1 (BASELINE.json configs[0], 256^2 x 1 on the scalar CPU path, no GPU) prints its own line with
 n_gpus 0: the C port timed as the labelled stand-in for the C# path (run_cfg1).
@@ -554,9 +561,14 @@ def run_cfg1(args):
     for f in range(args.warmup):
         oc.step(f / 60.0)
     t0 = time.perf_counter()
+    last = None
     for f in range(args.steps):
-        oc.step((args.warmup + f) / 60.0)
+        last = oc.step((args.warmup + f) / 60.0)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and last is not None:  # the last timed frame's textures (write_outputs' names)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in zip(("disp", "deriv", "turb"), last):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, np.float32))
     return {
         "metric": f"ocean-surface frames/sec ({cfg['desc']})",
         "value": round(args.steps / elapsed, 2),
@@ -583,6 +595,38 @@ def run_cfg1(args):
     }
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: all files together stay under 64 MB
+DUMP_SEED = 20251121
+
+
+def write_outputs(ctx, out_dir, rank=0, world=1):
+    """--dump-outputs: what ocean_step left for its caller after the last timed step -- the DISP, DERIV
+    and TURB textures of every (tile, cascade) the rank owns (DISP alone for a displacement-only
+    context), each as float32 <name>.npy (<name>_rank<r>.npy past one rank).  A texture set larger than
+    its share of DUMP_BUDGET_BYTES is written as a fixed sample: the flat float indices drawn by
+    numpy's default_rng(DUMP_SEED) over [tile][cascade][y][x][channel], the same in every run of the
+    same configuration, so two builds can be compared element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    texs = [("disp", oh.TEX_DISP)]
+    if ctx.planes == 4:
+        texs += [("deriv", oh.TEX_DERIV), ("turb", oh.TEX_TURB)]
+    ctx.synchronize()
+    keep = DUMP_BUDGET_BYTES // 4 // (len(texs) * world)
+    per_slice = ctx.n * ctx.n * 4
+    slices = [(t, c) for t in range(ctx.T) for c in range(ctx.C)]
+    idx = None
+    if per_slice * len(slices) > keep:  # sorted, so that one slice at a time is on the host
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, per_slice * len(slices), keep))
+        cut = np.searchsorted(idx, per_slice * np.arange(len(slices) + 1))
+    for name, tex in texs:
+        parts = []
+        for k, (t, c) in enumerate(slices):
+            a = ctx.read(tex, t, c).reshape(-1)
+            parts.append(a if idx is None else a[idx[cut[k]:cut[k + 1]] - k * per_slice])
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"),
+                np.concatenate(parts).astype(np.float32, copy=False))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -598,6 +642,11 @@ def main():
                     help="cfg5 past one GPU per cascade: contiguous column bands instead of even / odd columns")
     ap.add_argument("--only-update-loop", action="store_true",
                     help="run update_loop alone and print its JSON (the rocprofv3 record of the mip kernels)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: kernel events and roofline, the operator "
+                         "IFFT stage, the beyond-cache frame, the update loop, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the textures of the last timed step as DIR/<name>.npy (write_outputs)")
     args = ap.parse_args()
     if CONFIGS[args.config].get("cpu_only"):
         print(json.dumps(run_cfg1(args)), flush=True)
@@ -695,6 +744,51 @@ def main():
     barrier()
     elapsed = t1 - t0
 
+    if args.dump_outputs:  # the last timed step's textures, before anything else steps the context
+        write_outputs(ctx, args.dump_outputs, rank, world)
+
+    def headline(elapsed):
+        """The result line of a plain run: what the timed region alone gives."""
+        frames = args.steps * job_oceans  # ocean-frames (one frame of one ocean = all its cascades of N^2)
+        B = algorithmic_bytes(ctx)
+        return {
+            "metric": "ocean-surface frames/sec (4x1024^2 cascades)" if args.config == "cfg3"
+            else f"ocean-surface frames/sec ({cfg['desc']})",
+            "value": round(frames / elapsed, 2),
+            "unit": "frames/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "prewarm": {"frames": prewarm_frames, "seconds": round(prewarm_s, 3)},
+            "ms_per_step": round(1e3 * elapsed / args.steps, 5),
+            "higher_is_better": True,
+            "scaling": "weak" if cfg["per_rank"] else "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic (scene parameters of Waves.unity, seeded noise 20251121+tile)",
+            "config": {"workload": f"{args.config}: {cfg['desc']}", "n": n, "cascades": cfg["cascades"],
+                       "tiles_per_gpu": tiles, "tiles_total": job_oceans,
+                       "rank0_shard": {"cascades": [casc0, casc0 + C],
+                                       "columns": f"x = 2m + {parity}" if parity >= 0 else [x0, x0 + nx]},
+                       "schedule": "unfused" if args.unfused else "fused (pass A + pass B)",
+                       "parallelism": f"{'independent oceans' if cfg['per_rank'] else 'one job split'} "
+                                      f"over {world} GPU(s), no collective"},
+            "frame": {"algorithmic_bytes_per_gpu": B["frame"],
+                      "achieved_GBs_per_gpu": round(B["frame"] / (elapsed / args.steps) / 1e9, 1),
+                      "frac_per_gpu": round(B["frame"] / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
+                      "frac_of_measured_copy_per_gpu": round(B["frame"] / (elapsed / args.steps) / 1e9 / HBM_COPY_GBS, 4)},
+            "full": args.full,
+        }
+
+    if not args.full:  # a plain run ends here: no measurement beyond the timed steps
+        elapsed, _ = reduce_timing(elapsed, tiles, world)
+        if rank == 0:
+            print(json.dumps(headline(elapsed)), flush=True)
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # kernel region: the same K frames again with HIP events attached to every kernel
     # dispatch on the ctx stream (ocean_set_kernel_timing; hipExtLaunchKernel start/stop
     # events, so the durations are the kernels' own and agree with rocprofv3 --stats) ->
@@ -783,30 +877,9 @@ def main():
         cpu = cpu_baseline(cfg)
 
     if rank == 0:
-        frames = args.steps * job_oceans  # ocean-frames (one frame of one ocean = all its cascades of N^2)
-        value = frames / elapsed
-        out = {
-            "metric": "ocean-surface frames/sec (4x1024^2 cascades)" if args.config == "cfg3"
-            else f"ocean-surface frames/sec ({cfg['desc']})",
-            "value": round(value, 2),
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "prewarm": {"frames": prewarm_frames, "seconds": round(prewarm_s, 3)},
-            "ms_per_step": round(1e3 * elapsed / args.steps, 5),
-            "higher_is_better": True,
-            "scaling": "weak" if cfg["per_rank"] else "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (scene parameters of Waves.unity, seeded noise 20251121+tile)",
-            "config": {"workload": f"{args.config}: {cfg['desc']}", "n": n, "cascades": cfg["cascades"],
-                       "tiles_per_gpu": tiles, "tiles_total": job_oceans,
-                       "rank0_shard": {"cascades": [casc0, casc0 + C],
-                                       "columns": f"x = 2m + {parity}" if parity >= 0 else [x0, x0 + nx]},
-                       "schedule": "unfused" if args.unfused else "fused (pass A + pass B)",
-                       "parallelism": f"{'independent oceans' if cfg['per_rank'] else 'one job split'} "
-                                      f"over {world} GPU(s), no collective"},
+        out = headline(elapsed)
+        out["frame"]["ms_per_step_with_kernel_events"] = round(1e3 * elapsed_ev / args.steps, 5)
+        out.update({
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "measured_copy_GBs": HBM_COPY_GBS, "frac_of_measured_copy": round(achieved / HBM_COPY_GBS, 4),
@@ -824,16 +897,11 @@ def main():
                          "writes": writes, "memory_shape": shape},
             "kernels_us": {"pass_a" if not args.unfused else "rows": round(a_us, 3),
                            "pass_b" if not args.unfused else "cols": round(b_us, 3)},
-            "frame": {"algorithmic_bytes_per_gpu": B["frame"],
-                      "achieved_GBs_per_gpu": round(B["frame"] / (elapsed / args.steps) / 1e9, 1),
-                      "frac_per_gpu": round(B["frame"] / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-                      "frac_of_measured_copy_per_gpu": round(B["frame"] / (elapsed / args.steps) / 1e9 / HBM_COPY_GBS, 4),
-                      "ms_per_step_with_kernel_events": round(1e3 * elapsed_ev / args.steps, 5)},
             "ifft_stage": ifft_stage,
             "cache": cache,
             "update_loop": update,
             "cpu_baseline": cpu,
-        }
+        })
         print(json.dumps(out), flush=True)
     ctx.close()
     if world > 1:

@@ -11,7 +11,7 @@ TAG=${1:?tag}; shift
 CONFIG=${1:?config}; shift
 CMD=("$@")
 if [ ${#CMD[@]} -eq 0 ]; then
-    CMD=(python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-ifft-stage --no-beyond-cache --no-update-loop)
+    CMD=(python3 bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-ifft-stage --no-beyond-cache --no-update-loop)
 fi
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
