@@ -58,7 +58,11 @@ extern "C" {
  *      (Conventions).  New: ocean_readback_copy_ms.
  *   4  semantics changed: ocean_readback_copy_ms needs a request made with readback timing on
  *      (ocean_set_readback_timing; off by default, so a host that never asks for copy times
- *      records no timing events).  New: ocean_read_height_async, ocean_set_readback_timing. */
+ *      records no timing events).  New: ocean_read_height_async, ocean_set_readback_timing.
+ *      Added within version 4, with no change to any existing entry: ocean_query_surface,
+ *      ocean_query_surface_device, ocean_query_surface_async.  The version number does not tell
+ *      a library that has them from one that does not: a host that needs them probes for the
+ *      symbol (dlsym / EntryPointNotFoundException). */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -313,9 +317,56 @@ void ocean_readback_release(ocean_readback *rb);
 int ocean_read_height_async(ocean_ctx *ctx, int tile, int cascade, float *dst, size_t bytes,
                             ocean_readback **out);
 
+/* Surface queries: the point lookups of a buoyancy consumer done on the device, so that a host
+ * with M bodies moves M x 32 B per frame instead of a displacement slice (the reference reads
+ * slice 0 back every frame, WaterBody.cs:288-296, only for GetWaterHeight, :195-209, which
+ * BuoyantObject.FixedUpdate calls once per body).  Point i of `points` is (world x, world z) as
+ * float[2]; out[i] is float[8].  With S(p) = what ocean_sample_world returns for the point
+ * (p.x, p.z, lod 0) of tile `tile` (DERIV and TURB at level 0 also on OCEAN_F_MIPS contexts):
+ *
+ *   OCEAN_QUERY_SURFACE, iterations = K in [0, 16]: the height of the surface ABOVE q = (x, z).
+ *   The displacement is Lagrangian (the grid point p lands at p + D_xz(p)), so the water over q is
+ *   Dy(p*) with p* + D_xz(p*) = q; K steps of that fixed point, all in fp32 in this order:
+ *       p_0 = q;  for k < K:  D = S(p_k)[0..2],  p_{k+1} = (q.x - D.x, q.z - D.z);  D = S(p_K)[0..2]
+ *       out[8i + 0..3] = D.y, p_K.x, p_K.z, r = max(|(p_K.x + D.x) - q.x|, |(p_K.z + D.z) - q.z|)
+ *       out[8i + 4..7] = S(p_K)[8..10] (the normal at p_K), S(p_K)[3] (the foam at p_K)
+ *   r is the distance by which p_K misses q, i.e. the length of the step K + 1 would take.  The
+ *   iteration contracts where the displacement's Lipschitz constant is below 1 (no folded,
+ *   self-intersecting surface); elsewhere it stays bounded (|p_k - q| <= max |D_xz|) and r says so.
+ *   K = 0 is ocean_sample_world at q.  DISPLACEMENT_ONLY contexts give the normal (0, 1, 0), foam 0.
+ *
+ *   OCEAN_QUERY_REFERENCE, iterations = 0: GetWaterHeight's own texel pick (WaterBody.cs:195-209)
+ *   in fp32: a = -(N/2), b = N/2, u = saturate((x - a) / (b - a)), px = clamp((int)(u N), 0, N - 1),
+ *   py alike from z;  out[8i + 0..7] = DISP[tile * C + 0][py][px].y, (float)px, (float)py, 0, 0, 0, 0, 0
+ *   (cascade 0 of the tile, as the reference's slice 0).
+ *
+ * ocean_query_surface takes host buffers and blocks.  ocean_query_surface_device takes device
+ * pointers (points 4-B aligned, out 16-B aligned, else OCEAN_E_INVALID_ARG; any count >= 0) and is
+ * async on the ctx stream, ordered after the queued steps.  ocean_query_surface_async is the
+ * per-frame form: `points` is a host buffer consumed before the call returns (the caller may reuse
+ * it at once); the query runs on the ctx stream, after the steps queued so far and before later
+ * ones, and its count x 32 B land in `dst` on the copy stream like an ocean_read_async slice, with
+ * the same ocean_readback_status / _wait / _release / _copy_ms.
+ * All three: OCEAN_E_INVALID_ARG for a null pointer, count < 0, count > OCEAN_QUERY_MAX_POINTS (host
+ * and async forms), an unknown mode, iterations outside [0, 16] or nonzero in reference mode, or a
+ * tile out of range, all checked before any device call; then OCEAN_E_STATE before
+ * ocean_init_spectrum and OCEAN_E_UNSUPPORTED on a column-parity context (as world sampling).
+ * count = 0 is a no-op in the blocking and device forms and OCEAN_E_INVALID_ARG in the async form
+ * (there is no request to hand back). */
+#define OCEAN_QUERY_REFERENCE 0
+#define OCEAN_QUERY_SURFACE 1
+#define OCEAN_QUERY_MAX_POINTS 65536
+int ocean_query_surface(ocean_ctx *ctx, int tile, int mode, int iterations, const float *points, int count,
+                        float *out);
+int ocean_query_surface_device(ocean_ctx *ctx, int tile, int mode, int iterations, const float *points, int count,
+                               float *out);
+int ocean_query_surface_async(ocean_ctx *ctx, int tile, int mode, int iterations, const float *points, int count,
+                              float *dst, ocean_readback **out);
+
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
- * ocean_read_height_async request records HIP timing events around its device-to-host copy, for
- * ocean_readback_copy_ms.  Requests made while it is off record only untimed events. */
+ * ocean_read_height_async / ocean_query_surface_async request records HIP timing events around its
+ * device-to-host copy, for ocean_readback_copy_ms.  Requests made while it is off record only
+ * untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 
 /* Duration of a completed request's device-to-host copy in ms (HIP events on the copy stream around

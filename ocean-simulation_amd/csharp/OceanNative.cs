@@ -107,6 +107,15 @@ namespace OceanHip
         public static extern OceanStatus ocean_sample_world(IntPtr ctx, int tile, [In] float[] points, int count, [Out] float[] output);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_sample_world_device(IntPtr ctx, int tile, IntPtr points, int count, IntPtr output);
+        // Surface queries (added within ABI 4: a host that must run on an older version-4 library catches
+        // EntryPointNotFoundException on the first call).  mode: QueryReference / QuerySurface; 8 floats per point.
+        public const int QueryReference = 0, QuerySurface = 1, QueryMaxPoints = 65536;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_query_surface(IntPtr ctx, int tile, int mode, int iterations, [In] float[] points, int count, [Out] float[] output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_query_surface_device(IntPtr ctx, int tile, int mode, int iterations, IntPtr points, int count, IntPtr output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_query_surface_async(IntPtr ctx, int tile, int mode, int iterations, [In] float[] points, int count, IntPtr dst, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_read_async(IntPtr ctx, OceanTexture tex, int tile, int cascade, IntPtr dst, UIntPtr bytes, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

@@ -17,7 +17,11 @@ namespace OceanHip
     // What Update reads back every frame (ocean.h ocean_read_height_async): the height channel alone,
     // all GetWaterHeight reads (the reference's buoyancyData is private, WaterBody.cs:58, and .g is its
     // only use, :208), or the whole RGBA displacement slice as the reference requests it.
-    public enum Readback { Height, Rgba }
+    // Probes reads no slice back: Update issues one ocean_query_surface_async per frame for the world positions
+    // given to SetProbes (one per buoyant body) and ProbeHeights is the newest landed answer, 32 B per probe over
+    // the link.  In that mode GetWaterHeight keeps returning 0, as the reference does before its first readback,
+    // and buoyancyData stays empty.
+    public enum Readback { Height, Rgba, Probes }
 
     public sealed class WaterBodyNative : IDisposable
     {
@@ -32,10 +36,18 @@ namespace OceanHip
         public int device = 0;
         public ulong seed = 20251121;   // the reference's UnityEngine.Random is unseeded; this library's generator is
         public Readback readback = Readback.Height;  // set before Awake
+        public int probeMode = OceanNative.QuerySurface;  // Readback.Probes: ocean_query_surface_async's mode ...
+        public int probeIterations = 4;                   // ... and fixed-point steps (0 with QueryReference)
+        public int probeCapacity = 64;  // probes the pinned ring is sized for at Awake (or the probes set by then, if more)
 
         IntPtr ctx = IntPtr.Zero;
         float[] buoyancyData;           // displacement slice 0 (WaterBody.cs:58, :295): [y][x] heights, or RGBA [y][x][4]
-        int Floats => texturesSize * texturesSize * (readback == Readback.Height ? 1 : 4);  // per readback slice
+        float[] probes = new float[0];  // SetProbes' (world x, world z) pairs
+        float[] probeResults;           // the newest landed query, [M][8]
+        int probeCap;
+        // floats of one ring slot: a readback slice, or probeCap query results
+        int Floats => readback == Readback.Probes ? probeCap * 8
+                                                  : texturesSize * texturesSize * (readback == Readback.Height ? 1 : 4);
 
         public void Awake()
         {
@@ -48,6 +60,9 @@ namespace OceanHip
             ApplyParams();
             OceanNative.Check(OceanNative.ocean_generate_noise(ctx, seed), "ocean_generate_noise");
             OceanNative.Check(OceanNative.ocean_init_spectrum(ctx), "ocean_init_spectrum");
+            probeCap = Math.Max(Math.Max(probeCapacity, probes.Length / 2), 1);
+            if (readback == Readback.Probes && probeCap > OceanNative.QueryMaxPoints)
+                throw new InvalidOperationException("at most OceanNative.QueryMaxPoints probes");
             // readback ring: MaxReadbacksInFlight pinned slices allocated once, reused by every
             // request and freed only in Dispose (hipHostFree synchronizes the device: a free per
             // request would make each Update wait for the frame it just queued)
@@ -91,17 +106,22 @@ namespace OceanHip
         const int MaxReadbacksInFlight = 4;  // ring slots; the reference's request queue is engine-managed.
                                              // 2-4 in flight keep the 16 MiB copies back to back beside the
                                              // frames; 8 stretch each copy 2.5x (DESIGN.md section 1)
-        readonly System.Collections.Generic.Queue<(IntPtr req, IntPtr buf)> readbacks =
-            new System.Collections.Generic.Queue<(IntPtr req, IntPtr buf)>();
+        readonly System.Collections.Generic.Queue<(IntPtr req, IntPtr buf, int count)> readbacks =
+            new System.Collections.Generic.Queue<(IntPtr req, IntPtr buf, int count)>();  // count: Probes, the points asked
         readonly System.Collections.Generic.List<IntPtr> ring = new System.Collections.Generic.List<IntPtr>();
         readonly System.Collections.Generic.Stack<IntPtr> idle = new System.Collections.Generic.Stack<IntPtr>();
 
-        void Complete((IntPtr req, IntPtr buf) r, bool wait)
+        void Complete((IntPtr req, IntPtr buf, int count) r, bool wait)
         {
             int n = Floats;
             int st = wait ? (OceanNative.ocean_readback_wait(r.req) == OceanStatus.Ok ? 1 : -1)
                           : OceanNative.ocean_readback_status(r.req);
-            if (st == 1)
+            if (st == 1 && readback == Readback.Probes)
+            {
+                probeResults = new float[r.count * 8];
+                System.Runtime.InteropServices.Marshal.Copy(r.buf, probeResults, 0, r.count * 8);
+            }
+            else if (st == 1)
             {
                 buoyancyData ??= new float[n];
                 System.Runtime.InteropServices.Marshal.Copy(r.buf, buoyancyData, 0, n);
@@ -115,15 +135,20 @@ namespace OceanHip
             CalculateWavesTexturesAtTime(time);
             while (readbacks.Count > 0 && OceanNative.ocean_readback_status(readbacks.Peek().req) != 0)
                 Complete(readbacks.Dequeue(), false);
+            if (readback == Readback.Probes && probes.Length == 0) return;  // nobody asks: no request
             if (idle.Count == 0) Complete(readbacks.Dequeue(), true);  // every slot in flight: wait for the oldest
             var buf = idle.Pop();
             var bytes = (UIntPtr)(Floats * sizeof(float));
             IntPtr req;
-            var st = readback == Readback.Height
+            int count = probes.Length / 2;
+            // Probes: one query for every probe, in place of the slice request: 32 B per probe come back
+            var st = readback == Readback.Probes
+                         ? OceanNative.ocean_query_surface_async(ctx, 0, probeMode, probeIterations, probes, count, buf, out req)
+                     : readback == Readback.Height
                          ? OceanNative.ocean_read_height_async(ctx, 0, 0, buf, bytes, out req)
                          : OceanNative.ocean_read_async(ctx, OceanTexture.Displacement, 0, 0, buf, bytes, out req);
             if (st != OceanStatus.Ok) { idle.Push(buf); OceanNative.Check(st, "readback request"); }
-            readbacks.Enqueue((req, buf));
+            readbacks.Enqueue((req, buf, count));
         }
 
         public void WaitForReadbacks()
@@ -142,6 +167,30 @@ namespace OceanHip
             int y = Math.Clamp((int)(v * texturesSize), 0, texturesSize - 1);
             int t = y * texturesSize + x;
             return readback == Readback.Height ? buoyancyData[t] : buoyancyData[t * 4 + 1];  // .g = Dy
+        }
+
+        // The world positions Update asks about with Readback.Probes: [M][3] (x, y, z; x and z are used, as
+        // GetWaterHeight uses its worldPosition).  After Awake, at most the capacity the ring was sized for.
+        // Takes effect at the next Update; answers already in flight keep their own M.
+        public void SetProbes(float[] xyz)
+        {
+            if (ctx != IntPtr.Zero && readback == Readback.Probes && xyz.Length / 3 > probeCap)
+                throw new InvalidOperationException("more probes than the capacity the ring was sized for at Awake");
+            var p = new float[xyz.Length / 3 * 2];
+            for (int i = 0; i < xyz.Length / 3; i++) { p[2 * i] = xyz[3 * i]; p[2 * i + 1] = xyz[3 * i + 2]; }
+            probes = p;
+        }
+
+        // The newest landed query, [M][8] as ocean_query_surface returns it, or null before the first lands.
+        public float[] ProbeResults() => probeResults == null ? null : (float[])probeResults.Clone();
+
+        // The newest landed heights, [M] in SetProbes' order, or null before the first lands.
+        public float[] ProbeHeights()
+        {
+            if (probeResults == null) return null;
+            var h = new float[probeResults.Length / 8];
+            for (int i = 0; i < h.Length; i++) h[i] = probeResults[i * 8];
+            return h;
         }
 
         // What Water.shader reads at world positions (Water.shader:314-348): points are

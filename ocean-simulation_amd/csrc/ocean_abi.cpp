@@ -98,7 +98,7 @@ namespace ocean {
 void generate_noise_host(int n, uint64_t seed, float* out);
 }
 
-// Staging slots of ocean_read_async / ocean_read_height_async.  A slot is device memory as large as one
+// Staging slots of ocean_read_async / ocean_read_height_async / ocean_query_surface_async.  A slot is device memory as large as one
 // slice of the largest texture plus the events of the request holding it, created once with the slot: no
 // event is created per request.  `after` and `done` disable timing; the timed pair `tstart` / `tdone`
 // (ocean_readback_copy_ms) is created on the slot's first request made with readback timing on
@@ -106,8 +106,15 @@ void generate_noise_host(int n, uint64_t seed, float* out);
 // when it is released (after its host copy has landed), so a slot is never rewritten while a copy out of
 // it is pending, and no allocation or free sits between the context stream and the copy stream.  Shared
 // with the requests: it outlives a context destroyed before its requests are released.
+// A slot also holds the points and results of an ocean_query_surface_async request: results at its
+// base, the points behind them (kQueryPointsOffset), and, from the slot's first such request on, a
+// pinned host copy of the points (`pts_host`): the caller's buffer is consumed inside the call, and
+// the upload reads memory that stays put until the request is released.
+constexpr size_t kQueryPointsOffset = (size_t)OCEAN_QUERY_MAX_POINTS * 8 * sizeof(float);
+constexpr size_t kQuerySlotBytes = kQueryPointsOffset + (size_t)OCEAN_QUERY_MAX_POINTS * 2 * sizeof(float);
 struct StageSlot {
     void* mem = nullptr;
+    void* pts_host = nullptr;    // pinned, OCEAN_QUERY_MAX_POINTS points (ocean_query_surface_async only)
     hipEvent_t after = nullptr;  // the snapshot is in the slot (the copy stream waits for it)
     hipEvent_t done = nullptr;   // the host copy has landed (untimed requests)
     hipEvent_t tstart = nullptr, tdone = nullptr;  // timed requests: around the host copy itself
@@ -123,6 +130,7 @@ struct StagePool {
         (void)hipSetDevice(device);
         for (StageSlot* sl : all) {
             if (sl->mem) (void)hipFree(sl->mem);
+            if (sl->pts_host) (void)hipHostFree(sl->pts_host);
             for (hipEvent_t e : {sl->after, sl->done, sl->tstart, sl->tdone})
                 if (e) (void)hipEventDestroy(e);
             delete sl;
@@ -220,7 +228,7 @@ struct ocean_ctx {
     float4* deriv_mips = nullptr;  // OCEAN_F_MIPS chains (levels 1..log2 N per slice)
     float4* turb_mips = nullptr;
     size_t mip_chain = 0;
-    hipStream_t copy_stream = nullptr;  // ocean_read_async / ocean_read_height_async
+    hipStream_t copy_stream = nullptr;  // ocean_read_async / ocean_read_height_async / ocean_query_surface_async
     std::shared_ptr<StagePool> stage_pool;  // their staging slots
     bool readback_timing = false;           // ocean_set_readback_timing
     // host state.  `params` and the device `casc` are what the kernels run with; set_params
@@ -984,7 +992,8 @@ int start_readback(ocean_ctx* ctx, void* dst, size_t bytes, Snapshot&& snapshot,
     if (!ctx->stage_pool) {
         ctx->stage_pool = std::make_shared<StagePool>();
         ctx->stage_pool->device = ctx->device;
-        ctx->stage_pool->slot_bytes = ctx->texels() * 16;  // the largest slice (float4 textures)
+        // the largest slice (float4 textures), or a full surface query's points and results (N <= 256)
+        ctx->stage_pool->slot_bytes = std::max(ctx->texels() * 16, kQuerySlotBytes);
     }
     ocean_readback* rb = new (std::nothrow) ocean_readback();
     if (!rb) return fail(OCEAN_E_OUT_OF_MEMORY, "host allocation failed");
@@ -992,7 +1001,7 @@ int start_readback(ocean_ctx* ctx, void* dst, size_t bytes, Snapshot&& snapshot,
     rb->pool = ctx->stage_pool;
     rb->timed = ctx->readback_timing;
     hipError_t e = rb->pool->take(rb->timed, &rb->slot);
-    if (e == hipSuccess) e = snapshot(rb->slot->mem);
+    if (e == hipSuccess) e = snapshot(rb->slot);
     if (e == hipSuccess) e = hipEventRecord(rb->slot->after, ctx->stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(ctx->copy_stream, rb->slot->after, 0);
     if (e == hipSuccess && rb->timed) e = hipEventRecord(rb->slot->tstart, ctx->copy_stream);
@@ -1021,7 +1030,8 @@ int ocean_read_async(ocean_ctx* ctx, int texture, int tile, int cascade, void* d
     char* src = nullptr;
     if (int r = slice_ptr(ctx, texture, tile, cascade, bytes, &src)) return r;
     return start_readback(
-        ctx, dst, bytes, [&](void* slot) { return hipMemcpyAsync(slot, src, bytes, hipMemcpyDeviceToDevice, ctx->stream); },
+        ctx, dst, bytes,
+        [&](StageSlot* sl) { return hipMemcpyAsync(sl->mem, src, bytes, hipMemcpyDeviceToDevice, ctx->stream); },
         out);
 }
 
@@ -1037,8 +1047,8 @@ int ocean_read_height_async(ocean_ctx* ctx, int tile, int cascade, float* dst, s
     if (int r = slice_ptr(ctx, OCEAN_TEX_DISP, tile, cascade, ctx->texels() * 16, &src)) return r;
     return start_readback(
         ctx, dst, bytes,
-        [&](void* slot) {
-            return ocean::launch_extract_height(reinterpret_cast<const float4*>(src), static_cast<float*>(slot),
+        [&](StageSlot* sl) {
+            return ocean::launch_extract_height(reinterpret_cast<const float4*>(src), static_cast<float*>(sl->mem),
                                                 ctx->texels(), ctx->stream);
         },
         out);
@@ -1186,6 +1196,106 @@ int ocean_sample_world(ocean_ctx* ctx, int tile, const float* points, int count,
     if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
     if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
     return OCEAN_OK;
+}
+
+// Argument checks of the surface queries, before any device call (ocean.h); `limit`: the forms that
+// stage the points (host and async) take at most OCEAN_QUERY_MAX_POINTS.
+static int check_query(ocean_ctx* ctx, int tile, int mode, int iterations, const float* pts, int count, float* out,
+                       bool limit) {
+    if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+    if (!pts || !out) return fail(OCEAN_E_INVALID_ARG, "null points or output");
+    if (count < 0) return fail(OCEAN_E_INVALID_ARG, "negative point count");
+    if (limit && count > OCEAN_QUERY_MAX_POINTS)
+        return fail(OCEAN_E_INVALID_ARG, "point count " + std::to_string(count) + " > OCEAN_QUERY_MAX_POINTS");
+    if (mode != OCEAN_QUERY_REFERENCE && mode != OCEAN_QUERY_SURFACE) return fail(OCEAN_E_INVALID_ARG, "unknown query mode");
+    if (iterations < 0 || iterations > 16) return fail(OCEAN_E_INVALID_ARG, "iterations must be in [0, 16]");
+    if (mode == OCEAN_QUERY_REFERENCE && iterations != 0)
+        return fail(OCEAN_E_INVALID_ARG, "OCEAN_QUERY_REFERENCE takes iterations = 0");
+    if (tile < 0 || tile >= ctx->T) return fail(OCEAN_E_INVALID_ARG, "tile out of range");
+    return OCEAN_OK;
+}
+
+// ... and of the context's state, as world sampling: the cascade wavelengths exist only after init, and a
+// column-parity shard holds half the columns.
+static int check_query_state(const ocean_ctx* ctx) {
+    if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, "ocean_init_spectrum must precede ocean_query_surface");
+    if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, "surface query of a column-parity shard (half the columns)");
+    return OCEAN_OK;
+}
+
+// The query kernel on the ctx stream (device pointers; kind 2 of ocean_kernel_stats).
+static int launch_query(ocean_ctx* ctx, int tile, int mode, int iterations, const float* d_pts, int count,
+                        float* d_out) {
+    const ocean::DevView v = ctx->view();
+    return timed(ctx, 2,
+                 [&] { return ocean::launch_query_surface(v, tile, mode, iterations, d_pts, count, d_out, ctx->stream); },
+                 "query_surface");
+}
+
+int ocean_query_surface_device(ocean_ctx* ctx, int tile, int mode, int iterations, const float* points, int count,
+                               float* out) {
+    if (int r = check_query(ctx, tile, mode, iterations, points, count, out, false)) return r;
+    // the kernels read floats and write float4 rows (ocean.h)
+    if (((uintptr_t)points & 3) || ((uintptr_t)out & 15))
+        return fail(OCEAN_E_INVALID_ARG, "ocean_query_surface_device: points must be 4-byte and out 16-byte aligned");
+    if (int r = check_query_state(ctx)) return r;
+    if (count == 0) return OCEAN_OK;
+    OCEAN_ENTER(ctx);
+    return launch_query(ctx, tile, mode, iterations, points, count, out);
+}
+
+int ocean_query_surface(ocean_ctx* ctx, int tile, int mode, int iterations, const float* points, int count,
+                        float* out) {
+    if (int r = check_query(ctx, tile, mode, iterations, points, count, out, true)) return r;
+    if (int r = check_query_state(ctx)) return r;
+    if (count == 0) return OCEAN_OK;
+    OCEAN_ENTER(ctx);
+    const size_t in_bytes = (size_t)count * 2 * 4, out_bytes = (size_t)count * 8 * 4;
+    const size_t out_off = (in_bytes + 255) & ~(size_t)255;  // float4 output rows stay 16-B aligned
+    void* d = nullptr;
+    OCEAN_HIP(hipMallocAsync(&d, out_off + out_bytes, ctx->stream));
+    float* d_in = static_cast<float*>(d);
+    float* d_out = reinterpret_cast<float*>(static_cast<char*>(d) + out_off);
+    hipError_t e = hipMemcpyAsync(d_in, points, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+    int r = OCEAN_OK;
+    if (e == hipSuccess) r = launch_query(ctx, tile, mode, iterations, d_in, count, d_out);
+    if (e == hipSuccess && r == OCEAN_OK) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t ef = hipFreeAsync(d, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (r != OCEAN_OK) return r;
+    if (e != hipSuccess) return hip_fail(e, "ocean_query_surface copy");
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
+    return OCEAN_OK;
+}
+
+int ocean_query_surface_async(ocean_ctx* ctx, int tile, int mode, int iterations, const float* points, int count,
+                              float* dst, ocean_readback** out) {
+    if (!out) return fail(OCEAN_E_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (int r = check_query(ctx, tile, mode, iterations, points, count, dst, true)) return r;
+    if (count == 0) return fail(OCEAN_E_INVALID_ARG, "ocean_query_surface_async: no points, so no request");
+    if (int r = check_query_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    const size_t in_bytes = (size_t)count * 2 * 4;
+    return start_readback(
+        ctx, dst, (size_t)count * 8 * 4,
+        [&](StageSlot* sl) {
+            // the caller's points are consumed here, into pinned memory the slot owns: the upload below is
+            // then truly asynchronous and reads nothing of the caller's after this call returns
+            if (!sl->pts_host) {
+                const hipError_t e = hipHostMalloc(&sl->pts_host, kQuerySlotBytes - kQueryPointsOffset, hipHostMallocDefault);
+                if (e != hipSuccess) return e;
+            }
+            std::memcpy(sl->pts_host, points, in_bytes);
+            float* d_pts = reinterpret_cast<float*>(static_cast<char*>(sl->mem) + kQueryPointsOffset);
+            const hipError_t e = hipMemcpyAsync(d_pts, sl->pts_host, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) return e;
+            return launch_query(ctx, tile, mode, iterations, d_pts, count, static_cast<float*>(sl->mem)) == OCEAN_OK
+                       ? hipSuccess
+                       : hipErrorLaunchFailure;
+        },
+        out);
 }
 
 int ocean_set_column_band(ocean_ctx* ctx, int x_begin, int x_count) {

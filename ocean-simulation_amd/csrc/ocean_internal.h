@@ -1,5 +1,5 @@
 // Internal declarations shared by the C-ABI layer (ocean_abi.cpp) and the HIP
-// kernel translation units (spectrum.hip, fft2/3/4k.hip, mips.hip).  Not part of the ABI.
+// kernel translation units (spectrum.hip, fft2/3/4k.hip, mips.hip, sample.hip, query.hip).  Not part of the ABI.
 #pragma once
 
 #include <hip/hip_ext.h>
@@ -129,6 +129,9 @@ hipError_t launch_mips(const DevView& v, hipStream_t s);
 hipError_t launch_extract_height(const float4* disp_slice, float* dst, size_t texels, hipStream_t s);
 // sample.hip: cascade-summed world sampling (Water.shader:314-348), device pointers
 hipError_t launch_sample_world(const DevView& v, int tile, const float* pts, int count, float* out, hipStream_t s);
+// query.hip: surface queries (ocean_query_surface*), device pointers: pts float[count][2], out float[count][8]
+hipError_t launch_query_surface(const DevView& v, int tile, int mode, int iterations, const float* pts, int count,
+                                float* out, hipStream_t s);
 
 // fft4k.hip (N = 2048, 4096): four-step column passes C1 (in place on the
 // 16-wide tile-major intermediate) + C2 (with the pass-B epilogue); replace pass B.

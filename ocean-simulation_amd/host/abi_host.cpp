@@ -4,8 +4,12 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes]
 //
+// With probes the host reads no slice back: it sets five probes, runs F Updates (one surface query per
+// frame, water_body.h Readback::Probes) and writes probe_heights.bin (float32 [F][5]: ProbeHeights after
+// each Update, zeros before any query has landed), probe_results.bin (float32 [5][8]: the last query,
+// after WaitForReadbacks) and the summary line; tests/test_gpu_query_host.py checks them.
 // The readback mode (water_body.h Readback) defaults to height.  Writes <outdir>/buoyancy0.bin
 // (buoyancyData after the first F frames, float32 [n][n] heights, or [n][n][4] with rgba),
 // buoyancy1.bin (after OnValidate + one frame), heights.bin (float32
@@ -32,12 +36,12 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
-    if (mode != "height" && mode != "rgba") {
-        std::fprintf(stderr, "usage: readback mode must be height or rgba\n");
+    if (mode != "height" && mode != "rgba" && mode != "probes") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba or probes\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -58,7 +62,33 @@ int main(int argc, char** argv) {
         wb.texturesSize = n;
         wb.cascades.assign(scene, scene + (C < 4 ? C : 4));
         wb.seed = 42;
-        wb.readback = mode == "height" ? ocean_host::Readback::Height : ocean_host::Readback::Rgba;
+        wb.readback = mode == "height"  ? ocean_host::Readback::Height
+                      : mode == "rgba" ? ocean_host::Readback::Rgba
+                                       : ocean_host::Readback::Probes;
+        if (mode == "probes") {
+            // five bodies; Update asks for the surface above each (surface mode, 4 steps: the facade's defaults)
+            const std::vector<float> bodies = {0.0f,   0.0f, 0.0f,    37.5f,    1.0f, -12.25f, -410.0f, 0.0f,
+                                               250.75f, 1e4f, -2.0f, -3333.0f, -0.5f, 0.0f,    (float)n};
+            const size_t M = bodies.size() / 3;
+            wb.probeCapacity = M;
+            wb.SetProbes(bodies);
+            wb.Awake();
+            std::vector<float> heights;
+            for (int f = 0; f < F; ++f) {
+                wb.Update((float)f / 60.0f);
+                std::vector<float> h = wb.ProbeHeights();
+                h.resize(M, 0.0f);  // zeros before any query has landed
+                heights.insert(heights.end(), h.begin(), h.end());
+            }
+            wb.WaitForReadbacks();
+            write_bin(out + "/probe_heights.bin", heights.data(), heights.size());
+            const std::vector<float> last = wb.ProbeResults();
+            write_bin(out + "/probe_results.bin", last.data(), last.size());
+            std::printf("{\"frames\": %d, \"requested\": %ld, \"completed\": %ld, \"n\": %d, \"cascades\": %d, "
+                        "\"probes\": %zu}\n", F, wb.requested(), wb.completed(), n, (int)wb.cascades.size(), M);
+            wb.OnDisable();
+            return 0;
+        }
         wb.Awake();
         const float probe[4][2] = {{0.0f, 0.0f}, {-(float)n / 2, -(float)n / 2}, {(float)n / 2 - 1, 50.0f}, {500.0f, -500.0f}};
         std::vector<float> heights;

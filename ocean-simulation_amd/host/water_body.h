@@ -27,7 +27,11 @@ inline void check(int rc, const char* where) {
 // What Update reads back every frame: the height channel GetWaterHeight reads (ocean_read_height_async,
 // 4 B per texel; the reference's buoyancyData is private, WaterBody.cs:58, and .g is all its reader uses)
 // or the whole RGBA displacement slice (ocean_read_async, 16 B per texel) as the reference requests it.
-enum class Readback { Height, Rgba };
+// Probes reads no slice back: Update issues one ocean_query_surface_async per frame for the world positions
+// given to SetProbes (one per buoyant body) and ProbeHeights is the newest landed answer, 32 B per probe over
+// the link.  In that mode GetWaterHeight keeps returning 0, as the reference does before its first readback,
+// and buoyancyData stays empty.
+enum class Readback { Height, Rgba, Probes };
 
 struct WaterCascade {  // WaterCascade.cs:10-24 (script defaults)
     float wavelength = 10.0f, cutoffHigh = 5.0f, cutoffLow = 0.0001f, swell = 0.4f, fade = 0.1f;
@@ -45,6 +49,9 @@ public:
     size_t maxReadbacksInFlight = 4;  // bound on queued requests (set before Awake): 2-4 keep the copies back to
                                       // back beside the frames; 8 stretch each
     Readback readback = Readback::Height;  // set before Awake
+    int probeMode = OCEAN_QUERY_SURFACE;   // Readback::Probes: ocean_query_surface_async's mode ...
+    int probeIterations = 4;               // ... and fixed-point steps (0 with OCEAN_QUERY_REFERENCE)
+    size_t probeCapacity = 64;  // probes the pinned ring is sized for at Awake (or the probes set by then, if more)
 
     WaterBody() = default;
     WaterBody(const WaterBody&) = delete;
@@ -56,6 +63,9 @@ public:
         ApplyParams();
         check(ocean_generate_noise(ctx_, seed), "ocean_generate_noise");
         check(ocean_init_spectrum(ctx_), "ocean_init_spectrum");
+        probe_cap_ = std::max<size_t>({probeCapacity, probes_.size() / 2, 1});
+        if (readback == Readback::Probes && probe_cap_ > OCEAN_QUERY_MAX_POINTS)
+            throw std::runtime_error("at most OCEAN_QUERY_MAX_POINTS probes");
         // the readback ring: maxReadbacksInFlight pinned slices, plus the one the last landed slice stays
         // in, allocated once and reused, freed only in OnDisable (hipHostFree synchronizes the device,
         // so a free per request would make every Update wait for the frame it just queued)
@@ -85,6 +95,7 @@ public:
             if (st == 0) break;
             Complete(st);
         }
+        if (readback == Readback::Probes && probes_.empty()) return;  // nobody asks: no request
         // at most maxReadbacksInFlight requests queued (the ring's extra slot holds the landed slice):
         // when full, wait for the oldest
         while (!readbacks_.empty() && (readbacks_.size() >= std::max<size_t>(maxReadbacksInFlight, 1) || free_.empty())) {
@@ -94,12 +105,19 @@ public:
         Pending p;
         p.buf = free_.back();
         free_.pop_back();
-        const int rc = readback == Readback::Height
+        p.count = probes_.size() / 2;
+        // Probes: one query for every probe, in place of the slice request: 32 B per probe come back
+        const int rc = readback == Readback::Probes
+                           ? ocean_query_surface_async(ctx_, 0, probeMode, probeIterations, probes_.data(), (int)p.count,
+                                                       static_cast<float*>(p.buf), &p.req)
+                       : readback == Readback::Height
                            ? ocean_read_height_async(ctx_, 0, 0, static_cast<float*>(p.buf), SliceBytes(), &p.req)
                            : ocean_read_async(ctx_, OCEAN_TEX_DISP, 0, 0, p.buf, SliceBytes(), &p.req);
         if (rc != OCEAN_OK) {
             free_.push_back(p.buf);
-            check(rc, readback == Readback::Height ? "ocean_read_height_async" : "ocean_read_async");
+            check(rc, readback == Readback::Probes   ? "ocean_query_surface_async"
+                      : readback == Readback::Height ? "ocean_read_height_async"
+                                                     : "ocean_read_async");
         }
         readbacks_.push_back(p);
         ++requested_;
@@ -114,7 +132,7 @@ public:
 
     // WaterBody.cs:195-209, with its mapping of world x, z over [-texturesSize/2, texturesSize/2].
     float GetWaterHeight(float worldX, float worldZ) const {
-        if (!held_) return 0.0f;
+        if (!held_ || readback == Readback::Probes) return 0.0f;
         auto inverse_lerp = [](float a, float b, float v) {
             return a == b ? 0.0f : std::min(std::max((v - a) / (b - a), 0.0f), 1.0f);
         };
@@ -125,6 +143,33 @@ public:
         const int y = std::min(std::max((int)(v * n), 0), n - 1);
         const size_t t = (size_t)y * n + x;
         return readback == Readback::Height ? held_[t] : held_[t * 4 + 1];  // .g = Dy
+    }
+
+    // The world positions Update asks about with Readback::Probes: [M][3] (x, y, z; x and z are used, as
+    // GetWaterHeight uses its worldPosition).  After Awake, at most the capacity the ring was sized for.
+    // Takes effect at the next Update; answers already in flight keep their own M.
+    void SetProbes(const std::vector<float>& xyz) {
+        if (ctx_ && readback == Readback::Probes && xyz.size() / 3 > probe_cap_)
+            throw std::runtime_error("more probes than the capacity the ring was sized for at Awake");
+        probes_.clear();
+        for (size_t i = 0; i + 2 < xyz.size(); i += 3) {
+            probes_.push_back(xyz[i]);
+            probes_.push_back(xyz[i + 2]);
+        }
+    }
+
+    // The newest landed query, [M][8] as ocean_query_surface returns it, or empty before the first lands.
+    std::vector<float> ProbeResults() const {
+        if (readback != Readback::Probes || !held_) return {};
+        return std::vector<float>(held_, held_ + held_count_ * 8);
+    }
+
+    // The newest landed heights, [M] in SetProbes' order, or empty before the first lands.
+    std::vector<float> ProbeHeights() const {
+        std::vector<float> h;
+        if (readback != Readback::Probes || !held_) return h;
+        for (size_t i = 0; i < held_count_; ++i) h.push_back(held_[i * 8]);
+        return h;
     }
 
     // What Water.shader reads at world positions (x, z, lod) -> 12 floats per point.
@@ -144,7 +189,7 @@ public:
         for (auto& p : readbacks_) ocean_readback_release(p.req);
         readbacks_.clear();
         if (held_slot_) {  // the last landed slice outlives the pinned ring
-            last_.assign(held_, held_ + SliceBytes() / 4);
+            last_.assign(held_, held_ + HeldFloats());
             held_ = last_.data();
             held_slot_ = nullptr;
         }
@@ -159,11 +204,11 @@ public:
     // or [y][x][rgba] (Readback::Rgba); empty before the first readback lands.  Copied out of its pinned slot once, on the first call after it lands; later
     // calls return the same array until the next readback lands (the reference reads a field).
     const std::vector<float>& buoyancyData() {
-        if (held_ && !buoy_valid_) {
+        if (held_ && !buoy_valid_ && readback != Readback::Probes) {
             buoy_.assign(held_, held_ + SliceBytes() / 4);
             buoy_valid_ = true;
         }
-        if (!held_) buoy_.clear();
+        if (!held_ || readback == Readback::Probes) buoy_.clear();
         return buoy_;
     }
     long requested() const { return requested_; }
@@ -173,18 +218,27 @@ private:
     struct Pending {
         ocean_readback* req = nullptr;
         void* buf = nullptr;
+        size_t count = 0;  // Probes: the points of this request
     };
     ocean_ctx* ctx_ = nullptr;
     std::deque<Pending> readbacks_;
     std::vector<void*> free_, owned_;  // pinned readback ring: idle slots, all slots
     const float* held_ = nullptr;  // the last landed slice, in its pinned slot (out of the ring)
     void* held_slot_ = nullptr;
+    size_t held_count_ = 0;       // Probes: the points of the landed query
+    std::vector<float> probes_;   // SetProbes' (world x, world z) pairs
+    size_t probe_cap_ = 0;
     std::vector<float> last_;  // the last slice after OnDisable
     std::vector<float> buoy_;  // buoyancyData's copy of the held slice
     bool buoy_valid_ = false;
     long requested_ = 0, completed_ = 0;
 
-    size_t SliceBytes() const { return (size_t)texturesSize * texturesSize * (readback == Readback::Height ? 4 : 16); }
+    // bytes of one ring slot: a readback slice, or probe_cap_ query results
+    size_t SliceBytes() const {
+        if (readback == Readback::Probes) return probe_cap_ * 32;
+        return (size_t)texturesSize * texturesSize * (readback == Readback::Height ? 4 : 16);
+    }
+    size_t HeldFloats() const { return readback == Readback::Probes ? held_count_ * 8 : SliceBytes() / 4; }
 
     void ApplyParams() {
         ocean_params p{windSpeed, windDirectionX, windDirectionY, gravity, fetch, depth};
@@ -206,6 +260,7 @@ private:
             if (held_slot_) free_.push_back(held_slot_);
             held_slot_ = p.buf;
             held_ = static_cast<const float*>(p.buf);
+            held_count_ = p.count;
             buoy_valid_ = false;
             ++completed_;
         } else {

@@ -63,8 +63,12 @@ EXPORTED_SYMBOLS = (
     "ocean_readback_copy_ms", "ocean_read_height_async", "ocean_set_readback_timing",
     "ocean_host_alloc", "ocean_host_free", "ocean_last_error", "ocean_abi_version", "ocean_set_column_band",
     "ocean_reset_foam", "ocean_sample_world", "ocean_sample_world_device", "ocean_kernel_name",
-    "ocean_set_column_parity",
+    "ocean_set_column_parity", "ocean_query_surface", "ocean_query_surface_device", "ocean_query_surface_async",
 )
+
+# ocean_query_surface* modes and limits (ocean.h)
+QUERY_REFERENCE, QUERY_SURFACE = 0, 1
+QUERY_MAX_POINTS = 65536
 
 
 class OceanError(RuntimeError):
@@ -136,6 +140,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_abi_version": ([], i),
         "ocean_set_column_band": ([P, i, i], i),
         "ocean_set_column_parity": ([P, i], i),
+        "ocean_query_surface": ([P, i, i, i, P, i, P], i),
+        "ocean_query_surface_device": ([P, i, i, i, P, i, P], i),
+        "ocean_query_surface_async": ([P, i, i, i, P, i, P, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -265,6 +272,31 @@ class OceanContext:
                "ocean_sample_world")
         return out
 
+    @staticmethod
+    def _query_points(points) -> np.ndarray:
+        p = np.ascontiguousarray(points, np.float32)
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"points must be float32[M][2] = (world x, world z), got {p.shape}")
+        return p
+
+    def query_surface(self, points, tile: int = 0, mode: int = QUERY_SURFACE, iterations: int = 4) -> np.ndarray:
+        """Surface queries on the device (ocean.h ocean_query_surface), blocking: points float[M][2] =
+        (world x, world z) -> float32[M][8].  QUERY_SURFACE: (height of the surface above the point,
+        p.x, p.z, residual, normal x, y, z, foam) after `iterations` fixed-point steps of p + D_xz(p) = q;
+        QUERY_REFERENCE (iterations 0): (GetWaterHeight's texel .y, px, py, 0, 0, 0, 0, 0)."""
+        p = self._query_points(points)
+        out = np.empty((p.shape[0], 8), np.float32)
+        _check(self.lib.ocean_query_surface(self._h, tile, mode, iterations, p.ctypes.data, p.shape[0],
+                                            out.ctypes.data), "ocean_query_surface")
+        return out
+
+    def query_surface_async(self, points, tile: int = 0, mode: int = QUERY_SURFACE, iterations: int = 4,
+                            buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_query_surface_async): the query runs behind the queued steps and its
+        float32[M][8] lands in pinned host memory like a read_async slice; `points` is consumed by the call.
+        Poll .done() / .wait(), then .data; `buf`: a caller-owned pinned slot of at least M x 32 B."""
+        return Readback(self, TEX_DISP, tile, 0, buf, query=(self._query_points(points), mode, iterations))
+
     def read_async(self, tex: int, tile: int = 0, cascade: int = 0, buf: "PinnedBuffer" = None) -> "Readback":
         """AsyncGPUReadback.Request (WaterBody.cs:288-296): copy one slice into pinned
         host memory once the queued steps finish; poll .done() / .wait(), then .data.
@@ -349,34 +381,46 @@ class PinnedBuffer:
 
 
 class Readback:
-    """One ocean_read_async (or, `height`, ocean_read_height_async) request into pinned host memory:
-    a caller's PinnedBuffer slot, or one of its own (freed by release())."""
+    """One ocean_read_async (or, `height`, ocean_read_height_async; or, `query` = (points float32[M][2],
+    mode, iterations), ocean_query_surface_async) request into pinned host memory: a caller's PinnedBuffer
+    slot, or one of its own (freed by release())."""
 
     def __init__(self, ctx: "OceanContext", tex: int, tile: int, cascade: int, buf: Optional[PinnedBuffer] = None,
-                 height: bool = False):
+                 height: bool = False, query: Optional[tuple] = None):
         self.lib = ctx.lib
-        ch = 1 if height else _TEX_CHANNELS[tex]
-        self.shape = (ctx.n, ctx.n) if height else (ctx.n, ctx.n, ch)
-        self.nbytes = ctx.n * ctx.n * ch * 4
+        if query is not None:
+            self.shape = (query[0].shape[0], 8)
+            self.nbytes = query[0].shape[0] * 32
+        else:
+            ch = 1 if height else _TEX_CHANNELS[tex]
+            self.shape = (ctx.n, ctx.n) if height else (ctx.n, ctx.n, ch)
+            self.nbytes = ctx.n * ctx.n * ch * 4
         self._h = ctypes.c_void_p()
         self.slot = buf
         self._own = buf is None
         if buf is None:
-            buf = PinnedBuffer(self.nbytes)
+            buf = PinnedBuffer(max(self.nbytes, 32))  # (an empty query still reaches the library, which refuses it)
         elif buf.nbytes < self.nbytes:
-            raise ValueError(f"pinned slot of {buf.nbytes} B < slice {self.nbytes} B")
+            raise ValueError(f"pinned slot of {buf.nbytes} B < request {self.nbytes} B")
         self._pinned = buf
         self._buf = buf.ptr
-        if height:
+        if query is not None:
+            where = "ocean_query_surface_async"
+            pts, mode, iterations = query
+            rc = self.lib.ocean_query_surface_async(ctx._h, tile, mode, iterations, pts.ctypes.data, pts.shape[0],
+                                                    self._buf, ctypes.byref(self._h))
+        elif height:
+            where = "ocean_read_height_async"
             rc = self.lib.ocean_read_height_async(ctx._h, tile, cascade, self._buf, self.nbytes, ctypes.byref(self._h))
         else:
+            where = "ocean_read_async"
             rc = self.lib.ocean_read_async(ctx._h, tex, tile, cascade, self._buf, self.nbytes, ctypes.byref(self._h))
         if rc != OK:
             if self._own:
                 buf.release()
             self._pinned = None
             self._buf = ctypes.c_void_p()
-            _check(rc, "ocean_read_height_async" if height else "ocean_read_async")
+            _check(rc, where)
 
     def done(self) -> bool:
         rc = self.lib.ocean_readback_status(self._h)
@@ -456,6 +500,11 @@ class WaterBody:
     (ocean_read_height_async, 4 B per texel: the reference's buoyancyData is private,
     WaterBody.cs:58, and that is its only reader); "rgba" requests the whole Color slice
     (16 B per texel) as the reference does.  GetWaterHeight returns the same bits in both.
+    "probes" reads no slice back: SetProbes(points) names the world positions a consumer asks
+    about (one per buoyant body), Update issues one ocean_query_surface_async per frame for them
+    (probeMode, probeIterations) and ProbeHeights is the newest landed answer, 32 B per probe over
+    the link.  In this mode GetWaterHeight keeps returning 0, as the reference does before its
+    first readback, and buoyancyData stays None.
     """
     windSpeed: float = 1.0
     windDirection: tuple = (1.0, 1.0)
@@ -471,9 +520,15 @@ class WaterBody:
     mips: bool = True  # WaterBody.cs:228-229 creates DERIV / TURB with mip chains
     device: int = 0
     noise: Optional[np.ndarray] = None  # explicit noise texture (tile 0), float32[N][N][2]
-    readback: str = "height"  # "height" (DISP.y only) or "rgba" (the whole displacement slice)
+    readback: str = "height"  # "height" (DISP.y only), "rgba" (the whole displacement slice) or "probes"
+    probeMode: int = QUERY_SURFACE  # readback "probes": ocean_query_surface_async's mode ...
+    probeIterations: int = 4        # ... and fixed-point steps (0 with QUERY_REFERENCE)
+    probeCapacity: int = 64         # probes the pinned ring is sized for at Awake (or the probes set by then, if more)
 
     def __post_init__(self):
+        self._probes: Optional[np.ndarray] = None  # SetProbes' (world x, world z), float32[M][2]
+        self._probe_cap = 0
+        self._probe_view: Optional[np.ndarray] = None  # the last landed [M][8], a view of the held pinned slot
         self.ctx: Optional[OceanContext] = None
         self._buoy: Optional[np.ndarray] = None  # the last landed slice: a view of the held pinned slot
         self._readbacks: List[Readback] = []
@@ -501,10 +556,16 @@ class WaterBody:
         else:
             self.ctx.generate_noise(self.seed)
         self.ctx.init_spectrum()
-        if self.readback not in ("height", "rgba"):
-            raise ValueError(f"readback must be 'height' or 'rgba', got {self.readback!r}")
+        if self.readback not in ("height", "rgba", "probes"):
+            raise ValueError(f"readback must be 'height', 'rgba' or 'probes', got {self.readback!r}")
         self._timed = False
-        slice_bytes = self.texturesSize * self.texturesSize * (4 if self.readback == "height" else 16)
+        if self.readback == "probes":
+            self._probe_cap = max(int(self.probeCapacity), 0 if self._probes is None else len(self._probes), 1)
+            if self._probe_cap > QUERY_MAX_POINTS:
+                raise ValueError(f"at most {QUERY_MAX_POINTS} probes, got {self._probe_cap}")
+            slice_bytes = self._probe_cap * 32
+        else:
+            slice_bytes = self.texturesSize * self.texturesSize * (4 if self.readback == "height" else 16)
         # one slot more than the requests in flight: the one the last landed slice stays in
         self._ring = [PinnedBuffer(slice_bytes) for _ in range(self._in_flight() + 1)]
         self._idle = list(self._ring)
@@ -536,6 +597,8 @@ class WaterBody:
         each completed one refreshes buoyancyData, as the reference's callback does (:292-295)."""
         self.CalculateWavesTexturesAtTime(time)
         self._poll_readbacks()
+        if self.readback == "probes" and (self._probes is None or len(self._probes) == 0):
+            return  # nobody asks: no request
         # at most MAX_READBACKS_IN_FLIGHT requests queued (the ring's extra slot holds the landed slice):
         # when full, wait for the oldest
         while self._readbacks and (len(self._readbacks) >= self._in_flight() or not self._idle):
@@ -545,7 +608,10 @@ class WaterBody:
             self.ctx.set_readback_timing(self._timed)
         slot = self._idle.pop()
         try:
-            if self.readback == "height":
+            if self.readback == "probes":
+                # one query for every probe, in place of the slice request: 32 B per probe come back
+                rb = self.ctx.query_surface_async(self._probes, 0, self.probeMode, self.probeIterations, slot)
+            elif self.readback == "height":
                 rb = self.ctx.read_height_async(0, 0, slot)
             else:
                 rb = self.ctx.read_async(TEX_DISP, 0, 0, slot)
@@ -570,8 +636,31 @@ class WaterBody:
         if self._held is not None:
             self._idle.append(self._held)
         self._held = slot
+        if self.readback == "probes":  # buoyancyData is not filled: GetWaterHeight keeps returning 0
+            self._probe_view = view
+            return
         self._buoy = view
         self._buoy_copy = None
+
+    def SetProbes(self, points) -> None:
+        """The world positions Update asks about in readback "probes": [M][3] (x, y, z; x and z are
+        used, as GetWaterHeight uses its worldPosition).  After Awake, at most the capacity the ring
+        was sized for.  Takes effect at the next Update; answers already in flight keep their own M."""
+        p = np.asarray(points, np.float32).reshape(-1, 3)
+        if self.ctx is not None and self.readback == "probes" and len(p) > self._probe_cap:
+            raise ValueError(f"{len(p)} probes > the capacity {self._probe_cap} the ring was sized for at Awake")
+        self._probes = np.ascontiguousarray(p[:, [0, 2]])
+
+    @property
+    def ProbeResults(self) -> Optional[np.ndarray]:
+        """The newest landed query, float32[M][8] as ocean_query_surface returns it (a copy), or None
+        before the first lands."""
+        return None if self._probe_view is None else np.array(self._probe_view)
+
+    @property
+    def ProbeHeights(self) -> Optional[np.ndarray]:
+        """The newest landed heights, float32[M] in SetProbes' order, or None before the first lands."""
+        return None if self._probe_view is None else np.array(self._probe_view[:, 0])
 
     @property
     def buoyancyData(self) -> Optional[np.ndarray]:
@@ -632,6 +721,8 @@ class WaterBody:
         self._readbacks = []
         if self._buoy is not None:  # the last landed slice outlives the pinned ring
             self._buoy = self.buoyancyData
+        if self._probe_view is not None:
+            self._probe_view = np.array(self._probe_view)
         for b in self._ring:
             b.release()
         self._ring, self._idle, self._held = [], [], None
