@@ -62,7 +62,9 @@ extern "C" {
  *      Added within version 4, with no change to any existing entry: ocean_query_surface,
  *      ocean_query_surface_device, ocean_query_surface_async.  The version number does not tell
  *      a library that has them from one that does not: a host that needs them probes for the
- *      symbol (dlsym / EntryPointNotFoundException). */
+ *      symbol (dlsym / EntryPointNotFoundException).
+ *      Added later within version 4 in the same way: ocean_surface_grid, ocean_surface_grid_device,
+ *      ocean_surface_grid_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -363,10 +365,61 @@ int ocean_query_surface_device(ocean_ctx *ctx, int tile, int mode, int iteration
 int ocean_query_surface_async(ocean_ctx *ctx, int tile, int mode, int iterations, const float *points, int count,
                               float *dst, ocean_readback **out);
 
+/* Surface grids: the surface over the nodes of a regular grid, for the consumers that read it over an
+ * area and not at scattered points.  The reference's renderer builds a regular plane
+ * (MeshGenerator.cs:19-35: planeSize / trianglesSize cells a side, 101 x 101 vertices by default) and
+ * the domain stage of Water.shader (:314-334) moves every vertex by the cascade-summed displacement at
+ * its world position; a heightfield collider, a top-down map or a shoreline pass wants the height above
+ * every node.  No point list is passed: the grid is six numbers, (x0, z0, dx, dz, nx, ny).  Node (i, j),
+ * i < nx along world x and j < ny along world z, lies at
+ *       q.x = x0 + (float)i * dx,   q.z = z0 + (float)j * dz     (one fp32 multiply and one fp32 add each)
+ * and its result is element k = j * nx + i of `out`.  Zero and negative spacings are valid.  With S(p)
+ * what ocean_sample_world returns for the point (p.x, p.z, lod) of tile `tile`:
+ *
+ *   OCEAN_GRID_VERTICES, iterations = 0, lod >= 0: the displaced mesh of the domain stage.
+ *       out[8k + 0..3] = q.x + S(q)[0], S(q)[1], q.z + S(q)[2], S(q)[3]   (the vertex, fp32 adds; the foam)
+ *       out[8k + 4..7] = S(q)[8..11]                                      (the normal, 0)
+ *   DERIV and TURB use `lod` exactly as ocean_sample_world does (trilinear on OCEAN_F_MIPS contexts,
+ *   level 0 otherwise); DISP is always read at level 0.
+ *
+ *   OCEAN_GRID_SURFACE, iterations = K in [0, 16], lod = 0: the Eulerian surface.  out[8k + 0..7] is the
+ *   8-float record of OCEAN_QUERY_SURFACE for the point q with K iterations, bit for bit.
+ *
+ *   OCEAN_GRID_HEIGHTFIELD, same arguments: element 0 of that record alone, float[ny][nx]: 4 B per node
+ *   for colliders and readbacks.
+ *
+ * `bytes` must equal nx * ny * 32 (vertices, surface) or nx * ny * 4 (heightfield).
+ * ocean_surface_grid: `out` is a host buffer; blocks, as ocean_query_surface.
+ * ocean_surface_grid_device: `out` is a device pointer, 16-B aligned in every mode (else
+ * OCEAN_E_INVALID_ARG); async on the ctx stream, ordered after the queued steps: a renderer's vertex
+ * buffer is filled with no host copy.
+ * ocean_surface_grid_async: `out` is a host destination (pinned, ocean_host_alloc, for a truly
+ * asynchronous copy).  The grid is computed into a readback slot on the ctx stream, after the steps
+ * queued so far and before later ones, and copied on the copy stream like an ocean_read_async slice,
+ * with the same ocean_readback_status / _wait / _release / _copy_ms.  The result must fit a slot:
+ * bytes <= max(N * N * 16, OCEAN_QUERY_MAX_POINTS * 40), else OCEAN_E_INVALID_ARG.  *req is NULL after
+ * every failure.
+ * All three: OCEAN_E_INVALID_ARG, checked before any device call, for a null context, a null `out` or
+ * `req`, a tile out of range, an unknown mode, iterations outside [0, 16] or nonzero in vertices mode,
+ * a lod that is not finite, negative, or nonzero in surface and heightfield mode, a non-finite x0, z0,
+ * dx or dz, nx < 1 or ny < 1, nx * ny > OCEAN_GRID_MAX_NODES (in 64 bits) or a wrong `bytes`; then
+ * OCEAN_E_STATE before ocean_init_spectrum and OCEAN_E_UNSUPPORTED on a column-parity context (as the
+ * queries). */
+#define OCEAN_GRID_VERTICES 0
+#define OCEAN_GRID_SURFACE 1
+#define OCEAN_GRID_HEIGHTFIELD 2
+#define OCEAN_GRID_MAX_NODES (1 << 22)
+int ocean_surface_grid(ocean_ctx *ctx, int tile, int mode, int iterations, float lod, float x0, float z0,
+                       float dx, float dz, int nx, int ny, float *out, size_t bytes);
+int ocean_surface_grid_device(ocean_ctx *ctx, int tile, int mode, int iterations, float lod, float x0, float z0,
+                              float dx, float dz, int nx, int ny, float *out, size_t bytes);
+int ocean_surface_grid_async(ocean_ctx *ctx, int tile, int mode, int iterations, float lod, float x0, float z0,
+                             float dx, float dz, int nx, int ny, float *out, size_t bytes, ocean_readback **req);
+
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
- * ocean_read_height_async / ocean_query_surface_async request records HIP timing events around its
- * device-to-host copy, for ocean_readback_copy_ms.  Requests made while it is off record only
- * untimed events. */
+ * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async request records HIP
+ * timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it
+ * is off record only untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 
 /* Duration of a completed request's device-to-host copy in ms (HIP events on the copy stream around

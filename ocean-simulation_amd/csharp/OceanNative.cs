@@ -116,6 +116,15 @@ namespace OceanHip
         public static extern OceanStatus ocean_query_surface_device(IntPtr ctx, int tile, int mode, int iterations, IntPtr points, int count, IntPtr output);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_query_surface_async(IntPtr ctx, int tile, int mode, int iterations, [In] float[] points, int count, IntPtr dst, out IntPtr request);
+        // Surface grids (added within ABI 4 in the same way).  Node (i, j) lies at (x0 + i dx, z0 + j dz), result j * nx + i;
+        // mode: GridVertices / GridSurface (8 floats per node, bytes = nx * ny * 32) / GridHeightfield (1 float, nx * ny * 4).
+        public const int GridVertices = 0, GridSurface = 1, GridHeightfield = 2, GridMaxNodes = 1 << 22;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_surface_grid(IntPtr ctx, int tile, int mode, int iterations, float lod, float x0, float z0, float dx, float dz, int nx, int ny, [Out] float[] output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_surface_grid_device(IntPtr ctx, int tile, int mode, int iterations, float lod, float x0, float z0, float dx, float dz, int nx, int ny, IntPtr output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_surface_grid_async(IntPtr ctx, int tile, int mode, int iterations, float lod, float x0, float z0, float dx, float dz, int nx, int ny, IntPtr dst, UIntPtr bytes, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_read_async(IntPtr ctx, OceanTexture tex, int tile, int cascade, IntPtr dst, UIntPtr bytes, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

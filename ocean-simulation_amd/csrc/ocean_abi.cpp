@@ -98,7 +98,7 @@ namespace ocean {
 void generate_noise_host(int n, uint64_t seed, float* out);
 }
 
-// Staging slots of ocean_read_async / ocean_read_height_async / ocean_query_surface_async.  A slot is device memory as large as one
+// Staging slots of ocean_read_async / ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async.  A slot is device memory as large as one
 // slice of the largest texture plus the events of the request holding it, created once with the slot: no
 // event is created per request.  `after` and `done` disable timing; the timed pair `tstart` / `tdone`
 // (ocean_readback_copy_ms) is created on the slot's first request made with readback timing on
@@ -112,6 +112,8 @@ void generate_noise_host(int n, uint64_t seed, float* out);
 // the upload reads memory that stays put until the request is released.
 constexpr size_t kQueryPointsOffset = (size_t)OCEAN_QUERY_MAX_POINTS * 8 * sizeof(float);
 constexpr size_t kQuerySlotBytes = kQueryPointsOffset + (size_t)OCEAN_QUERY_MAX_POINTS * 2 * sizeof(float);
+// Workgroup tile of the grid kernel (grid.hip), nodes along x: the fastest of the shapes measured.
+constexpr int kGridTileDefault = 32;
 struct StageSlot {
     void* mem = nullptr;
     void* pts_host = nullptr;    // pinned, OCEAN_QUERY_MAX_POINTS points (ocean_query_surface_async only)
@@ -183,6 +185,7 @@ struct ocean_options {
     long op_chunk_mib = 0;  // OCEAN_OP_CHUNK_MIB: MiB of unit-planes per chunk of ocean_ifft2d (0: auto)
     int tile_w = 0;         // OCEAN_TILE_W: column-tile width of the fused path at N = 128..1024 (0: auto)
     int disp_cached = -1;   // OCEAN_DISP_CACHED: 0 / 1 force pass BQ's DISP store policy (disp_fits_cache); -1 auto
+    int grid_tile = 0;      // OCEAN_GRID_TILE: nodes along x of the grid kernel's workgroup tile, 64 / 32 / 16 (0: kept)
 
     static ocean_options from_env() {
         ocean_options o;
@@ -193,6 +196,7 @@ struct ocean_options {
         if (const char* e = std::getenv("OCEAN_OP_CHUNK_MIB")) o.op_chunk_mib = std::max(0L, std::atol(e));
         if (const char* e = std::getenv("OCEAN_TILE_W")) o.tile_w = std::max(0, std::atoi(e));
         if (const char* e = std::getenv("OCEAN_DISP_CACHED")) o.disp_cached = std::strcmp(e, "auto") ? std::atoi(e) != 0 : -1;
+        if (const char* e = std::getenv("OCEAN_GRID_TILE")) o.grid_tile = std::atoi(e);
         return o;
     }
 };
@@ -228,7 +232,7 @@ struct ocean_ctx {
     float4* deriv_mips = nullptr;  // OCEAN_F_MIPS chains (levels 1..log2 N per slice)
     float4* turb_mips = nullptr;
     size_t mip_chain = 0;
-    hipStream_t copy_stream = nullptr;  // ocean_read_async / ocean_read_height_async / ocean_query_surface_async
+    hipStream_t copy_stream = nullptr;  // ocean_read_async / _height_async / ocean_query_surface_async / ocean_surface_grid_async
     std::shared_ptr<StagePool> stage_pool;  // their staging slots
     bool readback_timing = false;           // ocean_set_readback_timing
     // host state.  `params` and the device `casc` are what the kernels run with; set_params
@@ -1296,6 +1300,106 @@ int ocean_query_surface_async(ocean_ctx* ctx, int tile, int mode, int iterations
                        : hipErrorLaunchFailure;
         },
         out);
+}
+
+// Argument checks of the surface grids, before any device call (ocean.h).
+static int check_grid(ocean_ctx* ctx, int tile, int mode, int iterations, float lod, float x0, float z0, float dx,
+                      float dz, int nx, int ny, const float* out, size_t bytes) {
+    if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+    if (!out) return fail(OCEAN_E_INVALID_ARG, "null output");
+    if (tile < 0 || tile >= ctx->T) return fail(OCEAN_E_INVALID_ARG, "tile out of range");
+    if (mode != OCEAN_GRID_VERTICES && mode != OCEAN_GRID_SURFACE && mode != OCEAN_GRID_HEIGHTFIELD)
+        return fail(OCEAN_E_INVALID_ARG, "unknown grid mode");
+    if (iterations < 0 || iterations > 16) return fail(OCEAN_E_INVALID_ARG, "iterations must be in [0, 16]");
+    if (mode == OCEAN_GRID_VERTICES && iterations != 0)
+        return fail(OCEAN_E_INVALID_ARG, "OCEAN_GRID_VERTICES takes iterations = 0");
+    if (!std::isfinite(lod) || lod < 0.0f) return fail(OCEAN_E_INVALID_ARG, "lod must be finite and >= 0");
+    if (mode != OCEAN_GRID_VERTICES && lod != 0.0f)
+        return fail(OCEAN_E_INVALID_ARG, "OCEAN_GRID_SURFACE and OCEAN_GRID_HEIGHTFIELD take lod = 0");
+    if (!std::isfinite(x0) || !std::isfinite(z0) || !std::isfinite(dx) || !std::isfinite(dz))
+        return fail(OCEAN_E_INVALID_ARG, "grid origin and spacing must be finite");
+    if (nx < 1 || ny < 1) return fail(OCEAN_E_INVALID_ARG, "nx and ny must be at least 1");
+    const uint64_t nodes = (uint64_t)nx * (uint64_t)ny;
+    if (nodes > (uint64_t)OCEAN_GRID_MAX_NODES)
+        return fail(OCEAN_E_INVALID_ARG, "nx * ny = " + std::to_string(nodes) + " > OCEAN_GRID_MAX_NODES");
+    const size_t want = (size_t)nodes * (mode == OCEAN_GRID_HEIGHTFIELD ? 4 : 32);
+    if (bytes != want)
+        return fail(OCEAN_E_INVALID_ARG, "byte count " + std::to_string(bytes) + " != nx * ny * " +
+                                             (mode == OCEAN_GRID_HEIGHTFIELD ? "4 = " : "32 = ") + std::to_string(want));
+    return OCEAN_OK;
+}
+
+// ... and of the context's state, as the queries.
+static int check_grid_state(const ocean_ctx* ctx) {
+    if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, "ocean_init_spectrum must precede ocean_surface_grid");
+    if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, "surface grid of a column-parity shard (half the columns)");
+    return OCEAN_OK;
+}
+
+// The grid kernel on the ctx stream (device pointer; kind 2 of ocean_kernel_stats).  The workgroup's tile:
+// the measured best (docs/MEASUREMENTS.md section 10) unless OCEAN_GRID_TILE names another (A/B).
+static int launch_grid(ocean_ctx* ctx, int tile, int mode, int iterations, float lod, float x0, float z0, float dx,
+                       float dz, int nx, int ny, float* d_out) {
+    const ocean::DevView v = ctx->view();
+    const int tw = ocean::grid_tile_supported(ctx->opt.grid_tile) ? ctx->opt.grid_tile : kGridTileDefault;
+    return timed(ctx, 2,
+                 [&] {
+                     return ocean::launch_surface_grid(v, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, tw, d_out,
+                                                       ctx->stream);
+                 },
+                 "surface_grid");
+}
+
+int ocean_surface_grid_device(ocean_ctx* ctx, int tile, int mode, int iterations, float lod, float x0, float z0,
+                              float dx, float dz, int nx, int ny, float* out, size_t bytes) {
+    if (int r = check_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out, bytes)) return r;
+    // the kernel writes float4 rows (one float per node in heightfield mode; one rule for all modes, ocean.h)
+    if ((uintptr_t)out & 15) return fail(OCEAN_E_INVALID_ARG, "ocean_surface_grid_device: out must be 16-byte aligned");
+    if (int r = check_grid_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    return launch_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out);
+}
+
+int ocean_surface_grid(ocean_ctx* ctx, int tile, int mode, int iterations, float lod, float x0, float z0, float dx,
+                       float dz, int nx, int ny, float* out, size_t bytes) {
+    if (int r = check_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out, bytes)) return r;
+    if (int r = check_grid_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    void* d = nullptr;
+    OCEAN_HIP(hipMallocAsync(&d, bytes, ctx->stream));
+    const int r = launch_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, static_cast<float*>(d));
+    hipError_t e = hipSuccess;
+    if (r == OCEAN_OK) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t ef = hipFreeAsync(d, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (r != OCEAN_OK) return r;
+    if (e != hipSuccess) return hip_fail(e, "ocean_surface_grid copy");
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
+    return OCEAN_OK;
+}
+
+int ocean_surface_grid_async(ocean_ctx* ctx, int tile, int mode, int iterations, float lod, float x0, float z0,
+                             float dx, float dz, int nx, int ny, float* out, size_t bytes, ocean_readback** req) {
+    if (!req) return fail(OCEAN_E_INVALID_ARG, "req is null");
+    *req = nullptr;
+    if (int r = check_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out, bytes)) return r;
+    // the result is written into a readback slot, whose size start_readback fixes: no points are staged
+    const size_t slot_bytes = std::max(ctx->texels() * 16, kQuerySlotBytes);
+    if (bytes > slot_bytes)
+        return fail(OCEAN_E_INVALID_ARG, "ocean_surface_grid_async: " + std::to_string(bytes) + " B exceed a readback slot of " +
+                                             std::to_string(slot_bytes) + " B");
+    if (int r = check_grid_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    return start_readback(
+        ctx, out, bytes,
+        [&](StageSlot* sl) {
+            return launch_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, static_cast<float*>(sl->mem)) ==
+                           OCEAN_OK
+                       ? hipSuccess
+                       : hipErrorLaunchFailure;
+        },
+        req);
 }
 
 int ocean_set_column_band(ocean_ctx* ctx, int x_begin, int x_count) {

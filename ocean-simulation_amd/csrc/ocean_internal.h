@@ -1,5 +1,5 @@
 // Internal declarations shared by the C-ABI layer (ocean_abi.cpp) and the HIP
-// kernel translation units (spectrum.hip, fft2/3/4k.hip, mips.hip, sample.hip, query.hip).  Not part of the ABI.
+// kernel translation units (spectrum.hip, fft2/3/4k.hip, mips.hip, sample.hip, query.hip, grid.hip).  Not part of the ABI.
 #pragma once
 
 #include <hip/hip_ext.h>
@@ -132,6 +132,11 @@ hipError_t launch_sample_world(const DevView& v, int tile, const float* pts, int
 // query.hip: surface queries (ocean_query_surface*), device pointers: pts float[count][2], out float[count][8]
 hipError_t launch_query_surface(const DevView& v, int tile, int mode, int iterations, const float* pts, int count,
                                 float* out, hipStream_t s);
+// grid.hip: surface grids (ocean_surface_grid*), device pointer: out float[ny][nx][8], or float[ny][nx] in
+// OCEAN_GRID_HEIGHTFIELD mode; tile_w = the workgroup's tile width in nodes (grid_tile_supported)
+bool grid_tile_supported(int tile_w);
+hipError_t launch_surface_grid(const DevView& v, int tile, int mode, int iterations, float lod, float x0, float z0,
+                               float dx, float dz, int nx, int ny, int tile_w, float* out, hipStream_t s);
 
 // fft4k.hip (N = 2048, 4096): four-step column passes C1 (in place on the
 // 16-wide tile-major intermediate) + C2 (with the pass-B epilogue); replace pass B.

@@ -64,11 +64,15 @@ EXPORTED_SYMBOLS = (
     "ocean_host_alloc", "ocean_host_free", "ocean_last_error", "ocean_abi_version", "ocean_set_column_band",
     "ocean_reset_foam", "ocean_sample_world", "ocean_sample_world_device", "ocean_kernel_name",
     "ocean_set_column_parity", "ocean_query_surface", "ocean_query_surface_device", "ocean_query_surface_async",
+    "ocean_surface_grid", "ocean_surface_grid_device", "ocean_surface_grid_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
 QUERY_REFERENCE, QUERY_SURFACE = 0, 1
 QUERY_MAX_POINTS = 65536
+# ocean_surface_grid* modes and limits (ocean.h)
+GRID_VERTICES, GRID_SURFACE, GRID_HEIGHTFIELD = 0, 1, 2
+GRID_MAX_NODES = 1 << 22
 
 
 class OceanError(RuntimeError):
@@ -143,6 +147,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_query_surface": ([P, i, i, i, P, i, P], i),
         "ocean_query_surface_device": ([P, i, i, i, P, i, P], i),
         "ocean_query_surface_async": ([P, i, i, i, P, i, P, ctypes.POINTER(P)], i),
+        "ocean_surface_grid": ([P, i, i, i, f, f, f, f, f, i, i, P, sz], i),
+        "ocean_surface_grid_device": ([P, i, i, i, f, f, f, f, f, i, i, P, sz], i),
+        "ocean_surface_grid_async": ([P, i, i, i, f, f, f, f, f, i, i, P, sz, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -297,6 +304,53 @@ class OceanContext:
         Poll .done() / .wait(), then .data; `buf`: a caller-owned pinned slot of at least M x 32 B."""
         return Readback(self, TEX_DISP, tile, 0, buf, query=(self._query_points(points), mode, iterations))
 
+    @staticmethod
+    def grid_points(x0: float, z0: float, dx: float, dz: float, nx: int, ny: int) -> np.ndarray:
+        """The nodes of a grid as ocean_surface_grid places them, float32[ny * nx][2] = (world x, world z):
+        node (i, j) at (x0 + float32(i) * dx, z0 + float32(j) * dz), one fp32 multiply and one fp32 add
+        each, at row j * nx + i."""
+        f32 = np.float32
+        xs = f32(x0) + np.arange(nx, dtype=f32) * f32(dx)
+        zs = f32(z0) + np.arange(ny, dtype=f32) * f32(dz)
+        out = np.empty((ny, nx, 2), f32)
+        out[..., 0] = xs[None, :]
+        out[..., 1] = zs[:, None]
+        return out.reshape(ny * nx, 2)
+
+    @staticmethod
+    def _grid_args(mode: int, iterations: Optional[int], nx: int, ny: int):
+        """(iterations, result shape, bytes): `iterations` defaults to 4, to 0 for GRID_VERTICES."""
+        if iterations is None:
+            iterations = 0 if mode == GRID_VERTICES else 4
+        nx, ny = int(nx), int(ny)
+        shape = (max(ny, 0), max(nx, 0)) if mode == GRID_HEIGHTFIELD else (max(ny, 0), max(nx, 0), 8)
+        return iterations, shape, int(np.prod(shape, dtype=np.int64)) * 4
+
+    def surface_grid(self, x0: float, z0: float, dx: float, dz: float, nx: int, ny: int, mode: int = GRID_SURFACE,
+                     iterations: Optional[int] = None, lod: float = 0.0, tile: int = 0) -> np.ndarray:
+        """The surface over a regular grid (ocean.h ocean_surface_grid), blocking: node (i, j) at
+        (x0 + i dx, z0 + j dz) -> float32[ny][nx][8], or float32[ny][nx] for GRID_HEIGHTFIELD.
+        GRID_VERTICES (iterations 0, `lod` as sample_world): displaced vertex x, y, z, foam, normal x, y, z, 0
+        (MeshGenerator's plane through the domain stage of Water.shader); GRID_SURFACE (`iterations`
+        defaults to 4): query_surface's record at every node; GRID_HEIGHTFIELD: its height alone."""
+        iterations, shape, nbytes = self._grid_args(mode, iterations, nx, ny)
+        if nx * ny > GRID_MAX_NODES:  # refused by the library as well; no host buffer of that size first
+            shape, nbytes = (0,), 0
+        out = np.empty(shape, np.float32)
+        _check(self.lib.ocean_surface_grid(self._h, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny,
+                                           out.ctypes.data, nbytes), "ocean_surface_grid")
+        return out
+
+    def surface_grid_async(self, x0: float, z0: float, dx: float, dz: float, nx: int, ny: int,
+                           mode: int = GRID_SURFACE, iterations: Optional[int] = None, lod: float = 0.0,
+                           tile: int = 0, buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_surface_grid_async): the grid is computed behind the queued steps and
+        lands in pinned host memory like a read_async slice.  Poll .done() / .wait(), then .data; `buf`: a
+        caller-owned pinned slot of at least the result's size."""
+        iterations, shape, nbytes = self._grid_args(mode, iterations, nx, ny)
+        return Readback(self, TEX_DISP, tile, 0, buf,
+                        grid=(mode, iterations, lod, x0, z0, dx, dz, nx, ny, shape, nbytes))
+
     def read_async(self, tex: int, tile: int = 0, cascade: int = 0, buf: "PinnedBuffer" = None) -> "Readback":
         """AsyncGPUReadback.Request (WaterBody.cs:288-296): copy one slice into pinned
         host memory once the queued steps finish; poll .done() / .wait(), then .data.
@@ -382,13 +436,16 @@ class PinnedBuffer:
 
 class Readback:
     """One ocean_read_async (or, `height`, ocean_read_height_async; or, `query` = (points float32[M][2],
-    mode, iterations), ocean_query_surface_async) request into pinned host memory: a caller's PinnedBuffer
+    mode, iterations), ocean_query_surface_async; or, `grid` = (mode, iterations, lod, x0, z0, dx, dz, nx, ny,
+    shape, bytes), ocean_surface_grid_async) request into pinned host memory: a caller's PinnedBuffer
     slot, or one of its own (freed by release())."""
 
     def __init__(self, ctx: "OceanContext", tex: int, tile: int, cascade: int, buf: Optional[PinnedBuffer] = None,
-                 height: bool = False, query: Optional[tuple] = None):
+                 height: bool = False, query: Optional[tuple] = None, grid: Optional[tuple] = None):
         self.lib = ctx.lib
-        if query is not None:
+        if grid is not None:
+            self.shape, self.nbytes = grid[9], grid[10]
+        elif query is not None:
             self.shape = (query[0].shape[0], 8)
             self.nbytes = query[0].shape[0] * 32
         else:
@@ -399,12 +456,17 @@ class Readback:
         self.slot = buf
         self._own = buf is None
         if buf is None:
-            buf = PinnedBuffer(max(self.nbytes, 32))  # (an empty query still reaches the library, which refuses it)
+            # (an empty query or a grid beyond the limits still reaches the library, which refuses it)
+            buf = PinnedBuffer(min(max(self.nbytes, 32), GRID_MAX_NODES * 32))
         elif buf.nbytes < self.nbytes:
             raise ValueError(f"pinned slot of {buf.nbytes} B < request {self.nbytes} B")
         self._pinned = buf
         self._buf = buf.ptr
-        if query is not None:
+        if grid is not None:
+            where = "ocean_surface_grid_async"
+            rc = self.lib.ocean_surface_grid_async(ctx._h, tile, *grid[:9], self._buf, self.nbytes,
+                                                   ctypes.byref(self._h))
+        elif query is not None:
             where = "ocean_query_surface_async"
             pts, mode, iterations = query
             rc = self.lib.ocean_query_surface_async(ctx._h, tile, mode, iterations, pts.ctypes.data, pts.shape[0],
@@ -704,6 +766,12 @@ class WaterBody:
         """What Water.shader reads at world positions (x, z, lod): summed displacement,
         derivatives, turbulence and the normal (Water.shader:314-348)."""
         return self.ctx.sample_world(np.asarray(points, np.float32).reshape(-1, 3), tile)
+
+    def SurfaceGrid(self, x0: float, z0: float, dx: float, dz: float, nx: int, ny: int, mode: int = GRID_SURFACE,
+                    iterations: Optional[int] = None, lod: float = 0.0, tile: int = 0) -> np.ndarray:
+        """The surface over a regular grid (OceanContext.surface_grid): MeshGenerator's plane displaced as
+        the domain stage of Water.shader does (GRID_VERTICES), the Eulerian surface or a height map."""
+        return self.ctx.surface_grid(x0, z0, dx, dz, nx, ny, mode, iterations, lod, tile)
 
     # texture-out contract (material properties, WaterBody.cs:277-281)
     def DisplacementsTextures(self, tile: int = 0) -> np.ndarray:
