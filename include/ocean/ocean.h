@@ -64,7 +64,9 @@ extern "C" {
  *      a library that has them from one that does not: a host that needs them probes for the
  *      symbol (dlsym / EntryPointNotFoundException).
  *      Added later within version 4 in the same way: ocean_surface_grid, ocean_surface_grid_device,
- *      ocean_surface_grid_async. */
+ *      ocean_surface_grid_async.
+ *      Added later within version 4 in the same way: ocean_body_buoyancy, ocean_body_buoyancy_device,
+ *      ocean_body_buoyancy_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -416,9 +418,79 @@ int ocean_surface_grid_device(ocean_ctx *ctx, int tile, int mode, int iterations
 int ocean_surface_grid_async(ocean_ctx *ctx, int tile, int mode, int iterations, float lod, float x0, float z0,
                              float dx, float dz, int nx, int ny, float *out, size_t bytes, ocean_readback **req);
 
+/* Buoyant bodies: M rigid bodies that share one hull of P probes, reduced on the device to 32 B per
+ * body, whatever P is.  The reference's model is one probe per body with the volume from
+ * transform.localScale (BuoyantObject.FixedUpdate -> GetWaterHeight; its README: "very basic"); a host
+ * that wants hulls that roll and pitch puts P probes on each body, and with the queries above it would
+ * transform M x P probes on the CPU, upload M x P x 8 B, read back M x P x 32 B and reduce them itself.
+ * Here the transform, the surface lookup and the reduction are one kernel.
+ *
+ *   hull:   probe j is float[5] = (rx, ry, rz, h, v): the centre of the probe's cell in the body frame, the
+ *           cell's vertical extent and its volume.
+ *   bodies: body b is float[10] = (cx, cy, cz, qx, qy, qz, qw, sx, sy, sz): the world position of the body
+ *           origin, a body -> world quaternion (the caller keeps it unit) and a per-axis scale (the role
+ *           of the reference's transform.localScale).
+ *   out:    record b is float[8].
+ *
+ * All arithmetic is fp32, each line one rounding per operation in the order written (no fused
+ * multiply-add).  Per probe j of body b, with c = (cx, cy, cz), u = (qx, qy, qz), s = (sx, sy, sz):
+ *       a   = (sx * rx, sy * ry, sz * rz)
+ *       t   = 2 * (u x a),  (u x a) = (u.y * a.z - u.z * a.y,  u.z * a.x - u.x * a.z,  u.x * a.y - u.y * a.x)
+ *       d   = (a + qw * t) + (u x t), componentwise, (u x t) formed like (u x a)        (a rotated by q)
+ *       w   = c + d                                                                    (world position)
+ *       mode OCEAN_QUERY_SURFACE, iterations = K in [0, 16]: rec = the 8-float record of ocean_query_surface
+ *           for the point (w.x, w.z) with K iterations, bit for bit: eta = rec[0], r = rec[3], n = rec[4..6]
+ *       mode OCEAN_QUERY_REFERENCE, iterations = 0: eta = rec[0] of that mode (GetWaterHeight's texel pick
+ *           at (w.x, w.z)), n = (0, 1, 0), r = 0
+ *       h'  = h * sy,   v' = ((v * sx) * sy) * sz                                      (the scaled cell)
+ *       bottom = w.y - 0.5f * h',   f = fminf(fmaxf((eta - bottom) / h', 0), 1)        (submerged fraction)
+ *       g   = v' * f                                                                   (submerged volume)
+ *       e   = (d.x, (d.y - 0.5f * h') + 0.5f * (f * h'), d.z)       (centroid of the submerged part of the
+ *                                                                    cell, relative to the body origin)
+ *       the seven terms: g, g * e.x, g * e.y, g * e.z, g * n.x, g * n.y, g * n.z
+ * The sum over a body's probes is defined exactly.  W = the smallest power of two >= P, capped at 64.
+ * Lane l < W accumulates t_l from +0: t_l = t_l + term, for its probes j = l, l + W, l + 2W, ... in
+ * ascending order; a lane without a probe keeps +0.  Then for s = W/2, W/4, ..., 1: t_l = t_l + t_(l xor s)
+ * for every l.  The result is t_0 (in numpy: fold the upper half of t onto the lower half until one is left).
+ *       out[8b + 0..6] = the seven sums
+ *       out[8b + 7]    = fmaxf over the body's probes of r (the worst fixed-point residual, as in the queries)
+ * What a host does with a record: the buoyant force is rho g out[0] along +y and acts at c + out[1..3] /
+ * out[0]; its torque about c is rho g (-out[3], 0, out[1]); out[4..6] normalised is the water plane under
+ * the hull.  The reference's box is approximately the one-probe hull (0, 0.5, 0, 1, 1) with the identity
+ * quaternion in reference mode: its bottom at pos.y, its height localScale.y, its volume the product of
+ * the scales.
+ * The library does not inspect hull or body values: a non-unit quaternion scales and shears as the
+ * formulas say, and h * sy = 0 or a non-finite input gives unspecified numbers (never an access outside
+ * the textures).
+ *
+ * ocean_body_buoyancy takes host buffers and blocks.  ocean_body_buoyancy_device takes device pointers
+ * (hull and bodies 4-B aligned, out 16-B aligned, else OCEAN_E_INVALID_ARG) and is async on the ctx
+ * stream, ordered after the queued steps; count is bounded by OCEAN_BODY_MAX_SAMPLES alone.
+ * ocean_body_buoyancy_async is the per-frame form, exactly as ocean_query_surface_async: `hull` and
+ * `bodies` are host buffers consumed before the call returns; the kernel runs on the ctx stream, after
+ * the steps queued so far and before later ones, and its count x 32 B land in `out` on the copy stream
+ * like an ocean_read_async slice, with the same ocean_readback_status / _wait / _release / _copy_ms.
+ * *req is NULL after every failure.
+ * All three: OCEAN_E_INVALID_ARG, checked before any device call, for a null ctx, hull, bodies, out or
+ * req, a tile out of range, an unknown mode, iterations outside [0, 16] or nonzero in reference mode,
+ * probes outside [1, OCEAN_BODY_MAX_PROBES], count < 0, count > OCEAN_BODY_MAX_BODIES (host and async
+ * forms, which stage the bodies), count * probes > OCEAN_BODY_MAX_SAMPLES (in 64 bits) or a misaligned
+ * device pointer; then OCEAN_E_STATE before ocean_init_spectrum and OCEAN_E_UNSUPPORTED on a
+ * column-parity context (as the queries).  count = 0 is a no-op in the blocking and device forms and
+ * OCEAN_E_INVALID_ARG in the async form (there is no request to hand back). */
+#define OCEAN_BODY_MAX_BODIES 8192
+#define OCEAN_BODY_MAX_PROBES 4096
+#define OCEAN_BODY_MAX_SAMPLES (1 << 22)
+int ocean_body_buoyancy(ocean_ctx *ctx, int tile, int mode, int iterations, const float *hull, int probes,
+                        const float *bodies, int count, float *out);
+int ocean_body_buoyancy_device(ocean_ctx *ctx, int tile, int mode, int iterations, const float *hull, int probes,
+                               const float *bodies, int count, float *out);
+int ocean_body_buoyancy_async(ocean_ctx *ctx, int tile, int mode, int iterations, const float *hull, int probes,
+                              const float *bodies, int count, float *out, ocean_readback **req);
+
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
- * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async request records HIP
- * timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it
+ * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async /
+ * ocean_body_buoyancy_async request records HIP timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it
  * is off record only untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 

@@ -125,6 +125,15 @@ namespace OceanHip
         public static extern OceanStatus ocean_surface_grid_device(IntPtr ctx, int tile, int mode, int iterations, float lod, float x0, float z0, float dx, float dz, int nx, int ny, IntPtr output, UIntPtr bytes);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_surface_grid_async(IntPtr ctx, int tile, int mode, int iterations, float lod, float x0, float z0, float dx, float dz, int nx, int ny, IntPtr dst, UIntPtr bytes, out IntPtr request);
+        // Buoyant bodies (added within ABI 4 in the same way).  hull [probes][5] = (rx, ry, rz, h, v), bodies [count][10] =
+        // (origin, quaternion xyzw, scale), 8 floats per body; mode and iterations as the queries (QueryReference: 0).
+        public const int BodyMaxBodies = 8192, BodyMaxProbes = 4096, BodyMaxSamples = 1 << 22;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_buoyancy(IntPtr ctx, int tile, int mode, int iterations, [In] float[] hull, int probes, [In] float[] bodies, int count, [Out] float[] output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_buoyancy_device(IntPtr ctx, int tile, int mode, int iterations, IntPtr hull, int probes, IntPtr bodies, int count, IntPtr output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_buoyancy_async(IntPtr ctx, int tile, int mode, int iterations, [In] float[] hull, int probes, [In] float[] bodies, int count, IntPtr dst, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_read_async(IntPtr ctx, OceanTexture tex, int tile, int cascade, IntPtr dst, UIntPtr bytes, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

@@ -203,6 +203,18 @@ namespace OceanHip
             return output;
         }
 
+        // BuoyantObject.FixedUpdate's lookup for M bodies of P probes each (ocean.h ocean_body_buoyancy): hull is
+        // [P][5] = (cell centre in the body frame, vertical extent, volume), bodies [M][10] = (origin, body -> world
+        // quaternion xyzw, per-axis scale); per body 8 floats: submerged volume V, V * centroid relative to the
+        // origin, V-weighted water normal, worst residual.  Force rho g V along +y; torque rho g (-out[3], 0, out[1]).
+        public float[] Buoyancy(float[] hull, float[] bodies, int iterations = 4, int mode = OceanNative.QuerySurface)
+        {
+            var output = new float[bodies.Length / 10 * 8];
+            OceanNative.Check(OceanNative.ocean_body_buoyancy(ctx, 0, mode, iterations, hull, hull.Length / 5, bodies,
+                                                              bodies.Length / 10, output), "ocean_body_buoyancy");
+            return output;
+        }
+
         // Texture-out contract: device pointers for same-process renderers (WaterBody.cs:277-281).
         public IntPtr DeviceTexture(OceanTexture tex, out ulong bytes)
         {

@@ -109,7 +109,8 @@ void generate_noise_host(int n, uint64_t seed, float* out);
 // A slot also holds the points and results of an ocean_query_surface_async request: results at its
 // base, the points behind them (kQueryPointsOffset), and, from the slot's first such request on, a
 // pinned host copy of the points (`pts_host`): the caller's buffer is consumed inside the call, and
-// the upload reads memory that stays put until the request is released.
+// the upload reads memory that stays put until the request is released.  An ocean_body_buoyancy_async
+// request uses the same places: its records at the base, its bodies and hull where the points go.
 constexpr size_t kQueryPointsOffset = (size_t)OCEAN_QUERY_MAX_POINTS * 8 * sizeof(float);
 constexpr size_t kQuerySlotBytes = kQueryPointsOffset + (size_t)OCEAN_QUERY_MAX_POINTS * 2 * sizeof(float);
 // Workgroup tile of the grid kernel (grid.hip), nodes along x: the fastest of the shapes measured.
@@ -1395,6 +1396,125 @@ int ocean_surface_grid_async(ocean_ctx* ctx, int tile, int mode, int iterations,
         ctx, out, bytes,
         [&](StageSlot* sl) {
             return launch_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, static_cast<float*>(sl->mem)) ==
+                           OCEAN_OK
+                       ? hipSuccess
+                       : hipErrorLaunchFailure;
+        },
+        req);
+}
+
+// Argument checks of the buoyant bodies, before any device call (ocean.h); `limit`: the forms that stage
+// the bodies (host and async) take at most OCEAN_BODY_MAX_BODIES.
+static int check_body(ocean_ctx* ctx, int tile, int mode, int iterations, const float* hull, int probes,
+                      const float* bodies, int count, const float* out, bool limit) {
+    if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+    if (!hull || !bodies || !out) return fail(OCEAN_E_INVALID_ARG, "null hull, bodies or output");
+    if (tile < 0 || tile >= ctx->T) return fail(OCEAN_E_INVALID_ARG, "tile out of range");
+    if (mode != OCEAN_QUERY_REFERENCE && mode != OCEAN_QUERY_SURFACE) return fail(OCEAN_E_INVALID_ARG, "unknown query mode");
+    if (iterations < 0 || iterations > 16) return fail(OCEAN_E_INVALID_ARG, "iterations must be in [0, 16]");
+    if (mode == OCEAN_QUERY_REFERENCE && iterations != 0)
+        return fail(OCEAN_E_INVALID_ARG, "OCEAN_QUERY_REFERENCE takes iterations = 0");
+    if (probes < 1 || probes > OCEAN_BODY_MAX_PROBES)
+        return fail(OCEAN_E_INVALID_ARG, "probes = " + std::to_string(probes) + " outside [1, OCEAN_BODY_MAX_PROBES]");
+    if (count < 0) return fail(OCEAN_E_INVALID_ARG, "negative body count");
+    if (limit && count > OCEAN_BODY_MAX_BODIES)
+        return fail(OCEAN_E_INVALID_ARG, "body count " + std::to_string(count) + " > OCEAN_BODY_MAX_BODIES");
+    const uint64_t samples = (uint64_t)count * (uint64_t)probes;
+    if (samples > (uint64_t)OCEAN_BODY_MAX_SAMPLES)
+        return fail(OCEAN_E_INVALID_ARG, "count * probes = " + std::to_string(samples) + " > OCEAN_BODY_MAX_SAMPLES");
+    return OCEAN_OK;
+}
+
+// ... and of the context's state, as the queries.
+static int check_body_state(const ocean_ctx* ctx) {
+    if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, "ocean_init_spectrum must precede ocean_body_buoyancy");
+    if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, "buoyancy on a column-parity shard (half the columns)");
+    return OCEAN_OK;
+}
+
+// The body kernel on the ctx stream (device pointers; kind 2 of ocean_kernel_stats).
+static int launch_body(ocean_ctx* ctx, int tile, int mode, int iterations, const float* d_hull, int probes,
+                       const float* d_bodies, int count, float* d_out) {
+    const ocean::DevView v = ctx->view();
+    return timed(ctx, 2,
+                 [&] {
+                     return ocean::launch_body_buoyancy(v, tile, mode, iterations, d_hull, probes, d_bodies, count, d_out,
+                                                        ctx->stream);
+                 },
+                 "body_buoyancy");
+}
+
+// The staged inputs of the host and async forms: the bodies, then the hull right behind them (floats both).
+constexpr size_t kBodyInputBytes = (size_t)OCEAN_BODY_MAX_BODIES * 10 * sizeof(float) +
+                                   (size_t)OCEAN_BODY_MAX_PROBES * 5 * sizeof(float);
+static_assert(kBodyInputBytes <= kQuerySlotBytes - kQueryPointsOffset, "a slot's pinned input copy holds every body request");
+static_assert((size_t)OCEAN_BODY_MAX_BODIES * 8 * sizeof(float) <= kQueryPointsOffset, "the records end before the inputs");
+
+int ocean_body_buoyancy_device(ocean_ctx* ctx, int tile, int mode, int iterations, const float* hull, int probes,
+                               const float* bodies, int count, float* out) {
+    if (int r = check_body(ctx, tile, mode, iterations, hull, probes, bodies, count, out, false)) return r;
+    // the kernel reads floats and writes float4 rows (ocean.h)
+    if (((uintptr_t)hull & 3) || ((uintptr_t)bodies & 3) || ((uintptr_t)out & 15))
+        return fail(OCEAN_E_INVALID_ARG, "ocean_body_buoyancy_device: hull and bodies must be 4-byte and out 16-byte aligned");
+    if (int r = check_body_state(ctx)) return r;
+    if (count == 0) return OCEAN_OK;
+    OCEAN_ENTER(ctx);
+    return launch_body(ctx, tile, mode, iterations, hull, probes, bodies, count, out);
+}
+
+int ocean_body_buoyancy(ocean_ctx* ctx, int tile, int mode, int iterations, const float* hull, int probes,
+                        const float* bodies, int count, float* out) {
+    if (int r = check_body(ctx, tile, mode, iterations, hull, probes, bodies, count, out, true)) return r;
+    if (int r = check_body_state(ctx)) return r;
+    if (count == 0) return OCEAN_OK;
+    OCEAN_ENTER(ctx);
+    const size_t body_bytes = (size_t)count * 10 * 4, hull_bytes = (size_t)probes * 5 * 4, out_bytes = (size_t)count * 8 * 4;
+    const size_t out_off = (body_bytes + hull_bytes + 255) & ~(size_t)255;  // float4 output rows stay 16-B aligned
+    void* d = nullptr;
+    OCEAN_HIP(hipMallocAsync(&d, out_off + out_bytes, ctx->stream));
+    float* d_bodies = static_cast<float*>(d);
+    float* d_hull = reinterpret_cast<float*>(static_cast<char*>(d) + body_bytes);
+    float* d_out = reinterpret_cast<float*>(static_cast<char*>(d) + out_off);
+    hipError_t e = hipMemcpyAsync(d_bodies, bodies, body_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_hull, hull, hull_bytes, hipMemcpyHostToDevice, ctx->stream);
+    int r = OCEAN_OK;
+    if (e == hipSuccess) r = launch_body(ctx, tile, mode, iterations, d_hull, probes, d_bodies, count, d_out);
+    if (e == hipSuccess && r == OCEAN_OK) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t ef = hipFreeAsync(d, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (r != OCEAN_OK) return r;
+    if (e != hipSuccess) return hip_fail(e, "ocean_body_buoyancy copy");
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
+    return OCEAN_OK;
+}
+
+int ocean_body_buoyancy_async(ocean_ctx* ctx, int tile, int mode, int iterations, const float* hull, int probes,
+                              const float* bodies, int count, float* out, ocean_readback** req) {
+    if (!req) return fail(OCEAN_E_INVALID_ARG, "req is null");
+    *req = nullptr;
+    if (int r = check_body(ctx, tile, mode, iterations, hull, probes, bodies, count, out, true)) return r;
+    if (count == 0) return fail(OCEAN_E_INVALID_ARG, "ocean_body_buoyancy_async: no bodies, so no request");
+    if (int r = check_body_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    const size_t body_bytes = (size_t)count * 10 * 4, hull_bytes = (size_t)probes * 5 * 4;
+    return start_readback(
+        ctx, out, (size_t)count * 8 * 4,
+        [&](StageSlot* sl) {
+            // as ocean_query_surface_async: the caller's hull and bodies are consumed here, into the pinned memory
+            // the slot owns, and one upload carries both behind the slot's results
+            if (!sl->pts_host) {
+                const hipError_t e = hipHostMalloc(&sl->pts_host, kQuerySlotBytes - kQueryPointsOffset, hipHostMallocDefault);
+                if (e != hipSuccess) return e;
+            }
+            std::memcpy(sl->pts_host, bodies, body_bytes);
+            std::memcpy(static_cast<char*>(sl->pts_host) + body_bytes, hull, hull_bytes);
+            float* d_bodies = reinterpret_cast<float*>(static_cast<char*>(sl->mem) + kQueryPointsOffset);
+            float* d_hull = reinterpret_cast<float*>(static_cast<char*>(sl->mem) + kQueryPointsOffset + body_bytes);
+            const hipError_t e =
+                hipMemcpyAsync(d_bodies, sl->pts_host, body_bytes + hull_bytes, hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) return e;
+            return launch_body(ctx, tile, mode, iterations, d_hull, probes, d_bodies, count, static_cast<float*>(sl->mem)) ==
                            OCEAN_OK
                        ? hipSuccess
                        : hipErrorLaunchFailure;

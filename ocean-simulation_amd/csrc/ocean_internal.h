@@ -1,5 +1,5 @@
 // Internal declarations shared by the C-ABI layer (ocean_abi.cpp) and the HIP
-// kernel translation units (spectrum.hip, fft2/3/4k.hip, mips.hip, sample.hip, query.hip, grid.hip).  Not part of the ABI.
+// kernel translation units (spectrum.hip, fft2/3/4k.hip, mips.hip, sample.hip, query.hip, grid.hip, body.hip).  Not part of the ABI.
 #pragma once
 
 #include <hip/hip_ext.h>
@@ -137,6 +137,11 @@ hipError_t launch_query_surface(const DevView& v, int tile, int mode, int iterat
 bool grid_tile_supported(int tile_w);
 hipError_t launch_surface_grid(const DevView& v, int tile, int mode, int iterations, float lod, float x0, float z0,
                                float dx, float dz, int nx, int ny, int tile_w, float* out, hipStream_t s);
+// body.hip: buoyant bodies (ocean_body_buoyancy*), device pointers: hull float[probes][5], bodies float[count][10],
+// out float[count][8]; body_segment_width = lanes per body (the smallest power of two >= probes, at most 64)
+int body_segment_width(int probes);
+hipError_t launch_body_buoyancy(const DevView& v, int tile, int mode, int iterations, const float* hull, int probes,
+                                const float* bodies, int count, float* out, hipStream_t s);
 
 // fft4k.hip (N = 2048, 4096): four-step column passes C1 (in place on the
 // 16-wide tile-major intermediate) + C2 (with the pass-B epilogue); replace pass B.

@@ -4,8 +4,12 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy]
 //
+// With buoyancy the host reads nothing back per frame: it runs F steps, then one WaterBody::Buoyancy for five
+// boxes of 4 x 3 probes (surface mode, 4 steps) and writes hull.bin (float32 [12][5]), bodies.bin (float32
+// [5][10]) and buoyancy.bin (float32 [5][8]); the summary line carries the records too ("records", %.9g: exact
+// for fp32); tests/test_gpu_body_host.py checks them.
 // With probes the host reads no slice back: it sets five probes, runs F Updates (one surface query per
 // frame, water_body.h Readback::Probes) and writes probe_heights.bin (float32 [F][5]: ProbeHeights after
 // each Update, zeros before any query has landed), probe_results.bin (float32 [5][8]: the last query,
@@ -36,12 +40,12 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
-    if (mode != "height" && mode != "rgba" && mode != "probes") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba or probes\n");
+    if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes or buoyancy\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -62,6 +66,36 @@ int main(int argc, char** argv) {
         wb.texturesSize = n;
         wb.cascades.assign(scene, scene + (C < 4 ? C : 4));
         wb.seed = 42;
+        if (mode == "buoyancy") {
+            // a box of 4 x 3 cells (x fastest, then z), one layer: cell centres of [-1/2, 1/2]^3
+            std::vector<float> hull;
+            for (int k = 0; k < 3; ++k)
+                for (int i = 0; i < 4; ++i) {
+                    const float cell[5] = {((float)i + 0.5f) / 4.0f - 0.5f, 0.0f, ((float)k + 0.5f) / 3.0f - 0.5f, 1.0f,
+                                           1.0f / 12.0f};
+                    hull.insert(hull.end(), cell, cell + 5);
+                }
+            // five boxes: origin, body -> world quaternion (x, y, z, w), scale
+            const std::vector<float> bodies = {
+                0.0f,    0.0f,   0.0f,     0.0f,  0.0f,  0.0f,  1.0f,  4.0f, 1.0f,  2.0f,
+                37.5f,   0.25f,  -12.25f,  0.5f,  0.5f,  0.5f,  0.5f,  3.0f, 2.0f,  3.0f,
+                -410.0f, -0.5f,  250.75f,  0.0f,  0.0f,  0.6f,  0.8f,  6.0f, 1.5f,  2.5f,
+                1e4f,    0.125f, -3333.0f, 0.28f, 0.0f,  0.0f,  0.96f, 2.0f, 0.75f, 8.0f,
+                -0.5f,   -0.25f, (float)n, 0.0f,  -0.6f, 0.0f,  0.8f,  5.0f, 3.0f,  1.0f};
+            wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
+            wb.Awake();
+            for (int f = 0; f < F; ++f) wb.Update((float)f / 60.0f);
+            const std::vector<float> rec = wb.Buoyancy(hull, bodies);
+            write_bin(out + "/hull.bin", hull.data(), hull.size());
+            write_bin(out + "/bodies.bin", bodies.data(), bodies.size());
+            write_bin(out + "/buoyancy.bin", rec.data(), rec.size());
+            std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"probes\": %zu, \"bodies\": %zu, \"records\": [", F, n,
+                        (int)wb.cascades.size(), hull.size() / 5, bodies.size() / 10);
+            for (size_t i = 0; i < rec.size(); ++i) std::printf("%s%.9g", i ? ", " : "", rec[i]);
+            std::printf("]}\n");
+            wb.OnDisable();
+            return 0;
+        }
         wb.readback = mode == "height"  ? ocean_host::Readback::Height
                       : mode == "rgba" ? ocean_host::Readback::Rgba
                                        : ocean_host::Readback::Probes;

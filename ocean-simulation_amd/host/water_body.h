@@ -179,6 +179,19 @@ public:
         return out;
     }
 
+    // BuoyantObject.FixedUpdate's lookup for M bodies of P probes each (ocean.h ocean_body_buoyancy): hull is
+    // [P][5] = (cell centre in the body frame, vertical extent, volume), bodies [M][10] = (origin, body -> world
+    // quaternion xyzw, per-axis scale) -> 8 floats per body: submerged volume V, V * centroid relative to the
+    // origin, V-weighted water normal, worst residual.  Force rho g V along +y; torque rho g (-out[3], 0, out[1]).
+    std::vector<float> Buoyancy(const std::vector<float>& hull, const std::vector<float>& bodies, int iterations = 4,
+                                int mode = OCEAN_QUERY_SURFACE) const {
+        std::vector<float> out(bodies.size() / 10 * 8);
+        check(ocean_body_buoyancy(ctx_, 0, mode, iterations, hull.data(), (int)(hull.size() / 5), bodies.data(),
+                                  (int)(bodies.size() / 10), out.data()),
+              "ocean_body_buoyancy");
+        return out;
+    }
+
     std::vector<float> ReadSlice(int texture, int cascade) const {
         std::vector<float> out(SliceBytes() / 4);
         check(ocean_read(ctx_, texture, 0, cascade, out.data(), SliceBytes()), "ocean_read");

@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = (
     "ocean_reset_foam", "ocean_sample_world", "ocean_sample_world_device", "ocean_kernel_name",
     "ocean_set_column_parity", "ocean_query_surface", "ocean_query_surface_device", "ocean_query_surface_async",
     "ocean_surface_grid", "ocean_surface_grid_device", "ocean_surface_grid_async",
+    "ocean_body_buoyancy", "ocean_body_buoyancy_device", "ocean_body_buoyancy_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -73,6 +74,10 @@ QUERY_MAX_POINTS = 65536
 # ocean_surface_grid* modes and limits (ocean.h)
 GRID_VERTICES, GRID_SURFACE, GRID_HEIGHTFIELD = 0, 1, 2
 GRID_MAX_NODES = 1 << 22
+# ocean_body_buoyancy* limits (ocean.h); the modes are the queries'
+BODY_MAX_BODIES = 8192
+BODY_MAX_PROBES = 4096
+BODY_MAX_SAMPLES = 1 << 22
 
 
 class OceanError(RuntimeError):
@@ -150,6 +155,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_surface_grid": ([P, i, i, i, f, f, f, f, f, i, i, P, sz], i),
         "ocean_surface_grid_device": ([P, i, i, i, f, f, f, f, f, i, i, P, sz], i),
         "ocean_surface_grid_async": ([P, i, i, i, f, f, f, f, f, i, i, P, sz, ctypes.POINTER(P)], i),
+        "ocean_body_buoyancy": ([P, i, i, i, P, i, P, i, P], i),
+        "ocean_body_buoyancy_device": ([P, i, i, i, P, i, P, i, P], i),
+        "ocean_body_buoyancy_async": ([P, i, i, i, P, i, P, i, P, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -351,6 +359,80 @@ class OceanContext:
         return Readback(self, TEX_DISP, tile, 0, buf,
                         grid=(mode, iterations, lod, x0, z0, dx, dz, nx, ny, shape, nbytes))
 
+    @staticmethod
+    def _body_args(hull, bodies):
+        h = np.ascontiguousarray(hull, np.float32)
+        b = np.ascontiguousarray(bodies, np.float32)
+        if h.ndim != 2 or h.shape[1] != 5:
+            raise ValueError(f"hull must be float32[P][5] = (rx, ry, rz, h, v), got {h.shape}")
+        if b.ndim != 2 or b.shape[1] != 10:
+            raise ValueError(f"bodies must be float32[M][10] = (c, quaternion xyzw, scale), got {b.shape}")
+        return h, b
+
+    def body_buoyancy(self, hull, bodies, iterations: int = 4, mode: int = QUERY_SURFACE, tile: int = 0) -> np.ndarray:
+        """Buoyant bodies on the device (ocean.h ocean_body_buoyancy), blocking: hull float[P][5] = (cell centre
+        in the body frame, vertical extent, volume), shared by the bodies float[M][10] = (origin, body -> world
+        quaternion xyzw, per-axis scale) -> float32[M][8]: (submerged volume V, V * centroid relative to the
+        origin xyz, V-weighted water normal xyz, worst residual).  `mode` and `iterations` as query_surface
+        (QUERY_REFERENCE takes iterations 0); buoyancy_wrench turns the records into forces."""
+        h, b = self._body_args(hull, bodies)
+        out = np.empty((b.shape[0], 8), np.float32)
+        _check(self.lib.ocean_body_buoyancy(self._h, tile, mode, iterations, h.ctypes.data, h.shape[0], b.ctypes.data,
+                                            b.shape[0], out.ctypes.data), "ocean_body_buoyancy")
+        return out
+
+    def body_buoyancy_async(self, hull, bodies, iterations: int = 4, mode: int = QUERY_SURFACE, tile: int = 0,
+                            buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_body_buoyancy_async): the kernel runs behind the queued steps and its
+        float32[M][8] lands in pinned host memory like a read_async slice; `hull` and `bodies` are consumed by
+        the call.  Poll .done() / .wait(), then .data; `buf`: a caller-owned pinned slot of at least M x 32 B."""
+        h, b = self._body_args(hull, bodies)
+        return Readback(self, TEX_DISP, tile, 0, buf, body=(h, b, mode, iterations))
+
+    def body_buoyancy_device(self, hull_ptr: int, probes: int, bodies_ptr: int, count: int, out_ptr: int,
+                             iterations: int = 4, mode: int = QUERY_SURFACE, tile: int = 0) -> None:
+        """The device-pointer form (ocean_body_buoyancy_device): hull float[probes][5], bodies float[count][10]
+        and out float[count][8] live on this context's device (hull and bodies 4-B, out 16-B aligned); async
+        on the context's stream, after the queued steps."""
+        vp = ctypes.c_void_p
+        _check(self.lib.ocean_body_buoyancy_device(self._h, tile, mode, iterations, vp(hull_ptr), probes, vp(bodies_ptr),
+                                                   count, vp(out_ptr)), "ocean_body_buoyancy_device")
+
+    @staticmethod
+    def box_hull(nx: int, nz: int, ny: int = 1) -> np.ndarray:
+        """The unit box [-1/2, 1/2]^3 cut into nx x ny x nz cells, as a hull float32[nx * ny * nz][5]: each
+        probe is its cell's centre ((i + 1/2) / n - 1/2 along each axis), h = 1 / ny, v = 1 / (nx ny nz); x
+        fastest, then z, then y.  A body's scale makes it a box of that size."""
+        if nx < 1 or nz < 1 or ny < 1:
+            raise ValueError("nx, nz and ny must be at least 1")
+        xs = (np.arange(nx, dtype=np.float64) + 0.5) / nx - 0.5
+        zs = (np.arange(nz, dtype=np.float64) + 0.5) / nz - 0.5
+        ys = (np.arange(ny, dtype=np.float64) + 0.5) / ny - 0.5
+        hull = np.empty((ny, nz, nx, 5), np.float32)
+        hull[..., 0] = xs[None, None, :]
+        hull[..., 1] = ys[:, None, None]
+        hull[..., 2] = zs[None, :, None]
+        hull[..., 3] = 1.0 / ny
+        hull[..., 4] = 1.0 / (nx * ny * nz)
+        return hull.reshape(nx * ny * nz, 5)
+
+    @staticmethod
+    def buoyancy_wrench(out, density: float = 1000.0, gravity: float = 9.81):
+        """What a rigid-body solver takes from body_buoyancy's records float[M][8], in float64: (force [M][3] =
+        (0, density gravity out[0], 0); its application point relative to the body origin [M][3] = out[1..3] /
+        out[0], zero for a dry body; torque about the body origin [M][3] = density gravity (-out[3], 0, out[1]))."""
+        o = np.asarray(out, np.float64).reshape(-1, 8)
+        k = float(density) * float(gravity)
+        force = np.zeros((len(o), 3))
+        force[:, 1] = k * o[:, 0]
+        wet = o[:, 0] != 0.0
+        point = np.zeros((len(o), 3))
+        point[wet] = o[wet, 1:4] / o[wet, 0:1]
+        torque = np.zeros((len(o), 3))
+        torque[:, 0] = -k * o[:, 3]
+        torque[:, 2] = k * o[:, 1]
+        return force, point, torque
+
     def read_async(self, tex: int, tile: int = 0, cascade: int = 0, buf: "PinnedBuffer" = None) -> "Readback":
         """AsyncGPUReadback.Request (WaterBody.cs:288-296): copy one slice into pinned
         host memory once the queued steps finish; poll .done() / .wait(), then .data.
@@ -437,13 +519,18 @@ class PinnedBuffer:
 class Readback:
     """One ocean_read_async (or, `height`, ocean_read_height_async; or, `query` = (points float32[M][2],
     mode, iterations), ocean_query_surface_async; or, `grid` = (mode, iterations, lod, x0, z0, dx, dz, nx, ny,
-    shape, bytes), ocean_surface_grid_async) request into pinned host memory: a caller's PinnedBuffer
+    shape, bytes), ocean_surface_grid_async; or, `body` = (hull float32[P][5], bodies float32[M][10], mode,
+    iterations), ocean_body_buoyancy_async) request into pinned host memory: a caller's PinnedBuffer
     slot, or one of its own (freed by release())."""
 
     def __init__(self, ctx: "OceanContext", tex: int, tile: int, cascade: int, buf: Optional[PinnedBuffer] = None,
-                 height: bool = False, query: Optional[tuple] = None, grid: Optional[tuple] = None):
+                 height: bool = False, query: Optional[tuple] = None, grid: Optional[tuple] = None,
+                 body: Optional[tuple] = None):
         self.lib = ctx.lib
-        if grid is not None:
+        if body is not None:
+            self.shape = (body[1].shape[0], 8)
+            self.nbytes = body[1].shape[0] * 32
+        elif grid is not None:
             self.shape, self.nbytes = grid[9], grid[10]
         elif query is not None:
             self.shape = (query[0].shape[0], 8)
@@ -462,7 +549,13 @@ class Readback:
             raise ValueError(f"pinned slot of {buf.nbytes} B < request {self.nbytes} B")
         self._pinned = buf
         self._buf = buf.ptr
-        if grid is not None:
+        if body is not None:
+            where = "ocean_body_buoyancy_async"
+            hull, bodies, mode, iterations = body
+            rc = self.lib.ocean_body_buoyancy_async(ctx._h, tile, mode, iterations, hull.ctypes.data, hull.shape[0],
+                                                    bodies.ctypes.data, bodies.shape[0], self._buf,
+                                                    ctypes.byref(self._h))
+        elif grid is not None:
             where = "ocean_surface_grid_async"
             rc = self.lib.ocean_surface_grid_async(ctx._h, tile, *grid[:9], self._buf, self.nbytes,
                                                    ctypes.byref(self._h))
@@ -772,6 +865,11 @@ class WaterBody:
         """The surface over a regular grid (OceanContext.surface_grid): MeshGenerator's plane displaced as
         the domain stage of Water.shader does (GRID_VERTICES), the Eulerian surface or a height map."""
         return self.ctx.surface_grid(x0, z0, dx, dz, nx, ny, mode, iterations, lod, tile)
+
+    def Buoyancy(self, hull, bodies, iterations: int = 4, mode: int = QUERY_SURFACE, tile: int = 0) -> np.ndarray:
+        """BuoyantObject.FixedUpdate's lookup for M bodies of P probes each (OceanContext.body_buoyancy): the
+        displaced volume, where it acts and the water plane under every hull, float32[M][8]."""
+        return self.ctx.body_buoyancy(hull, bodies, iterations, mode, tile)
 
     # texture-out contract (material properties, WaterBody.cs:277-281)
     def DisplacementsTextures(self, tile: int = 0) -> np.ndarray:
