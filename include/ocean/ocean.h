@@ -34,6 +34,7 @@
  *   PLANEp float2 [T*C][N][N]     p = 0 DxDz, 1 DyDxz, 2 DyxDyz, 3 DxxDzz
  *   DISP   float4 [T*C][N][N]     DERIV float4 [T*C][N][N]  TURB  float4 [T*C][N][N]
  *   NORMAL float4 [T*C][N][N]     (derived output, OCEAN_F_NORMALS only)
+ *   VEL    float4 [T*C][N][N]     (derived output, OCEAN_F_VELOCITY only; zero after ocean_create)
  */
 #ifndef OCEAN_OCEAN_H
 #define OCEAN_OCEAN_H
@@ -66,7 +67,9 @@ extern "C" {
  *      Added later within version 4 in the same way: ocean_surface_grid, ocean_surface_grid_device,
  *      ocean_surface_grid_async.
  *      Added later within version 4 in the same way: ocean_body_buoyancy, ocean_body_buoyancy_device,
- *      ocean_body_buoyancy_async. */
+ *      ocean_body_buoyancy_async.
+ *      Added later within version 4 in the same way: OCEAN_F_VELOCITY, OCEAN_TEX_VELOCITY, ocean_query_velocity,
+ *      ocean_query_velocity_device, ocean_query_velocity_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -84,8 +87,11 @@ extern "C" {
                                           evolve -> 4 x ifft2d -> fill (WaterBody.cs:180-190) */
 #define OCEAN_F_MIPS 0x8u              /* allocate mip chains for DERIV and TURB and regenerate them
                                           in every ocean_step (WaterBody.cs:191-192, :228-229) */
+#define OCEAN_F_VELOCITY 0x10u         /* also keep the VELOCITY texture, the time derivative of DISP, written
+                                          by every ocean_step (see ocean_query_velocity); combines with every
+                                          other flag */
 
-/* texture ids for ocean_read / ocean_write / ocean_get_device_ptr */
+/* texture ids for ocean_read / ocean_read_async / ocean_write / ocean_get_device_ptr */
 enum ocean_texture {
     OCEAN_TEX_NOISE = 0,  /* _RandomNoiseTexture           WaterBody.cs:86-100 (per tile, cascade ignored) */
     OCEAN_TEX_H0 = 1,     /* _InitialSpectrumTextures      InitialSpectrum.compute:14 */
@@ -97,7 +103,9 @@ enum ocean_texture {
     OCEAN_TEX_DISP = 7,   /* _DisplacementsTextures        ResultTexturesFiller.compute:7 */
     OCEAN_TEX_DERIV = 8,  /* _DerivativesTextures          ResultTexturesFiller.compute:8 */
     OCEAN_TEX_TURB = 9,   /* _TurbulenceTextures (foam state) ResultTexturesFiller.compute:9 */
-    OCEAN_TEX_NORMAL = 10 /* derived: normalize(-Dyx/(1+Dxx), 1, -Dyz/(1+Dzz)), w = 0 */
+    OCEAN_TEX_NORMAL = 10, /* derived: normalize(-Dyx/(1+Dxx), 1, -Dyz/(1+Dzz)), w = 0 */
+    OCEAN_TEX_VELOCITY = 11 /* derived: d/dt of DISP.xyz, and dDxz/dt in .w (OCEAN_F_VELOCITY only;
+                               E_INVALID_ARG on any other context; written like OCEAN_TEX_NORMAL) */
 };
 
 typedef struct ocean_ctx ocean_ctx;
@@ -488,9 +496,61 @@ int ocean_body_buoyancy_device(ocean_ctx *ctx, int tile, int mode, int iteration
 int ocean_body_buoyancy_async(ocean_ctx *ctx, int tile, int mode, int iterations, const float *hull, int probes,
                               const float *bodies, int count, float *out, ocean_readback **req);
 
+/* Surface velocity: how the water moves, where the entries above say where it is.  The reference's only
+ * physics consumer applies drag against still water (BuoyantObject.FixedUpdate: -rb.velocity * drag); a host
+ * that wants a hull to surge with a crest, drift down-wave or be damped relative to the water that carries
+ * it, or that spawns spray and advects foam particles, needs the water's own velocity.  It is the inverse
+ * transform of dh/dt, exact in t (no second frame, no difference of two readbacks).
+ *
+ * A context created with OCEAN_F_VELOCITY owns the texture OCEAN_TEX_VELOCITY, VEL float4 [T*C][N][N], zero
+ * after ocean_create, and every ocean_step(t) writes it after the frame (and the mip chains), on the ctx
+ * stream, under the fused and the OCEAN_F_UNFUSED schedule alike; DISPLACEMENT_ONLY contexts are supported
+ * (only H0 and WAVES are read).  Without the flag a context allocates, launches and returns what it always
+ * did.  All arithmetic is fp32, one rounding per operation in the order written (no fused multiply-add).
+ * Per texel i, with h0 = H0[i], w = WAVES[i] (w.w = omega) and (ex, ey) = (cos, sin)(omega * t), the frame's
+ * own phase factor (TimeDependentSpectrum.compute:25):
+ *       A  = (h0.x * ex - h0.y * ey,     h0.x * ey + h0.y * ex)                (the two products of h(k, t), :26)
+ *       B  = (h0.z * ex - h0.w * (-ey),  h0.z * (-ey) + h0.w * ex)
+ *       g  = (A.x - B.x, A.y - B.y)
+ *       ht = (-(g.y * w.w), g.x * w.w)                                         (dh/dt = i omega (A - B))
+ *       V0, V1 = the DxDz and DyDxz packing of TimeDependentSpectrum.compute:27-43 applied to ht in place of h:
+ *            ih = (-ht.y, ht.x);  dx = (ih * w.x) * w.y;  dz = (ih * w.z) * w.y;  aux = (-ht) * w.y;
+ *            dzdx = (aux * w.x) * w.z;   V0 = (dx.x - dz.y, dx.y + dz.x);   V1 = (ht.x - dzdx.y, ht.y + dzdx.x)
+ * Both planes go through the operator of ocean_ifft2d (centred, unnormalised, permuted), exactly as it
+ * treats PLANE0 and PLANE1, and VEL[i] = (Re V0, Re V1, Im V0, Im V1).  Out-of-band texels (omega = 0) are zero.
+ * The packing is the reference's on purpose: its spectrum is not Hermitian on the Nyquist row and column,
+ * so DISP.y carries a leak of Dxz; with the same packing VEL.xyz is the exact time derivative of DISP.xyz as
+ * this library computes it, that quirk included, and VEL.w is dDxz/dt, which the packing yields with it.
+ * ocean_set_column_band with anything but the whole band, and ocean_set_column_parity with anything but
+ * -1, return OCEAN_E_UNSUPPORTED on a velocity context.  The velocity launches count as kind 2 of
+ * ocean_kernel_stats / ocean_kernel_name; kinds 0 and 1 and ocean_step_bytes keep meaning the frame's passes.
+ *
+ * ocean_query_velocity: point i of `points` is the world position q = (x, z) as float[2]; out[i] is float[8].
+ * K = `iterations` in [0, 16] steps of ocean_query_surface's fixed point, the identical operations, then
+ *       Vs(p) = sum over the cascades c, in order from 0, of VEL_c bilinearly filtered at (p.x / L_c, p.z / L_c)
+ *               (level 0; the taps and the sum of ocean_sample_world's DISP)
+ *       D = S(p_K)[0..2]
+ *       out[8i + 0..3] = Vs(p_K).x, Vs(p_K).y, Vs(p_K).z, r        (r as in ocean_query_surface)
+ *       out[8i + 4..7] = D.y, p_K.x, p_K.z, Vs(p_K).w
+ * This is the velocity of the water PARTICLE that is on the surface above q: what drag and advection need.
+ * It is not d eta / dt at the fixed position q; that is Vy - grad eta . V_xz, which a host forms from this
+ * record and the normal of ocean_query_surface (grad eta = (-n.x / n.y, -n.z / n.y)).  K = 0 is the plain
+ * cascade-summed sample of VEL at q.  Before the first ocean_step VEL is zero and the query is valid.
+ * The three forms, their validation, limits, alignment, ordering, count = 0 and *req = NULL after every
+ * failure are exactly those of ocean_query_surface, ocean_query_surface_device and ocean_query_surface_async
+ * in OCEAN_QUERY_SURFACE mode (there is no mode argument): OCEAN_E_INVALID_ARG before any device call, then
+ * OCEAN_E_UNSUPPORTED on a context without OCEAN_F_VELOCITY, OCEAN_E_STATE before ocean_init_spectrum and
+ * OCEAN_E_UNSUPPORTED on a column-parity context.  The async form stages its points and lands count x 32 B
+ * through the same readback slots. */
+int ocean_query_velocity(ocean_ctx *ctx, int tile, int iterations, const float *points, int count, float *out);
+int ocean_query_velocity_device(ocean_ctx *ctx, int tile, int iterations, const float *points, int count,
+                                float *out);
+int ocean_query_velocity_async(ocean_ctx *ctx, int tile, int iterations, const float *points, int count,
+                               float *dst, ocean_readback **req);
+
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
  * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async /
- * ocean_body_buoyancy_async request records HIP timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it
+ * ocean_body_buoyancy_async / ocean_query_velocity_async request records HIP timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it
  * is off record only untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 

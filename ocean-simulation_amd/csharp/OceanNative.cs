@@ -25,6 +25,7 @@ namespace OceanHip
         Normals = 0x2,           // also write the per-cascade NORMAL texture
         Unfused = 0x4,           // reference-shaped schedule: evolve -> 4 x IFFT -> fill
         Mips = 0x8,              // DERIV / TURB mip chains regenerated every step (GenerateMips)
+        Velocity = 0x10,         // also keep the VELOCITY texture (d/dt of the displacement), written every step
     }
 
     public enum OceanTexture : int
@@ -32,6 +33,7 @@ namespace OceanHip
         Noise = 0, H0 = 1, Waves = 2,
         Plane0 = 3, Plane1 = 4, Plane2 = 5, Plane3 = 6,   // DxDz, DyDxz, DyxDyz, DxxDzz
         Displacement = 7, Derivatives = 8, Turbulence = 9, Normal = 10,
+        Velocity = 11,   // OceanFlags.Velocity contexts only: d/dt of Displacement.xyz, dDxz/dt in .w
     }
 
     // WaterBody.cs:10-14
@@ -134,6 +136,14 @@ namespace OceanHip
         public static extern OceanStatus ocean_body_buoyancy_device(IntPtr ctx, int tile, int mode, int iterations, IntPtr hull, int probes, IntPtr bodies, int count, IntPtr output);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_body_buoyancy_async(IntPtr ctx, int tile, int mode, int iterations, [In] float[] hull, int probes, [In] float[] bodies, int count, IntPtr dst, out IntPtr request);
+        // Surface velocity (added within ABI 4 in the same way; OceanFlags.Velocity contexts).  8 floats per point: velocity
+        // x, y, z of the water particle on the surface above the point, residual, height, p.x, p.z, dDxz/dt.
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_query_velocity(IntPtr ctx, int tile, int iterations, [In] float[] points, int count, [Out] float[] output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_query_velocity_device(IntPtr ctx, int tile, int iterations, IntPtr points, int count, IntPtr output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_query_velocity_async(IntPtr ctx, int tile, int iterations, [In] float[] points, int count, IntPtr dst, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_read_async(IntPtr ctx, OceanTexture tex, int tile, int cascade, IntPtr dst, UIntPtr bytes, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

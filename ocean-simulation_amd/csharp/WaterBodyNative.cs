@@ -38,6 +38,7 @@ namespace OceanHip
         public Readback readback = Readback.Height;  // set before Awake
         public int probeMode = OceanNative.QuerySurface;  // Readback.Probes: ocean_query_surface_async's mode ...
         public int probeIterations = 4;                   // ... and fixed-point steps (0 with QueryReference)
+        public bool velocity = false;   // set before Awake: also keep the VELOCITY texture (GetWaterVelocity)
         public int probeCapacity = 64;  // probes the pinned ring is sized for at Awake (or the probes set by then, if more)
 
         IntPtr ctx = IntPtr.Zero;
@@ -55,8 +56,8 @@ namespace OceanHip
             if (OceanNative.ocean_abi_version() != OceanNative.AbiVersion)
                 throw new InvalidOperationException("liboceanhip ABI " + OceanNative.ocean_abi_version() + ", expected " +
                                                     OceanNative.AbiVersion);
-            OceanNative.Check(OceanNative.ocean_create(device, texturesSize, cascades.Length, 1, OceanFlags.Mips, out ctx),
-                              "ocean_create");
+            var flags = OceanFlags.Mips | (velocity ? OceanFlags.Velocity : OceanFlags.None);
+            OceanNative.Check(OceanNative.ocean_create(device, texturesSize, cascades.Length, 1, flags, out ctx), "ocean_create");
             ApplyParams();
             OceanNative.Check(OceanNative.ocean_generate_noise(ctx, seed), "ocean_generate_noise");
             OceanNative.Check(OceanNative.ocean_init_spectrum(ctx), "ocean_init_spectrum");
@@ -213,6 +214,17 @@ namespace OceanHip
             OceanNative.Check(OceanNative.ocean_body_buoyancy(ctx, 0, mode, iterations, hull, hull.Length / 5, bodies,
                                                               bodies.Length / 10, output), "ocean_body_buoyancy");
             return output;
+        }
+
+        // The velocity (x, y, z) of the water particle on the surface above (worldX, worldZ), at the last step's time
+        // (ocean.h ocean_query_velocity; `velocity` set before Awake): what drag relative to the water and particle
+        // advection need.  The reference has no counterpart: BuoyantObject drags against still water.
+        public float[] GetWaterVelocity(float worldX, float worldZ, int iterations = 4)
+        {
+            var output = new float[8];
+            OceanNative.Check(OceanNative.ocean_query_velocity(ctx, 0, iterations, new[] { worldX, worldZ }, 1, output),
+                              "ocean_query_velocity");
+            return new[] { output[0], output[1], output[2] };
         }
 
         // Texture-out contract: device pointers for same-process renderers (WaterBody.cs:277-281).

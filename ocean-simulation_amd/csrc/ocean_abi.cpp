@@ -98,7 +98,7 @@ namespace ocean {
 void generate_noise_host(int n, uint64_t seed, float* out);
 }
 
-// Staging slots of ocean_read_async / ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async.  A slot is device memory as large as one
+// Staging slots of ocean_read_async / ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async / ocean_query_velocity_async.  A slot is device memory as large as one
 // slice of the largest texture plus the events of the request holding it, created once with the slot: no
 // event is created per request.  `after` and `done` disable timing; the timed pair `tstart` / `tdone`
 // (ocean_readback_copy_ms) is created on the slot's first request made with readback timing on
@@ -187,6 +187,7 @@ struct ocean_options {
     int tile_w = 0;         // OCEAN_TILE_W: column-tile width of the fused path at N = 128..1024 (0: auto)
     int disp_cached = -1;   // OCEAN_DISP_CACHED: 0 / 1 force pass BQ's DISP store policy (disp_fits_cache); -1 auto
     int grid_tile = 0;      // OCEAN_GRID_TILE: nodes along x of the grid kernel's workgroup tile, 64 / 32 / 16 (0: kept)
+    int vel_nt = 0;         // OCEAN_VEL_NT=1: the velocity pack kernel writes VEL with nontemporal stores
 
     static ocean_options from_env() {
         ocean_options o;
@@ -198,6 +199,7 @@ struct ocean_options {
         if (const char* e = std::getenv("OCEAN_TILE_W")) o.tile_w = std::max(0, std::atoi(e));
         if (const char* e = std::getenv("OCEAN_DISP_CACHED")) o.disp_cached = std::strcmp(e, "auto") ? std::atoi(e) != 0 : -1;
         if (const char* e = std::getenv("OCEAN_GRID_TILE")) o.grid_tile = std::atoi(e);
+        if (const char* e = std::getenv("OCEAN_VEL_NT")) o.vel_nt = std::atoi(e) != 0;
         return o;
     }
 };
@@ -225,6 +227,8 @@ struct ocean_ctx {
     float4* deriv = nullptr;
     float4* turb = nullptr;
     float4* normal = nullptr;
+    float4* vel = nullptr;     // OCEAN_F_VELOCITY: the VELOCITY texture ...
+    float2* vplane = nullptr;  // ... and its two scratch planes, [2][U][N][N] plane-major (velocity.hip)
     float2* tw = nullptr;
     float* casc = nullptr;
     float2* tplane = nullptr;  // fused-path intermediate (tile-major), P planes
@@ -405,6 +409,7 @@ void* tex_ptr(ocean_ctx* ctx, int tex, size_t* elem_bytes, size_t* slices) {
         case OCEAN_TEX_DERIV: *elem_bytes = 16; return ctx->deriv;
         case OCEAN_TEX_TURB: *elem_bytes = 16; return ctx->turb;
         case OCEAN_TEX_NORMAL: *elem_bytes = 16; return ctx->normal;
+        case OCEAN_TEX_VELOCITY: *elem_bytes = 16; return ctx->vel;
     }
     return nullptr;
 }
@@ -412,7 +417,7 @@ void* tex_ptr(ocean_ctx* ctx, int tex, size_t* elem_bytes, size_t* slices) {
 int slice_ptr(ocean_ctx* ctx, int tex, int tile, int cascade, size_t bytes, char** out) {
     size_t eb = 0, slices = 0;
     void* base = tex_ptr(ctx, tex, &eb, &slices);
-    if (tex < OCEAN_TEX_NOISE || tex > OCEAN_TEX_NORMAL) return fail(OCEAN_E_INVALID_ARG, "unknown texture id");
+    if (tex < OCEAN_TEX_NOISE || tex > OCEAN_TEX_VELOCITY) return fail(OCEAN_E_INVALID_ARG, "unknown texture id");
     if (!base) return fail(OCEAN_E_INVALID_ARG, "texture not allocated for this context's flags");
     if (tile < 0 || tile >= ctx->T) return fail(OCEAN_E_INVALID_ARG, "tile out of range");
     if (tex != OCEAN_TEX_NOISE && (cascade < 0 || cascade >= ctx->C))
@@ -429,7 +434,7 @@ int slice_ptr(ocean_ctx* ctx, int tex, int tile, int cascade, size_t bytes, char
 void free_all(ocean_ctx* c) {
     void* ptrs[] = {c->noise, c->h0, c->h0k, c->waves, c->plane[0], c->disp, c->deriv,
                     c->turb,  c->normal, c->tw,    c->casc,     c->tplane, c->foam, c->deriv_mips, c->turb_mips,
-                    c->qside};
+                    c->qside, c->vel, c->vplane};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (auto& t : c->pending) {
@@ -464,7 +469,7 @@ int ocean_create(int device, int n, int n_cascades, int n_tiles, uint32_t flags,
     if (n_cascades < 1 || n_cascades > ocean::kMaxCascades)
         return fail(OCEAN_E_UNSUPPORTED, "n_cascades must be in [1, 5], got " + std::to_string(n_cascades));
     if (n_tiles < 1) return fail(OCEAN_E_INVALID_ARG, "n_tiles must be >= 1");
-    if (flags & ~(OCEAN_F_DISPLACEMENT_ONLY | OCEAN_F_NORMALS | OCEAN_F_UNFUSED | OCEAN_F_MIPS))
+    if (flags & ~(OCEAN_F_DISPLACEMENT_ONLY | OCEAN_F_NORMALS | OCEAN_F_UNFUSED | OCEAN_F_MIPS | OCEAN_F_VELOCITY))
         return fail(OCEAN_E_INVALID_ARG, "unknown flag bits");
     if ((flags & OCEAN_F_DISPLACEMENT_ONLY) && (flags & OCEAN_F_NORMALS))
         return fail(OCEAN_E_INVALID_ARG, "NORMALS needs the derivative planes (not DISPLACEMENT_ONLY)");
@@ -537,6 +542,10 @@ int ocean_create(int device, int n, int n_cascades, int n_tiles, uint32_t flags,
         for (int l = 1; (n >> l) >= 1; ++l) c->mip_chain += (size_t)(n >> l) * (n >> l);
         ok = ok && alloc((void**)&c->deriv_mips, c->mip_chain * U * 16);
         ok = ok && alloc((void**)&c->turb_mips, c->mip_chain * U * 16);
+    }
+    if (flags & OCEAN_F_VELOCITY) {
+        ok = ok && alloc((void**)&c->vel, tex * U * 16);
+        ok = ok && alloc((void**)&c->vplane, tex * U * 8 * 2);
     }
     const size_t tw_entries = (size_t)n + 128 + ocean::stage_twiddle_entries(n);
     ok = ok && alloc((void**)&c->tw, tw_entries * 8);
@@ -685,6 +694,51 @@ int ocean_evolve(ocean_ctx* ctx, float time) {
     return timed(ctx, 2, [&] { return ocean::launch_evolve(v, time, ctx->stream); }, "evolve");
 }
 
+namespace {
+// The operator IFFT over `ups` consecutive unit-planes from `base`, in place; its row launches are timed as
+// kind `kind_rows`, its column launches as `kind_cols`.
+int ifft_unit_planes(ocean_ctx* ctx, const ocean::DevView& v, float2* base0, int ups, int kind_rows, int kind_cols) {
+    const size_t up_elems = ctx->texels();  // one unit-plane
+    if (ctx->n == 4096) {
+        // Folded columns, in place (fft2.hip k_rowsf / k_colsf_ip): per chunk of unit-planes, rows +
+        // the decimation-in-frequency fold onto the planes' own rows (z_b at rows b L + n), then
+        // 2048-point column tiles of both sub-planes per item, back into the planes, permuted.  A chunk
+        // of at most OCEAN_OP_CHUNK_MIB stays in the Infinity Cache between the two launches (auto 256
+        // MiB: two unit-planes; docs/MEASUREMENTS.md section 8).
+        const long mib = ctx->opt.op_chunk_mib > 0 ? ctx->opt.op_chunk_mib : 256;
+        const int k = (int)std::max<size_t>(1, ((size_t)mib << 20) / (up_elems * 8));
+        for (int c0 = 0; c0 < ups; c0 += k) {
+            const int kc = std::min(k, ups - c0);
+            float2* planes = base0 + (size_t)c0 * up_elems;
+            if (int r = timed(ctx, kind_rows, [&] { return ocean::launch_ifft_fold(v, planes, kc, 0, ctx->stream); },
+                              "ifft_rows"))
+                return r;
+            if (int r = timed(ctx, kind_cols, [&] { return ocean::launch_ifft_fold(v, planes, kc, 1, ctx->stream); },
+                              "ifft_cols"))
+                return r;
+        }
+        return OCEAN_OK;
+    }
+    // In-place row and column launches per chunk of at most OCEAN_OP_CHUNK_MIB of unit-planes, so
+    // the column launch re-reads the rows' output from the Infinity Cache when the plane set is
+    // larger than it.  Auto: 256 MiB (4 x 4 x 1024^2 x 4 planes, 512 MiB, fresh data: 128 / 192 /
+    // 256 / 320 / 384 MiB / unchunked 0.69 / 0.69 / 0.736 / 0.63 / 0.60 / 0.57 of peak; cfg3's 128
+    // MiB: one chunk).  At N = 1024 / 2048 the column launch takes XCD-paired halves of 16-column
+    // tiles (fft2.hip Cols2).
+    const long mib = ctx->opt.op_chunk_mib > 0 ? ctx->opt.op_chunk_mib : 256;
+    const int k = (int)std::max<size_t>(1, ((size_t)mib << 20) / (up_elems * 8));
+    for (int c0 = 0; c0 < ups; c0 += k) {
+        const int kc = std::min(k, ups - c0);
+        float2* base = base0 + (size_t)c0 * up_elems;
+        if (int r = timed(ctx, kind_rows, [&] { return ocean::launch_ifft_rows_v2(v, base, kc, ctx->stream); }, "ifft_rows"))
+            return r;
+        if (int r = timed(ctx, kind_cols, [&] { return ocean::launch_ifft_cols_v2(v, base, kc, ctx->stream); }, "ifft_cols"))
+            return r;
+    }
+    return OCEAN_OK;
+}
+}  // namespace
+
 int ocean_ifft2d(ocean_ctx* ctx, int plane_mask) {
     OCEAN_ENTER(ctx);
     if (plane_mask < 0 || plane_mask > 15) return fail(OCEAN_E_INVALID_ARG, "plane_mask must be in [0, 15]");
@@ -692,7 +746,6 @@ int ocean_ifft2d(ocean_ctx* ctx, int plane_mask) {
         if ((plane_mask & (1 << p)) && p >= ctx->P)
             return fail(OCEAN_E_INVALID_ARG, "plane not allocated (DISPLACEMENT_ONLY context)");
     const ocean::DevView v = ctx->view();
-    const size_t up_elems = ctx->texels();  // one unit-plane
     for (int p = 0; p < 4;) {
         if (!(plane_mask & (1 << p))) {
             ++p;
@@ -700,45 +753,7 @@ int ocean_ifft2d(ocean_ctx* ctx, int plane_mask) {
         }
         int np = 1;  // run of consecutive planes: one launch per direction (planes are one allocation)
         while (p + np < 4 && (plane_mask & (1 << (p + np)))) ++np;
-        if (ctx->n == 4096) {
-            // Folded columns, in place (fft2.hip k_rowsf / k_colsf_ip): per chunk of unit-planes, rows +
-            // the decimation-in-frequency fold onto the planes' own rows (z_b at rows b L + n), then
-            // 2048-point column tiles of both sub-planes per item, back into the planes, permuted.  A chunk
-            // of at most OCEAN_OP_CHUNK_MIB stays in the Infinity Cache between the two launches (auto 256
-            // MiB: two unit-planes; docs/MEASUREMENTS.md section 8).
-            const int ups = np * (int)ctx->units();
-            const long mib = ctx->opt.op_chunk_mib > 0 ? ctx->opt.op_chunk_mib : 256;
-            const int k = (int)std::max<size_t>(1, ((size_t)mib << 20) / (up_elems * 8));
-            for (int c0 = 0; c0 < ups; c0 += k) {
-                const int kc = std::min(k, ups - c0);
-                float2* planes = ctx->plane[p] + (size_t)c0 * up_elems;
-                if (int r = timed(ctx, 0, [&] { return ocean::launch_ifft_fold(v, planes, kc, 0, ctx->stream); },
-                                  "ifft_rows"))
-                    return r;
-                if (int r = timed(ctx, 1, [&] { return ocean::launch_ifft_fold(v, planes, kc, 1, ctx->stream); },
-                                  "ifft_cols"))
-                    return r;
-            }
-            p += np;
-            continue;
-        }
-        // In-place row and column launches per chunk of at most OCEAN_OP_CHUNK_MIB of unit-planes, so
-        // the column launch re-reads the rows' output from the Infinity Cache when the plane set is
-        // larger than it.  Auto: 256 MiB (4 x 4 x 1024^2 x 4 planes, 512 MiB, fresh data: 128 / 192 /
-        // 256 / 320 / 384 MiB / unchunked 0.69 / 0.69 / 0.736 / 0.63 / 0.60 / 0.57 of peak; cfg3's 128
-        // MiB: one chunk).  At N = 1024 / 2048 the column launch takes XCD-paired halves of 16-column
-        // tiles (fft2.hip Cols2).
-        const int ups = np * (int)ctx->units();
-        const long mib = ctx->opt.op_chunk_mib > 0 ? ctx->opt.op_chunk_mib : 256;
-        const int k = (int)std::max<size_t>(1, ((size_t)mib << 20) / (up_elems * 8));
-        for (int c0 = 0; c0 < ups; c0 += k) {
-            const int kc = std::min(k, ups - c0);
-            float2* base = ctx->plane[p] + (size_t)c0 * up_elems;
-            if (int r = timed(ctx, 0, [&] { return ocean::launch_ifft_rows_v2(v, base, kc, ctx->stream); }, "ifft_rows"))
-                return r;
-            if (int r = timed(ctx, 1, [&] { return ocean::launch_ifft_cols_v2(v, base, kc, ctx->stream); }, "ifft_cols"))
-                return r;
-        }
+        if (int r = ifft_unit_planes(ctx, v, ctx->plane[p], np * (int)ctx->units(), 0, 1)) return r;
         p += np;
     }
     return OCEAN_OK;
@@ -760,6 +775,21 @@ int generate_mips(ocean_ctx* ctx) {
     const ocean::DevView v = ctx->view();
     return timed(ctx, 2, [&] { return ocean::launch_mips(v, ctx->stream); }, "mips");
 }
+
+// OCEAN_F_VELOCITY: VEL at `time`, after the frame on the ctx stream (ocean.h): dh/dt packed into the two
+// scratch planes, the operator IFFT over them as 2 U unit-planes (chunked like ocean_ifft2d), interleaved
+// into VEL.  Every launch is kind 2: kinds 0 and 1 stay the frame's two passes.
+int step_velocity(ocean_ctx* ctx, float time) {
+    if (!(ctx->flags & OCEAN_F_VELOCITY)) return OCEAN_OK;
+    const ocean::DevView v = ctx->view();
+    if (int r = timed(ctx, 2, [&] { return ocean::launch_evolve_velocity(v, ctx->vplane, time, ctx->stream); },
+                      "evolve_velocity"))
+        return r;
+    if (int r = ifft_unit_planes(ctx, v, ctx->vplane, 2 * (int)ctx->units(), 2, 2)) return r;
+    return timed(ctx, 2,
+                 [&] { return ocean::launch_pack_velocity(v, ctx->vplane, ctx->vel, ctx->opt.vel_nt != 0, ctx->stream); },
+                 "pack_velocity");
+}
 }  // namespace
 
 int ocean_step(ocean_ctx* ctx, float time) {
@@ -769,10 +799,11 @@ int ocean_step(ocean_ctx* ctx, float time) {
         if (int r = ocean_evolve(ctx, time)) return r;
         if (int r = ocean_ifft2d(ctx, (1 << ctx->P) - 1)) return r;
         if (int r = ocean_fill(ctx)) return r;
-        return generate_mips(ctx);
+    } else {
+        if (int r = step_fused(ctx, time)) return r;
     }
-    if (int r = step_fused(ctx, time)) return r;
-    return generate_mips(ctx);
+    if (int r = generate_mips(ctx)) return r;
+    return step_velocity(ctx, time);
 }
 
 namespace {
@@ -1137,7 +1168,7 @@ int ocean_write(ocean_ctx* ctx, int texture, int tile, int cascade, const void* 
 
 int ocean_get_device_ptr(ocean_ctx* ctx, int texture, void** ptr, size_t* bytes) {
     if (!ctx || !ptr || !bytes) return fail(OCEAN_E_INVALID_ARG, "null argument");
-    if (texture < OCEAN_TEX_NOISE || texture > OCEAN_TEX_NORMAL) return fail(OCEAN_E_INVALID_ARG, "unknown texture id");
+    if (texture < OCEAN_TEX_NOISE || texture > OCEAN_TEX_VELOCITY) return fail(OCEAN_E_INVALID_ARG, "unknown texture id");
     size_t eb = 0, slices = 0;
     void* base = tex_ptr(ctx, texture, &eb, &slices);
     if (!base) return fail(OCEAN_E_INVALID_ARG, "texture not allocated for this context's flags");
@@ -1301,6 +1332,87 @@ int ocean_query_surface_async(ocean_ctx* ctx, int tile, int mode, int iterations
                        : hipErrorLaunchFailure;
         },
         out);
+}
+
+// The surface-velocity queries (ocean.h): the surface query's checks (surface mode), then the context's flag
+// and state.
+static int check_velocity_state(const ocean_ctx* ctx) {
+    if (!(ctx->flags & OCEAN_F_VELOCITY))
+        return fail(OCEAN_E_UNSUPPORTED, "ocean_query_velocity needs a context created with OCEAN_F_VELOCITY");
+    if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, "ocean_init_spectrum must precede ocean_query_velocity");
+    if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, "velocity query of a column-parity shard (half the columns)");
+    return OCEAN_OK;
+}
+
+// The velocity query kernel on the ctx stream (device pointers; kind 2 of ocean_kernel_stats).
+static int launch_velocity_query(ocean_ctx* ctx, int tile, int iterations, const float* d_pts, int count, float* d_out) {
+    const ocean::DevView v = ctx->view();
+    return timed(ctx, 2,
+                 [&] { return ocean::launch_query_velocity(v, ctx->vel, tile, iterations, d_pts, count, d_out, ctx->stream); },
+                 "query_velocity");
+}
+
+int ocean_query_velocity_device(ocean_ctx* ctx, int tile, int iterations, const float* points, int count, float* out) {
+    if (int r = check_query(ctx, tile, OCEAN_QUERY_SURFACE, iterations, points, count, out, false)) return r;
+    // the kernel reads floats and writes float4 rows (ocean.h)
+    if (((uintptr_t)points & 3) || ((uintptr_t)out & 15))
+        return fail(OCEAN_E_INVALID_ARG, "ocean_query_velocity_device: points must be 4-byte and out 16-byte aligned");
+    if (int r = check_velocity_state(ctx)) return r;
+    if (count == 0) return OCEAN_OK;
+    OCEAN_ENTER(ctx);
+    return launch_velocity_query(ctx, tile, iterations, points, count, out);
+}
+
+int ocean_query_velocity(ocean_ctx* ctx, int tile, int iterations, const float* points, int count, float* out) {
+    if (int r = check_query(ctx, tile, OCEAN_QUERY_SURFACE, iterations, points, count, out, true)) return r;
+    if (int r = check_velocity_state(ctx)) return r;
+    if (count == 0) return OCEAN_OK;
+    OCEAN_ENTER(ctx);
+    const size_t in_bytes = (size_t)count * 2 * 4, out_bytes = (size_t)count * 8 * 4;
+    const size_t out_off = (in_bytes + 255) & ~(size_t)255;  // float4 output rows stay 16-B aligned
+    void* d = nullptr;
+    OCEAN_HIP(hipMallocAsync(&d, out_off + out_bytes, ctx->stream));
+    float* d_in = static_cast<float*>(d);
+    float* d_out = reinterpret_cast<float*>(static_cast<char*>(d) + out_off);
+    hipError_t e = hipMemcpyAsync(d_in, points, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+    int r = OCEAN_OK;
+    if (e == hipSuccess) r = launch_velocity_query(ctx, tile, iterations, d_in, count, d_out);
+    if (e == hipSuccess && r == OCEAN_OK) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t ef = hipFreeAsync(d, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (r != OCEAN_OK) return r;
+    if (e != hipSuccess) return hip_fail(e, "ocean_query_velocity copy");
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
+    return OCEAN_OK;
+}
+
+int ocean_query_velocity_async(ocean_ctx* ctx, int tile, int iterations, const float* points, int count, float* dst,
+                               ocean_readback** req) {
+    if (!req) return fail(OCEAN_E_INVALID_ARG, "req is null");
+    *req = nullptr;
+    if (int r = check_query(ctx, tile, OCEAN_QUERY_SURFACE, iterations, points, count, dst, true)) return r;
+    if (count == 0) return fail(OCEAN_E_INVALID_ARG, "ocean_query_velocity_async: no points, so no request");
+    if (int r = check_velocity_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    const size_t in_bytes = (size_t)count * 2 * 4;
+    return start_readback(
+        ctx, dst, (size_t)count * 8 * 4,
+        [&](StageSlot* sl) {
+            // as ocean_query_surface_async: the caller's points are consumed here, into the slot's pinned memory
+            if (!sl->pts_host) {
+                const hipError_t e = hipHostMalloc(&sl->pts_host, kQuerySlotBytes - kQueryPointsOffset, hipHostMallocDefault);
+                if (e != hipSuccess) return e;
+            }
+            std::memcpy(sl->pts_host, points, in_bytes);
+            float* d_pts = reinterpret_cast<float*>(static_cast<char*>(sl->mem) + kQueryPointsOffset);
+            const hipError_t e = hipMemcpyAsync(d_pts, sl->pts_host, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) return e;
+            return launch_velocity_query(ctx, tile, iterations, d_pts, count, static_cast<float*>(sl->mem)) == OCEAN_OK
+                       ? hipSuccess
+                       : hipErrorLaunchFailure;
+        },
+        req);
 }
 
 // Argument checks of the surface grids, before any device call (ocean.h).
@@ -1525,6 +1637,8 @@ int ocean_body_buoyancy_async(ocean_ctx* ctx, int tile, int mode, int iterations
 int ocean_set_column_band(ocean_ctx* ctx, int x_begin, int x_count) {
     OCEAN_ENTER(ctx);
     const int n = ctx->n;
+    if ((ctx->flags & OCEAN_F_VELOCITY) && (x_begin != 0 || x_count != n))
+        return fail(OCEAN_E_UNSUPPORTED, "a velocity context (OCEAN_F_VELOCITY) computes the whole band only");
     const int g = std::min(n, std::max(16, 8192 / n));  // a multiple of every tile width of the fused passes
     if (x_begin < 0 || x_count < 1 || x_begin + x_count > n || x_begin % g || x_count % g)
         return fail(OCEAN_E_INVALID_ARG, "column band [" + std::to_string(x_begin) + ", +" + std::to_string(x_count) +
@@ -1540,6 +1654,8 @@ int ocean_set_column_band(ocean_ctx* ctx, int x_begin, int x_count) {
 
 int ocean_set_column_parity(ocean_ctx* ctx, int parity) {
     OCEAN_ENTER(ctx);
+    if ((ctx->flags & OCEAN_F_VELOCITY) && parity != -1)
+        return fail(OCEAN_E_UNSUPPORTED, "a velocity context (OCEAN_F_VELOCITY) takes no column parity");
     if (parity < -1 || parity > 1) return fail(OCEAN_E_INVALID_ARG, "parity must be -1 (off), 0 or 1");
     if (parity < 0) {
         ctx->col_par = -1;

@@ -1,5 +1,5 @@
 // Internal declarations shared by the C-ABI layer (ocean_abi.cpp) and the HIP
-// kernel translation units (spectrum.hip, fft2/3/4k.hip, mips.hip, sample.hip, query.hip, grid.hip, body.hip).  Not part of the ABI.
+// kernel translation units (spectrum.hip, fft2/3/4k.hip, mips.hip, sample.hip, query.hip, grid.hip, body.hip, velocity.hip).  Not part of the ABI.
 #pragma once
 
 #include <hip/hip_ext.h>
@@ -142,6 +142,15 @@ hipError_t launch_surface_grid(const DevView& v, int tile, int mode, int iterati
 int body_segment_width(int probes);
 hipError_t launch_body_buoyancy(const DevView& v, int tile, int mode, int iterations, const float* hull, int probes,
                                 const float* bodies, int count, float* out, hipStream_t s);
+// velocity.hip: surface velocity (OCEAN_F_VELOCITY).  `scratch` is the context's two velocity planes, float2
+// [2][U][N][N] plane-major: launch_evolve_velocity writes the packed planes of dh/dt at t there (from v.h0 and
+// v.waves), the operator IFFT transforms them in place as 2 U unit-planes, launch_pack_velocity interleaves them
+// into vel float4 [U][N][N] (streamed: nontemporal stores).  launch_query_velocity: ocean_query_velocity*,
+// device pointers: pts float[count][2], out float[count][8].
+hipError_t launch_evolve_velocity(const DevView& v, float2* scratch, float t, hipStream_t s);
+hipError_t launch_pack_velocity(const DevView& v, const float2* scratch, float4* vel, bool streamed, hipStream_t s);
+hipError_t launch_query_velocity(const DevView& v, const float4* vel, int tile, int iterations, const float* pts,
+                                 int count, float* out, hipStream_t s);
 
 // fft4k.hip (N = 2048, 4096): four-step column passes C1 (in place on the
 // 16-wide tile-major intermediate) + C2 (with the pass-B epilogue); replace pass B.

@@ -4,8 +4,12 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity]
 //
+// With velocity the host reads nothing back per frame either: it creates the context with OCEAN_F_VELOCITY, runs F
+// steps, then one WaterBody::Velocity for five points (4 steps) and writes velocity_points.bin (float32 [5][2]) and
+// velocity.bin (float32 [5][8]); the summary line carries the records too ("records", %.9g: exact for fp32);
+// tests/test_gpu_velocity_host.py checks them.
 // With buoyancy the host reads nothing back per frame: it runs F steps, then one WaterBody::Buoyancy for five
 // boxes of 4 x 3 probes (surface mode, 4 steps) and writes hull.bin (float32 [12][5]), bodies.bin (float32
 // [5][10]) and buoyancy.bin (float32 [5][8]); the summary line carries the records too ("records", %.9g: exact
@@ -40,12 +44,12 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
-    if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes or buoyancy\n");
+    if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy or velocity\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -91,6 +95,23 @@ int main(int argc, char** argv) {
             write_bin(out + "/buoyancy.bin", rec.data(), rec.size());
             std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"probes\": %zu, \"bodies\": %zu, \"records\": [", F, n,
                         (int)wb.cascades.size(), hull.size() / 5, bodies.size() / 10);
+            for (size_t i = 0; i < rec.size(); ++i) std::printf("%s%.9g", i ? ", " : "", rec[i]);
+            std::printf("]}\n");
+            wb.OnDisable();
+            return 0;
+        }
+        if (mode == "velocity") {
+            // five positions (world x, world z): the probes mode's bodies
+            const std::vector<float> points = {0.0f, 0.0f, 37.5f, -12.25f, -410.0f, 250.75f, 1e4f, -3333.0f, -0.5f, (float)n};
+            wb.velocity = true;
+            wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
+            wb.Awake();
+            for (int f = 0; f < F; ++f) wb.Update((float)f / 60.0f);
+            const std::vector<float> rec = wb.Velocity(points);
+            write_bin(out + "/velocity_points.bin", points.data(), points.size());
+            write_bin(out + "/velocity.bin", rec.data(), rec.size());
+            std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"points\": %zu, \"records\": [", F, n,
+                        (int)wb.cascades.size(), points.size() / 2);
             for (size_t i = 0; i < rec.size(); ++i) std::printf("%s%.9g", i ? ", " : "", rec[i]);
             std::printf("]}\n");
             wb.OnDisable();

@@ -51,6 +51,7 @@ public:
     Readback readback = Readback::Height;  // set before Awake
     int probeMode = OCEAN_QUERY_SURFACE;   // Readback::Probes: ocean_query_surface_async's mode ...
     int probeIterations = 4;               // ... and fixed-point steps (0 with OCEAN_QUERY_REFERENCE)
+    bool velocity = false;      // set before Awake: also keep the VELOCITY texture (Velocity)
     size_t probeCapacity = 64;  // probes the pinned ring is sized for at Awake (or the probes set by then, if more)
 
     WaterBody() = default;
@@ -59,7 +60,9 @@ public:
     ~WaterBody() { OnDisable(); }
 
     void Awake() {
-        check(ocean_create(device, texturesSize, (int)cascades.size(), 1, OCEAN_F_MIPS, &ctx_), "ocean_create");
+        check(ocean_create(device, texturesSize, (int)cascades.size(), 1, OCEAN_F_MIPS | (velocity ? OCEAN_F_VELOCITY : 0u),
+                           &ctx_),
+              "ocean_create");
         ApplyParams();
         check(ocean_generate_noise(ctx_, seed), "ocean_generate_noise");
         check(ocean_init_spectrum(ctx_), "ocean_init_spectrum");
@@ -189,6 +192,17 @@ public:
         check(ocean_body_buoyancy(ctx_, 0, mode, iterations, hull.data(), (int)(hull.size() / 5), bodies.data(),
                                   (int)(bodies.size() / 10), out.data()),
               "ocean_body_buoyancy");
+        return out;
+    }
+
+    // The water's velocity at M world positions (ocean.h ocean_query_velocity; `velocity` set before Awake):
+    // points [M][2] = (world x, world z) -> 8 floats per point: velocity x, y, z of the water particle on the
+    // surface above the point, residual, height, p.x, p.z, dDxz/dt.  What drag relative to the water and particle
+    // advection need; the reference's BuoyantObject drags against still water.
+    std::vector<float> Velocity(const std::vector<float>& points, int iterations = 4) const {
+        std::vector<float> out(points.size() / 2 * 8);
+        check(ocean_query_velocity(ctx_, 0, iterations, points.data(), (int)(points.size() / 2), out.data()),
+              "ocean_query_velocity");
         return out;
     }
 

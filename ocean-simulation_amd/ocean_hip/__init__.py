@@ -46,12 +46,14 @@ F_DISPLACEMENT_ONLY = 0x1
 F_NORMALS = 0x2
 F_UNFUSED = 0x4
 F_MIPS = 0x8
+F_VELOCITY = 0x10
 
 TEX_NOISE, TEX_H0, TEX_WAVES = 0, 1, 2
 TEX_PLANE0, TEX_PLANE1, TEX_PLANE2, TEX_PLANE3 = 3, 4, 5, 6
 TEX_DISP, TEX_DERIV, TEX_TURB, TEX_NORMAL = 7, 8, 9, 10
+TEX_VELOCITY = 11
 _TEX_CHANNELS = {TEX_NOISE: 2, TEX_H0: 4, TEX_WAVES: 4, TEX_PLANE0: 2, TEX_PLANE1: 2, TEX_PLANE2: 2,
-                 TEX_PLANE3: 2, TEX_DISP: 4, TEX_DERIV: 4, TEX_TURB: 4, TEX_NORMAL: 4}
+                 TEX_PLANE3: 2, TEX_DISP: 4, TEX_DERIV: 4, TEX_TURB: 4, TEX_NORMAL: 4, TEX_VELOCITY: 4}
 
 # symbols declared in include/ocean/ocean.h
 EXPORTED_SYMBOLS = (
@@ -66,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "ocean_set_column_parity", "ocean_query_surface", "ocean_query_surface_device", "ocean_query_surface_async",
     "ocean_surface_grid", "ocean_surface_grid_device", "ocean_surface_grid_async",
     "ocean_body_buoyancy", "ocean_body_buoyancy_device", "ocean_body_buoyancy_async",
+    "ocean_query_velocity", "ocean_query_velocity_device", "ocean_query_velocity_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -158,6 +161,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_body_buoyancy": ([P, i, i, i, P, i, P, i, P], i),
         "ocean_body_buoyancy_device": ([P, i, i, i, P, i, P, i, P], i),
         "ocean_body_buoyancy_async": ([P, i, i, i, P, i, P, i, P, ctypes.POINTER(P)], i),
+        "ocean_query_velocity": ([P, i, i, P, i, P], i),
+        "ocean_query_velocity_device": ([P, i, i, P, i, P], i),
+        "ocean_query_velocity_async": ([P, i, i, P, i, P, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -311,6 +317,30 @@ class OceanContext:
         float32[M][8] lands in pinned host memory like a read_async slice; `points` is consumed by the call.
         Poll .done() / .wait(), then .data; `buf`: a caller-owned pinned slot of at least M x 32 B."""
         return Readback(self, TEX_DISP, tile, 0, buf, query=(self._query_points(points), mode, iterations))
+
+    def query_velocity(self, points, tile: int = 0, iterations: int = 4) -> np.ndarray:
+        """Surface velocity on the device (ocean.h ocean_query_velocity; F_VELOCITY contexts), blocking: points
+        float[M][2] = (world x, world z) -> float32[M][8]: (velocity x, y, z of the water particle on the
+        surface above the point, residual, height, p.x, p.z, dDxz/dt) after `iterations` fixed-point steps,
+        the same as query_surface's."""
+        p = self._query_points(points)
+        out = np.empty((p.shape[0], 8), np.float32)
+        _check(self.lib.ocean_query_velocity(self._h, tile, iterations, p.ctypes.data, p.shape[0], out.ctypes.data),
+               "ocean_query_velocity")
+        return out
+
+    def query_velocity_async(self, points, tile: int = 0, iterations: int = 4, buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_query_velocity_async), as query_surface_async: the query runs behind the
+        queued steps and its float32[M][8] lands in pinned host memory; `points` is consumed by the call."""
+        return Readback(self, TEX_DISP, tile, 0, buf, velocity=(self._query_points(points), iterations))
+
+    def query_velocity_device(self, points_ptr: int, count: int, out_ptr: int, tile: int = 0, iterations: int = 4) -> None:
+        """The device-pointer form (ocean_query_velocity_device): points float[count][2] and out float[count][8]
+        live on this context's device (points 4-B, out 16-B aligned); async on the context's stream, after
+        the queued steps."""
+        vp = ctypes.c_void_p
+        _check(self.lib.ocean_query_velocity_device(self._h, tile, iterations, vp(points_ptr), count, vp(out_ptr)),
+               "ocean_query_velocity_device")
 
     @staticmethod
     def grid_points(x0: float, z0: float, dx: float, dz: float, nx: int, ny: int) -> np.ndarray:
@@ -520,14 +550,18 @@ class Readback:
     """One ocean_read_async (or, `height`, ocean_read_height_async; or, `query` = (points float32[M][2],
     mode, iterations), ocean_query_surface_async; or, `grid` = (mode, iterations, lod, x0, z0, dx, dz, nx, ny,
     shape, bytes), ocean_surface_grid_async; or, `body` = (hull float32[P][5], bodies float32[M][10], mode,
-    iterations), ocean_body_buoyancy_async) request into pinned host memory: a caller's PinnedBuffer
+    iterations), ocean_body_buoyancy_async; or, `velocity` = (points float32[M][2], iterations),
+    ocean_query_velocity_async) request into pinned host memory: a caller's PinnedBuffer
     slot, or one of its own (freed by release())."""
 
     def __init__(self, ctx: "OceanContext", tex: int, tile: int, cascade: int, buf: Optional[PinnedBuffer] = None,
                  height: bool = False, query: Optional[tuple] = None, grid: Optional[tuple] = None,
-                 body: Optional[tuple] = None):
+                 body: Optional[tuple] = None, velocity: Optional[tuple] = None):
         self.lib = ctx.lib
-        if body is not None:
+        if velocity is not None:
+            self.shape = (velocity[0].shape[0], 8)
+            self.nbytes = velocity[0].shape[0] * 32
+        elif body is not None:
             self.shape = (body[1].shape[0], 8)
             self.nbytes = body[1].shape[0] * 32
         elif grid is not None:
@@ -549,7 +583,12 @@ class Readback:
             raise ValueError(f"pinned slot of {buf.nbytes} B < request {self.nbytes} B")
         self._pinned = buf
         self._buf = buf.ptr
-        if body is not None:
+        if velocity is not None:
+            where = "ocean_query_velocity_async"
+            pts, iterations = velocity
+            rc = self.lib.ocean_query_velocity_async(ctx._h, tile, iterations, pts.ctypes.data, pts.shape[0], self._buf,
+                                                     ctypes.byref(self._h))
+        elif body is not None:
             where = "ocean_body_buoyancy_async"
             hull, bodies, mode, iterations = body
             rc = self.lib.ocean_body_buoyancy_async(ctx._h, tile, mode, iterations, hull.ctypes.data, hull.shape[0],
@@ -673,6 +712,7 @@ class WaterBody:
     displacementOnly: bool = False
     normals: bool = False
     mips: bool = True  # WaterBody.cs:228-229 creates DERIV / TURB with mip chains
+    velocity: bool = False  # also keep the VELOCITY texture (F_VELOCITY): GetWaterVelocity
     device: int = 0
     noise: Optional[np.ndarray] = None  # explicit noise texture (tile 0), float32[N][N][2]
     readback: str = "height"  # "height" (DISP.y only), "rgba" (the whole displacement slice) or "probes"
@@ -702,6 +742,8 @@ class WaterBody:
         flags = (F_DISPLACEMENT_ONLY if self.displacementOnly else 0) | (F_NORMALS if self.normals else 0)
         if self.mips and not self.displacementOnly:
             flags |= F_MIPS
+        if self.velocity:
+            flags |= F_VELOCITY
         self.ctx = OceanContext(self.texturesSize, len(self.cascades), self.tiles, flags, self.device)
         self.ctx.set_params(self.params(), [c.as_dict() for c in self.cascades])
         if self.noise is not None:
@@ -870,6 +912,14 @@ class WaterBody:
         """BuoyantObject.FixedUpdate's lookup for M bodies of P probes each (OceanContext.body_buoyancy): the
         displaced volume, where it acts and the water plane under every hull, float32[M][8]."""
         return self.ctx.body_buoyancy(hull, bodies, iterations, mode, tile)
+
+    def GetWaterVelocity(self, worldPosition, iterations: int = 4, tile: int = 0) -> np.ndarray:
+        """The velocity (x, y, z) of the water particle on the surface above worldPosition (x and z are used, as
+        GetWaterHeight uses them), float32[3]: what drag relative to the water and particle advection need
+        (OceanContext.query_velocity; `velocity=True`).  The reference has no counterpart: its BuoyantObject
+        drags against still water.  Blocking, and exact at the last step's time."""
+        q = np.float32([[worldPosition[0], worldPosition[2]]])
+        return self.ctx.query_velocity(q, tile, iterations)[0, :3].copy()
 
     # texture-out contract (material properties, WaterBody.cs:277-281)
     def DisplacementsTextures(self, tile: int = 0) -> np.ndarray:
