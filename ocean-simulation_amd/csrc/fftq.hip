@@ -33,6 +33,24 @@ struct QTex {
     float2 q[3];
 };
 
+// Read-only tables of the pruned passes (item table, live extents), written at ocean_init_spectrum only:
+// read through the constant address space, a uniform index gives a scalar load.
+typedef __attribute__((address_space(4))) const int cint_t;
+// Their kernel arguments: empty in the dense instantiations, whose code is then the unpruned kernels' own.
+template <bool PRUNE>
+struct AqTable {};
+template <>
+struct AqTable<true> {
+    const int* tab;  // item -> (context unit << 16 | y1)
+    int ubase;       // context unit of the view's unit 0
+};
+template <bool PRUNE>
+struct BqExtents {};
+template <>
+struct BqExtents<true> {
+    const int* ext;  // live extent m_u of the view's unit u
+};
+
 // Q1..Q3 at k (a) and at -k (b) from the reference planes P(k) = o, P(-k) = om.
 __device__ __forceinline__ void q_planes(const Planes4& o, const Planes4& om, QTex& a, QTex& b) {
     const float2 h2 = hsum(o.p[1], om.p[1]), h3 = hsum(o.p[2], om.p[2]);
@@ -106,9 +124,13 @@ __device__ __forceinline__ float2* q_side(const DevView& v, int u) { return v.qs
 // that the chunk's three planes lie within 4 GiB of the base (go_aq), else the 64-bit form runs.
 // Three workgroups per CU (43.5 KiB of LDS each at N = 1024) need <= 168 VGPRs: the split pass 1 below
 // takes 170 unconstrained, 168 with two spilled.
-template <int N, bool BAND = false, int WT = 0, bool OFF32 = true>
+// PRUNE (band-limited cascades): the launch covers the live items only; item `it` is
+// tab[it] = (unit of the context << 16 | y1) (prune_items.h), ubase = the context unit of the view's unit 0.
+// The lookup is uniform per workgroup and read through the constant address space, so it stays in scalar
+// registers; rows of dead items are not written (pass BQ does not load them).
+template <int N, bool BAND = false, int WT = 0, bool OFF32 = true, bool PRUNE = false>
 __global__ __launch_bounds__(N / 4) __attribute__((amdgpu_waves_per_eu(N == 1024 ? 3 : 1, N == 1024 ? 3 : 10))) void
-k_pass_aq(DevView v, float time, int items) {
+k_pass_aq(DevView v, float time, int items, AqTable<PRUNE> pt) {
     constexpr int R0 = 4, NJ = N / R0;
     constexpr int IPU = N / 2 + 1;  // items per unit
     using TW = StageTw<N, R0>;
@@ -128,14 +150,25 @@ k_pass_aq(DevView v, float time, int items) {
     const int j = (int)threadIdx.x;
     const int jm = (NJ - j) & (NJ - 1);
     const bool j0 = (j == 0);
-    auto rows_of = [&](int it, int& u, int& y1, int& y2) {
-        u = it / IPU;
-        y1 = it - u * IPU;
+    static_assert(!(PRUNE && BAND), "column-band contexts run the dense schedule");
+    // what names item `it`: its packed table entry (PRUNE) or the index itself
+    auto key_of = [&](int it) {
+        if constexpr (PRUNE) return (int)((const cint_t*)pt.tab)[it];
+        else return it;
+    };
+    auto rows_of = [&](int key, int& u, int& y1, int& y2) {
+        if constexpr (PRUNE) {
+            u = (key >> 16) - pt.ubase;
+            y1 = key & 0xffff;
+        } else {
+            u = key / IPU;
+            y1 = key - u * IPU;
+        }
         y2 = (N - y1) & (N - 1);
     };
-    auto load_pair = [&](int it, float2 (&a)[R0], float2 (&b)[R0]) {
+    auto load_pair = [&](int key, float2 (&a)[R0], float2 (&b)[R0]) {
         int u, y1, y2;
-        rows_of(it, u, y1, y2);
+        rows_of(key, u, y1, y2);
         const float2* r1 = v.h0k + ((size_t)u * N + y1) * N;
         const float2* r2 = v.h0k + ((size_t)u * N + y2) * N;
 #pragma unroll
@@ -155,13 +188,22 @@ k_pass_aq(DevView v, float time, int items) {
     };
     float2 A[R0], B[R0], An[R0], Bn[R0];
     int it = blockIdx.x;
-    if (it < items) load_pair(it, A, B);
+    int key = 0;  // PRUNE: the current item's table entry, read one item ahead with its h0k
+    if (it < items) {
+        key = key_of(it);
+        load_pair(key, A, B);
+    }
     __syncthreads();  // twiddles, band
     for (; it < items; it += gridDim.x) {
         const int next = it + gridDim.x;
-        if (next < items) load_pair(next, An, Bn);
+        int nkey = 0;
+        if (next < items) {
+            nkey = key_of(next);
+            load_pair(nkey, An, Bn);
+        }
         int u, y1, y2;
-        rows_of(it, u, y1, y2);
+        rows_of(PRUNE ? key : it, u, y1, y2);
+        if (PRUNE) key = nkey;
         const WaveBand wb = band[(u + v.c0) % v.C];
         const bool self = (y1 == y2);
         const Win wunit = make_win(v.tplane + (size_t)u * TILES * N * W, 0);
@@ -558,8 +600,14 @@ __global__ __launch_bounds__(N / 4) void k_pass_a3pp(DevView v, float time, int 
 //   step 3: R[Q3] -> (Dyz, Dxx)         foam (Dxx, Dzz, Dxz), TURB, DERIV = (Dyx, Dyz, Dxx, Dzz)
 // Three tile loads per item run through a three-slot register ring (two steps ahead), as in
 // k_pass_b3; d0 is staged through LDS.  DC (DevView::disp_cached): DISP with default-policy stores.
-template <int N, bool BAND = false, int WT = 0, bool DC = false>
-__global__ __launch_bounds__((WT ? WT : b3_w(N)) * N / kElems) void k_pass_bq(DevView v, int items) {
+// PRUNE (band-limited cascades): ext[u] = the live extent m_u of the view's unit u.  Pass AQ wrote the
+// rows [N/2 - m_u, N/2 + m_u] only, and the rest of the region holds other units' or other frames' data, so
+// a stage-0 input of a dead row is zero per row and per lane: its load takes a lane offset past the tile's
+// window, which the buffer range check answers with 0 without a fetch.  d0 of dead rows and srow of a dead
+// row 0 are zero the same way.  The arithmetic after the loads is the dense kernel's.
+template <int N, bool BAND = false, int WT = 0, bool DC = false, bool PRUNE = false>
+__global__ __launch_bounds__((WT ? WT : b3_w(N)) * N / kElems) void k_pass_bq(DevView v, int items, BqExtents<PRUNE> pe) {
+    static_assert(!(PRUNE && BAND), "column-band contexts run the dense schedule");
     using CT = ColTile<N, WT ? WT : b3_w(N)>;
     using E = typename CT::E;
     using TW = typename CT::TW;
@@ -606,8 +654,24 @@ __global__ __launch_bounds__((WT ? WT : b3_w(N)) * N / kElems) void k_pass_bq(De
         const int u = ft / CT::tiles, x0 = (ft % CT::tiles) * W;
         return make_win(base + (size_t)u * N * N + x0, (unsigned)((N * N - x0) * 16));
     };
+    auto extent_of = [&](int u) {
+        if constexpr (PRUNE) return (int)((const cint_t*)pe.ext)[u];
+        else return N / 2;
+    };
+    constexpr int kDeadOff = 0x40000000;  // a lane offset past every window (TILE * 8 bytes), scalar offsets included
+    // row y of a unit of extent m is live iff |y - N/2| <= m: none of a flat unit's (m = -1, a uniform test)
+    auto is_live = [&](int y, int m) { return m >= 0 && (unsigned)(y - (N / 2 - m)) <= (unsigned)(2 * m); };
     auto load = [&](int item, int p, float2 (&d)[kElems]) {
         const Win w = make_win(v.tplane + (size_t)p * v.inter_stride + (size_t)full(item) * TILE, TILE * 8);
+        if constexpr (PRUNE) {
+            const int m = extent_of(full(item) / CT::tiles);
+#pragma unroll
+            for (int i = 0; i < kElems; ++i) {
+                const int vo = is_live(lj + CT::in_dy(i), m) ? toff * 8 : kDeadOff;
+                d[i] = DC ? bload2<2>(w, vo, CT::in_dy(i) * W * 8) : bload2(w, vo, CT::in_dy(i) * W * 8);
+            }
+            return;
+        }
         // DC: the intermediate's loads are nontemporal too (it is dead once read), which leaves DISP the
         // cache room; together +1.1-2.1 % at cfg3.  Without DC (chunked frames) they stay default-policy: at cfg4
         // nontemporal loads measured -1.1 to +1.1 % on two boxes (docs/MEASUREMENTS.md section 8)
@@ -636,10 +700,15 @@ __global__ __launch_bounds__((WT ? WT : b3_w(N)) * N / kElems) void k_pass_bq(De
         for (int st = 0; st < 4; ++st) {
             if (st == 0) {  // side values for step 1: the unit's d0 and, on row-0 lanes, srow
                 const float2* side = q_side(v, u);
+                const int m = extent_of(u);
 #pragma unroll
-                for (int k = 0; k < DPL; ++k)
-                    if (k * T + (int)threadIdx.x < N) dd[k] = side[k * T + threadIdx.x];
-                if (lj == 0) srow = side[N + x0 + lb];
+                for (int k = 0; k < DPL; ++k) {
+                    const int y = k * T + (int)threadIdx.x;
+                    if (PRUNE) dd[k] = make_float2(0.0f, 0.0f);
+                    if (y < N && (!PRUNE || is_live(y, m))) dd[k] = side[y];
+                }
+                if (PRUNE) srow = make_float2(0.0f, 0.0f);
+                if (lj == 0 && m == N / 2) srow = side[N + x0 + lb];
                 load(item, 2, nx2);  // R[Q3]
             } else if (st == 1) {
                 // R[Q4] = i kz R[Q1] + d0 (row 0: srow) into the free ring slot
@@ -717,21 +786,32 @@ int grid_q(K kernel, int threads, int items) {
 // k_pass_a3pp OFF32): the last byte of plane 2 lies below 4 GiB from the base.
 bool inter_off32(const DevView& v) { return ((size_t)2 * v.inter_stride + v.inter_stride) * 8 <= ((size_t)1 << 32); }
 
-template <int N, bool BAND = false, int WT = 0, bool OFF32 = true>
-hipError_t go_aq(const DevView& v, float t, hipStream_t s) {
+template <int N, bool BAND = false, int WT = 0, bool OFF32 = true, bool PRUNE = false>
+hipError_t go_aq(const DevView& v, float t, hipStream_t s, const PruneView* pv) {
     if constexpr (WT == 0) {
-        if (v.tile_w != inter_w(N)) return go_aq<N, BAND, 4, OFF32>(v, t, s);
+        if (v.tile_w != inter_w(N)) return go_aq<N, BAND, 4, OFF32, PRUNE>(v, t, s, pv);
     }
-    if constexpr (!BAND) {
-        if (v.nx != N) return go_aq<N, true, WT, OFF32>(v, t, s);
+    if constexpr (!BAND && !PRUNE) {
+        if (v.nx != N) return pv ? hipErrorInvalidValue : go_aq<N, true, WT, OFF32>(v, t, s, nullptr);
     }
     if constexpr (OFF32) {
-        if (!inter_off32(v)) return go_aq<N, BAND, WT, false>(v, t, s);
+        if (!inter_off32(v)) return go_aq<N, BAND, WT, false, PRUNE>(v, t, s, pv);
+    }
+    if constexpr (!BAND && !PRUNE) {
+        if (pv) return go_aq<N, false, WT, OFF32, true>(v, t, s, pv);
     }
     constexpr int T = N / 4;
-    const int items = v.units * (N / 2 + 1);
-    const int g = grid_q(k_pass_aq<N, BAND, WT, OFF32>, T, items);
-    launch((k_pass_aq<N, BAND, WT, OFF32>), dim3(g), dim3(T), 0, s, v, t, items);
+    if constexpr (PRUNE) {
+        if (pv->items <= 0) return hipErrorInvalidValue;  // the caller launches nothing for an empty chunk
+        // min(items, resident slots), as the dense launch: the balanced grid ceil(items / rounds) measured
+        // 5.6 % slower at cfg3 (532 workgroups against 768; docs/MEASUREMENTS.md section 13)
+        const int g = grid_q(k_pass_aq<N, BAND, WT, OFF32, true>, T, pv->items);
+        launch((k_pass_aq<N, BAND, WT, OFF32, true>), dim3(g), dim3(T), 0, s, v, t, pv->items, AqTable<true>{pv->tab, pv->ubase});
+    } else {
+        const int items = v.units * (N / 2 + 1);
+        const int g = grid_q(k_pass_aq<N, BAND, WT, OFF32>, T, items);
+        launch((k_pass_aq<N, BAND, WT, OFF32>), dim3(g), dim3(T), 0, s, v, t, items, AqTable<false>{});
+    }
     return hipGetLastError();
 }
 
@@ -747,22 +827,27 @@ hipError_t go_a3q(const DevView& v, float t, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int N, bool BAND = false, int WT = 0, bool DC = false>
-hipError_t go_bq(const DevView& v, hipStream_t s) {
+template <int N, bool BAND = false, int WT = 0, bool DC = false, bool PRUNE = false>
+hipError_t go_bq(const DevView& v, hipStream_t s, const PruneView* pv) {
     if constexpr (WT == 0) {
-        if (v.tile_w != inter_w(N)) return go_bq<N, BAND, 4, DC>(v, s);
+        if (v.tile_w != inter_w(N)) return go_bq<N, BAND, 4, DC, PRUNE>(v, s, pv);
     }
-    if constexpr (!BAND) {
-        if (v.nx != N) return go_bq<N, true, WT, DC>(v, s);
+    if constexpr (!BAND && !PRUNE) {
+        if (v.nx != N) return pv ? hipErrorInvalidValue : go_bq<N, true, WT, DC>(v, s, nullptr);
     }
     if constexpr (!DC) {
-        if (v.disp_cached) return go_bq<N, BAND, WT, true>(v, s);
+        if (v.disp_cached) return go_bq<N, BAND, WT, true, PRUNE>(v, s, pv);
+    }
+    if constexpr (!BAND && !PRUNE) {
+        if (pv) return go_bq<N, false, WT, DC, true>(v, s, pv);
     }
     constexpr int W = WT ? WT : b3_w(N);
     constexpr int T = W * N / kElems;
     const int items = v.units * (v.nx / W);
-    const int g = grid_q(k_pass_bq<N, BAND, WT, DC>, T, items);
-    launch((k_pass_bq<N, BAND, WT, DC>), dim3(g), dim3(T), 0, s, v, items);
+    const int g = grid_q(k_pass_bq<N, BAND, WT, DC, PRUNE>, T, items);
+    BqExtents<PRUNE> pe;
+    if constexpr (PRUNE) pe.ext = pv->ext;
+    launch((k_pass_bq<N, BAND, WT, DC, PRUNE>), dim3(g), dim3(T), 0, s, v, items, pe);
     return hipGetLastError();
 }
 
@@ -772,8 +857,9 @@ hipError_t go_bq(const DevView& v, hipStream_t s) {
 // than the column passes save (4 x 2048^2: 612 against 599 us per frame; docs/MEASUREMENTS.md section 3).
 bool pass_q_supported(int n, int planes) { return planes == 4 && (n == 512 || n == 1024 || n == 4096); }
 
-hipError_t launch_pass_a_q(const DevView& v, float t, hipStream_t s) {
+hipError_t launch_pass_a_q(const DevView& v, float t, hipStream_t s, const PruneView* pv) {
     if (!pass_q_supported(v.n, v.planes) || !v.qside) return hipErrorInvalidValue;
+    if (pv && (v.n > 1024 || v.xstr != 1 || v.nx != v.n)) return hipErrorInvalidValue;
     if (v.xstr == 2) {  // column parity (even / odd columns of every row): pass A3PP on mirror-pair rows
         if (v.n != 4096 || v.x0 != 0 || v.nx != v.n / 2 || !v.h0k) return hipErrorInvalidValue;
         constexpr int T = 4096 / 4;
@@ -788,16 +874,17 @@ hipError_t launch_pass_a_q(const DevView& v, float t, hipStream_t s) {
         return hipGetLastError();
     }
     switch (v.n) {
-        case 512: return v.h0k ? go_aq<512>(v, t, s) : hipErrorInvalidValue;
-        case 1024: return v.h0k ? go_aq<1024>(v, t, s) : hipErrorInvalidValue;
+        case 512: return v.h0k ? go_aq<512>(v, t, s, pv) : hipErrorInvalidValue;
+        case 1024: return v.h0k ? go_aq<1024>(v, t, s, pv) : hipErrorInvalidValue;
         case 4096: return go_a3q<4096>(v, t, s);
     }
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_pass_b_q(const DevView& v, hipStream_t s) {
+hipError_t launch_pass_b_q(const DevView& v, hipStream_t s, const PruneView* pv) {
     if (!pass_q_supported(v.n, v.planes) || v.n > 1024 || !v.qside) return hipErrorInvalidValue;
-    return v.n == 512 ? go_bq<512>(v, s) : go_bq<1024>(v, s);
+    if (pv && v.nx != v.n) return hipErrorInvalidValue;
+    return v.n == 512 ? go_bq<512>(v, s, pv) : go_bq<1024>(v, s, pv);
 }
 
 }  // namespace ocean

@@ -20,6 +20,7 @@
 #include "fft_core.h"
 #include "device_scope.h"
 #include "ocean_internal.h"
+#include "prune_items.h"
 
 namespace {
 
@@ -188,6 +189,7 @@ struct ocean_options {
     int disp_cached = -1;   // OCEAN_DISP_CACHED: 0 / 1 force pass BQ's DISP store policy (disp_fits_cache); -1 auto
     int grid_tile = 0;      // OCEAN_GRID_TILE: nodes along x of the grid kernel's workgroup tile, 64 / 32 / 16 (0: kept)
     int vel_nt = 0;         // OCEAN_VEL_NT=1: the velocity pack kernel writes VEL with nontemporal stores
+    int prune = 1;          // OCEAN_PRUNE=0: passes AQ / BQ run every row of a band-limited cascade (dense schedule)
 
     static ocean_options from_env() {
         ocean_options o;
@@ -200,6 +202,7 @@ struct ocean_options {
         if (const char* e = std::getenv("OCEAN_DISP_CACHED")) o.disp_cached = std::strcmp(e, "auto") ? std::atoi(e) != 0 : -1;
         if (const char* e = std::getenv("OCEAN_GRID_TILE")) o.grid_tile = std::atoi(e);
         if (const char* e = std::getenv("OCEAN_VEL_NT")) o.vel_nt = std::atoi(e) != 0;
+        if (const char* e = std::getenv("OCEAN_PRUNE")) o.prune = std::atoi(e);
         return o;
     }
 };
@@ -234,6 +237,12 @@ struct ocean_ctx {
     float2* tplane = nullptr;  // fused-path intermediate (tile-major), P planes
     float* foam = nullptr;     // foam state (tile-major)
     float2* qside = nullptr;   // three-plane frame side arrays (d0, srow per unit of a chunk)
+    // band-limited cascades (fftq.hip PRUNE): per-unit live extents [U], then pass AQ's item table, on the
+    // device; their host copy; valid from ocean_init_spectrum on (the frame uses them only while use_q holds,
+    // that is while h0k is the spectrum they were reduced from)
+    int* prune_dev = nullptr;
+    ocean::PruneItems prune;
+    bool prune_ready = false;
     float4* deriv_mips = nullptr;  // OCEAN_F_MIPS chains (levels 1..log2 N per slice)
     float4* turb_mips = nullptr;
     size_t mip_chain = 0;
@@ -434,7 +443,7 @@ int slice_ptr(ocean_ctx* ctx, int tex, int tile, int cascade, size_t bytes, char
 void free_all(ocean_ctx* c) {
     void* ptrs[] = {c->noise, c->h0, c->h0k, c->waves, c->plane[0], c->disp, c->deriv,
                     c->turb,  c->normal, c->tw,    c->casc,     c->tplane, c->foam, c->deriv_mips, c->turb_mips,
-                    c->qside, c->vel, c->vplane};
+                    c->qside, c->vel, c->vplane, c->prune_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (auto& t : c->pending) {
@@ -537,6 +546,8 @@ int ocean_create(int device, int n, int n_cascades, int n_tiles, uint32_t flags,
                                       ocean::pass_q_supported(n, c->P) ? chunk_units(c, q_planes(c)) : 1);
     ok = ok && alloc((void**)&c->tplane, tex * c->inter_units * 8 * c->P);
     if (ocean::pass_q_supported(n, c->P)) ok = ok && alloc((void**)&c->qside, c->inter_units * 2 * n * 8);
+    if (c->opt.prune && c->qside && c->h0k && n <= 1024 && U < (size_t)ocean::kPruneMaxUnits)
+        ok = ok && alloc((void**)&c->prune_dev, (U + U * (n / 2 + 1)) * sizeof(int));
     if (flags & OCEAN_F_NORMALS) ok = ok && alloc((void**)&c->normal, tex * U * 16);
     if (flags & OCEAN_F_MIPS) {
         for (int l = 1; (n >> l) >= 1; ++l) c->mip_chain += (size_t)(n >> l) * (n >> l);
@@ -655,6 +666,31 @@ int ocean_generate_noise(ocean_ctx* ctx, uint64_t seed) {
     return OCEAN_OK;
 }
 
+namespace {
+// Band-limited cascades: the live extent of every unit reduced from the new h0k, read back, and pass AQ's
+// item table built from it (prune_items.h).  The side arrays are cleared with it, but nothing relies on that:
+// they are per chunk slot and reused by every chunk of a frame, so what keeps pass BQ from the d0 and srow of
+// rows no item wrote is its own live-row test (fftq.hip is_live), as for the intermediate.
+int rebuild_prune(ocean_ctx* ctx) {
+    ctx->prune_ready = false;
+    if (!ctx->prune_dev) return OCEAN_OK;
+    const ocean::DevView v = ctx->view();
+    const int U = (int)ctx->units();
+    OCEAN_HIP(ocean::launch_live_extent(v, ctx->prune_dev, ctx->stream));
+    std::vector<int> ext((size_t)U);
+    OCEAN_HIP(hipMemcpyAsync(ext.data(), ctx->prune_dev, (size_t)U * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    OCEAN_HIP(hipMemsetAsync(ctx->qside, 0, ctx->inter_units * 2 * ctx->n * 8, ctx->stream));
+    OCEAN_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->prune.build(ext.data(), U, ctx->n);
+    if (!ctx->prune.items.empty())
+        OCEAN_HIP(hipMemcpyAsync(ctx->prune_dev + U, ctx->prune.items.data(), ctx->prune.items.size() * sizeof(int),
+                                 hipMemcpyHostToDevice, ctx->stream));
+    OCEAN_HIP(hipStreamSynchronize(ctx->stream));  // the table is pageable host memory
+    ctx->prune_ready = true;
+    return OCEAN_OK;
+}
+}  // namespace
+
 int ocean_init_spectrum(ocean_ctx* ctx) {
     OCEAN_ENTER(ctx);
     if (!ctx->params_set) return fail(OCEAN_E_STATE, "ocean_set_params must precede ocean_init_spectrum");
@@ -676,7 +712,7 @@ int ocean_init_spectrum(ocean_ctx* ctx) {
     ctx->spectrum_ready = true;
     ctx->h0k_valid = ctx->h0k != nullptr;
     ctx->h0_conj = true;
-    return OCEAN_OK;
+    return rebuild_prune(ctx);
 }
 
 int ocean_reset_foam(ocean_ctx* ctx) {
@@ -914,8 +950,30 @@ int step_fused(ocean_ctx* ctx, float time) {
             continue;
         }
         if (q) {
-            if (int r = timed(ctx, 0, [&] { return ocean::launch_pass_a_q(c, time, ctx->stream); }, "pass_a")) return r;
-            if (int r = timed(ctx, 1, [&] { return ocean::launch_pass_b_q(c, ctx->stream); }, "pass_b")) return r;
+            // band-limited cascades: the chunk's live items.  The pruned kernels measured 2.2 % of a frame
+            // slower than the dense ones where 1.8 % of the items are dead (a scene whose amplitudes underflow
+            // in a few outer rows) and 4.7-6.6 % faster where 22 % are (docs/MEASUREMENTS.md section 13); in
+            // between nothing is measured.  A chunk runs them when at least 1 / kPruneMinDeadShare of its items
+            // is dead, else (a fully dense context included) the dense kernels.  Both passes of a chunk take the
+            // same choice.  The choice is per chunk, so dense and pruned chunks may alternate over the same
+            // intermediate region: a dense pass AQ writes every row its pass BQ reads, and a pruned pass BQ reads
+            // no row its pass AQ did not write, so neither depends on what the other left there.
+            constexpr long kPruneMinDeadShare = 8;
+            ocean::PruneView pv{};
+            bool prune = ctx->prune_ready && !ctx->prune.dense && c.nx == ctx->n;
+            if (prune) {
+                int first = 0;
+                ctx->prune.chunk(u0, c.units, &first, &pv.items);
+                pv.tab = ctx->prune_dev + U + first;
+                pv.ubase = u0;
+                pv.ext = ctx->prune_dev + u0;
+                prune = (long)pv.items * kPruneMinDeadShare <= (long)c.units * (ctx->n / 2 + 1) * (kPruneMinDeadShare - 1);
+            }
+            const ocean::PruneView* pp = prune ? &pv : nullptr;
+            if (!prune || pv.items > 0)  // a chunk with no live item launches no pass A
+                if (int r = timed(ctx, 0, [&] { return ocean::launch_pass_a_q(c, time, ctx->stream, pp); }, "pass_a"))
+                    return r;
+            if (int r = timed(ctx, 1, [&] { return ocean::launch_pass_b_q(c, ctx->stream, pp); }, "pass_b")) return r;
             continue;
         }
         if (int r = timed(ctx, 0, [&] {

@@ -103,6 +103,9 @@ hipError_t launch_foam_import(const DevView& v, hipStream_t s);
 hipError_t launch_noise(const DevView& v, uint64_t seed, hipStream_t s);
 // h0k = h0.xy (a context whose h0k is allocated after its spectrum: ocean_set_column_parity)
 hipError_t launch_h0k_extract(const DevView& v, hipStream_t s);
+// ext[u] (device, [units]) = the largest |y - N/2| over the rows y of unit u's h0k that hold a texel != 0
+// (a NaN counts), -1 when the unit holds none
+hipError_t launch_live_extent(const DevView& v, int* ext, hipStream_t s);
 
 // fft2.hip: the operator IFFT (IFFT.InverseFastFourierTransform): persistent,
 // software-pipelined row and column(+permute) launches, in place.
@@ -164,8 +167,19 @@ hipError_t launch_pass_a_v4(const DevView& v, float t, hipStream_t s);
 // (mirror-pair rows, N = 512 / 1024) or A3Q (one row per item, N = 2048 / 4096), then pass BQ
 // (column tiles, four transforms, N <= 1024) or the four-step column passes with Q planes.
 bool pass_q_supported(int n, int planes);
-hipError_t launch_pass_a_q(const DevView& v, float t, hipStream_t s);
-hipError_t launch_pass_b_q(const DevView& v, hipStream_t s);
+// Band-limited cascades (N = 512 / 1024, full column band): the live rows of a view's units, device
+// pointers.  tab = the view's `items` live items of pass AQ, each (context unit << 16 | y1) with the
+// view's unit 0 being context unit ubase (prune_items.h); ext = the live extent m_u of each unit of the
+// view (launch_live_extent).  Pass AQ then writes live rows only and pass BQ loads live rows only, so
+// both passes of a chunk take the same PruneView or none (null: the dense schedule).
+struct PruneView {
+    const int* tab;
+    int items;
+    int ubase;
+    const int* ext;
+};
+hipError_t launch_pass_a_q(const DevView& v, float t, hipStream_t s, const PruneView* pv = nullptr);
+hipError_t launch_pass_b_q(const DevView& v, hipStream_t s, const PruneView* pv = nullptr);
 // fft4k.hip with the three-plane intermediate: C1 also forms and transforms R[Q4] into the fourth
 // plane slot; C2 runs the three-plane epilogue.
 hipError_t launch_pass_c4q(const DevView& v, hipStream_t s);

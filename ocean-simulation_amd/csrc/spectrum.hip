@@ -220,6 +220,20 @@ __global__ __launch_bounds__(256) void k_h0k_extract(DevView v) {
         v.h0k[i] = *reinterpret_cast<const float2*>(&v.h0[i]);
 }
 
+// Live extent of each unit's spectrum (launch_live_extent): one workgroup per row (u, y) of h0k; a row
+// with any texel != 0 (NaN included: !(x == 0)) raises ext[u] to |y - N/2|.  ext starts at -1.
+__global__ __launch_bounds__(256) void k_live_extent(DevView v, int* ext) {
+    const int n = v.n;
+    const int u = (int)blockIdx.x / n, y = (int)blockIdx.x % n;
+    const float2* row = v.h0k + ((size_t)u * n + y) * n;
+    bool any = false;
+    for (int x = (int)threadIdx.x; x < n; x += (int)blockDim.x) {
+        const float2 h = row[x];
+        any = any || !(h.x == 0.0f) || !(h.y == 0.0f);
+    }
+    if (__syncthreads_or(any) && threadIdx.x == 0) atomicMax(ext + u, y < n / 2 ? n / 2 - y : y - n / 2);
+}
+
 unsigned grid_for(size_t total) {
     size_t g = (total + 255) / 256;
     return (unsigned)(g < 16384 ? (g == 0 ? 1 : g) : 16384);
@@ -257,6 +271,13 @@ hipError_t launch_foam_import(const DevView& v, hipStream_t s) {
 hipError_t launch_h0k_extract(const DevView& v, hipStream_t s) {
     if (!v.h0k) return hipErrorInvalidValue;
     launch(k_h0k_extract, dim3(grid_for((size_t)v.n * v.n * v.units)), dim3(256), 0, s, v);
+    return hipGetLastError();
+}
+
+hipError_t launch_live_extent(const DevView& v, int* ext, hipStream_t s) {
+    if (!v.h0k || !ext) return hipErrorInvalidValue;
+    if (const hipError_t e = hipMemsetAsync(ext, 0xff, (size_t)v.units * sizeof(int), s)) return e;  // -1
+    launch(k_live_extent, dim3((unsigned)(v.units * v.n)), dim3(256), 0, s, v, ext);
     return hipGetLastError();
 }
 
