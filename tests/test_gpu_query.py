@@ -18,14 +18,14 @@ EPS32 = float(np.finfo(np.float32).eps)
 
 
 class Textures:
-    """The context's own DISP / DERIV / TURB of tile 0, read back once, and S(p) over them."""
+    """The context's own DISP / DERIV / TURB of tile `tile`, read back once, and S(p) over them."""
 
-    def __init__(self, ctx, cas):
+    def __init__(self, ctx, cas, tile=0):
         full = not ctx.flags & oh.F_DISPLACEMENT_ONLY
         self.lengths = [c["wavelength"] for c in cas]
-        self.disp = ctx.read_all(oh.TEX_DISP)
-        self.deriv = ctx.read_all(oh.TEX_DERIV) if full else None
-        self.turb = ctx.read_all(oh.TEX_TURB) if full else None
+        self.disp = ctx.read_all(oh.TEX_DISP, tile)
+        self.deriv = ctx.read_all(oh.TEX_DERIV, tile) if full else None
+        self.turb = ctx.read_all(oh.TEX_TURB, tile) if full else None
 
     def _pts(self, p):
         return np.concatenate([p, np.zeros((len(p), 1), f32)], axis=1)  # lod 0: level 0 also with mip chains
@@ -68,10 +68,11 @@ def restate_reference(disp0, q):
     return out
 
 
-def make_ctx(n, cas, flags=0, noise=None, times=(0.5, 1.0)):
-    ctx = oh.OceanContext(n, len(cas), 1, flags)
+def make_ctx(n, cas, flags=0, noise=None, times=(0.5, 1.0), tiles=1):
+    ctx = oh.OceanContext(n, len(cas), tiles, flags)
     ctx.set_params(O.scene_params(), cas)
-    ctx.set_noise(0, O.generate_noise(n, 20251121) if noise is None else noise)
+    for t in range(tiles):  # its own noise per tile, so that no two tiles hold the same water
+        ctx.set_noise(t, O.generate_noise(n, 20251121 + t) if noise is None else noise)
     ctx.init_spectrum()
     for t in times:
         ctx.step(t)

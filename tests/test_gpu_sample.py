@@ -70,10 +70,10 @@ def check_sample_bound(got, ref, disp, deriv, turb):
     assert not bad.any(), f"normal off its bound at {np.flatnonzero(bad)[:5]}: {dn[bad][:5]} > {nb[bad][:5]}"
 
 
-def _mips(ctx, tex, C):
+def _mips(ctx, tex, C, tile=0):
     n = ctx.n
     levels = n.bit_length() - 1
-    return [[ctx.read_mip(tex, lv, 0, c) for lv in range(1, levels + 1)] for c in range(C)]
+    return [[ctx.read_mip(tex, lv, tile, c) for lv in range(1, levels + 1)] for c in range(C)]
 
 
 @pytest.mark.parametrize("n,ncasc,flags", [(64, 1, 0), (256, 4, 0), (1024, 4, 0),

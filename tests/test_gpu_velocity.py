@@ -1,7 +1,8 @@
 """GPU tests of the surface velocity (OCEAN_F_VELOCITY, csrc/velocity.hip): the VELOCITY texture against the
 oracle's transform of velocity_planes (tests/test_velocity_abi.py) formed from the context's own H0 and WAVES,
-the finite-difference condition on the context's own DISP where no CPU transform exists (N = 4096), the
-absence of side effects on the frame, and ocean_query_velocity / _device / _async bit for bit against a numpy
+the finite-difference condition on the context's own DISP where no CPU transform exists (N = 4096), the same
+parity over several tiles, in shallow water, with the operator chunked inside the scratch and with the streamed
+pack, the absence of side effects on the frame, and ocean_query_velocity / _device / _async bit for bit against a numpy
 restatement on top of the surface query's (tests/test_gpu_query.py)."""
 import ctypes
 
@@ -10,6 +11,8 @@ import pytest
 
 import ocean_hip as oh
 import oracle as O
+from test_gpu_parity import _ctx_with_env
+from test_gpu_parity import make_ctx as parity_ctx
 from test_gpu_query import KS, Textures, make_ctx, restate_surface
 from test_gpu_sample import _points
 from test_velocity_abi import finite_difference_bound, velocity_texture
@@ -43,6 +46,97 @@ def test_velocity_texture_parity(n, ncasc, flags):
     ptr, nbytes = ctx.device_ptr(oh.TEX_VELOCITY)
     assert ptr and nbytes == ncasc * n * n * 16
     ctx.close()
+
+
+def check_velocity_parity(ctx, tile, t):
+    """VEL of `tile` at the time t of the last step against velocity_texture of that tile's own H0 and WAVES:
+    the parity tolerance, every channel and cascade."""
+    got = ctx.read_all(oh.TEX_VELOCITY, tile)
+    want = velocity_texture(ctx.read_all(oh.TEX_H0, tile), ctx.read_all(oh.TEX_WAVES, tile), t)
+    assert np.abs(want[..., :3]).max() > 0
+    for c in range(ctx.C):
+        for ch in range(4):
+            e = O.rel_err(got[c, ..., ch], want[c, ..., ch])
+            print(f"N = {ctx.n}, tile {tile}, t = {t}, cascade {c}, channel {ch}: rel err {e:.2e}")
+            assert e <= 1e-5, (ctx.n, tile, t, c, ch, e)
+
+
+@pytest.mark.parametrize("n,ncasc,tiles", [(64, 2, 3), (128, 4, 2), (512, 2, 2)])
+def test_velocity_texture_parity_over_tiles(n, ncasc, tiles):
+    """U = T * C units with their own noise per tile: k_evolve_velocity and k_pack_velocity over every unit, the
+    [2][U] plane-major scratch and the operator over its 2 U unit-planes.  Every tile's VEL against that
+    tile's own spectrum at the parity tolerance, at t = 1.25 and t = 100; the tiles' VEL differ."""
+    ctx = make_ctx(n, O.SCENE_CASCADES[:ncasc], V, times=(), tiles=tiles)
+    for t in (1.25, 100.0):
+        ctx.step(t)
+        for tile in range(tiles):
+            check_velocity_parity(ctx, tile, t)
+    vel = [ctx.read_all(oh.TEX_VELOCITY, tile) for tile in range(tiles)]
+    for a in range(tiles):
+        for b in range(a + 1, tiles):
+            for c in range(ncasc):
+                assert not np.array_equal(vel[a][c], vel[b][c]), (a, b, c)
+    ptr, nbytes = ctx.device_ptr(oh.TEX_VELOCITY)
+    assert ptr and nbytes == tiles * ncasc * n * n * 16
+    ctx.close()
+
+
+def test_velocity_texture_parity_shallow():
+    """Depth 4 (the shallow scene of test_gpu_parity.test_shallow_frames_vs_oracle): the TMA correction and the
+    finite-depth dw/dk reach the velocity path through H0.  omega itself stays the deep-water sqrt(g k) at every
+    depth, as in the reference (InitialSpectrum.compute:33-35): WAVES is the deep scene's, H0 is not."""
+    n, cas = 128, O.SCENE_CASCADES[:2]
+    deep, _ = parity_ctx(n, cas, flags=V)
+    ctx, _ = parity_ctx(n, cas, params=O.scene_params(shallow=True), flags=V)
+    np.testing.assert_array_equal(ctx.read_all(oh.TEX_WAVES), deep.read_all(oh.TEX_WAVES))
+    assert not np.array_equal(ctx.read_all(oh.TEX_H0), deep.read_all(oh.TEX_H0))
+    deep.close()
+    for t in (1.25, 100.0):
+        ctx.step(t)
+        check_velocity_parity(ctx, 0, t)
+    ctx.close()
+
+
+def test_velocity_operator_chunks():
+    """OCEAN_OP_CHUNK_MIB (read per context in ocean_create) = 6 at N = 512 with U = 4: a unit-plane is 2 MiB,
+    so the operator takes the 8 unit-planes of the [2][U] scratch as 3 + 3 + 2 -- one chunk straddles the
+    v0 / v1 boundary, one is partial.  Per step that is evolve + 3 x (rows, columns) + pack = 8 launches of
+    kind 2 against 4 in one chunk; VEL is bit-identical, and DISP, DERIV and TURB equal a plain context's."""
+    n, cas, tiles = 512, O.SCENE_CASCADES[:2], 2
+    res = []
+    for env, flags in (({"OCEAN_OP_CHUNK_MIB": "6"}, V), ({"OCEAN_OP_CHUNK_MIB": "0"}, V), ({}, 0)):
+        ctx, _ = _ctx_with_env(env, n, cas, tiles=tiles, flags=flags)
+        ctx.set_kernel_timing(True)
+        for t in (0.5, 1.0):
+            ctx.step(t)
+        launches = ctx.kernel_stats(2)[1]
+        ctx.set_kernel_timing(False)
+        texs = (oh.TEX_DISP, oh.TEX_DERIV, oh.TEX_TURB) + ((oh.TEX_VELOCITY,) if flags else ())
+        res.append((launches, [[ctx.read_all(tex, tile) for tile in range(tiles)] for tex in texs]))
+        ctx.close()
+    (n_chunked, chunked), (n_whole, whole), (n_plain, plain) = res
+    assert n_whole == n_plain + 2 * 4 and n_chunked == n_plain + 2 * 8
+    assert np.abs(whole[3][1]).max() > 0
+    np.testing.assert_array_equal(chunked[3], whole[3])
+    for a, b, c in zip(chunked[:3], whole[:3], plain):
+        np.testing.assert_array_equal(a, c)
+        np.testing.assert_array_equal(b, c)
+
+
+def test_velocity_streamed_pack():
+    """OCEAN_VEL_NT=1 selects k_pack_velocity<true>, the pack with streamed stores: the same VEL bit for bit,
+    over 2 tiles x 2 cascades at N = 128 after two steps."""
+    n, cas, tiles = 128, O.SCENE_CASCADES[:2], 2
+    res = []
+    for env, kernel in (({"OCEAN_VEL_NT": "1"}, "k_pack_velocity<true>"), ({}, "k_pack_velocity<false>")):
+        ctx, _ = _ctx_with_env(env, n, cas, tiles=tiles, flags=V)
+        for t in (0.5, 1.0):
+            ctx.step(t)
+        assert kernel in ctx.kernel_name(2)  # the step's last launch
+        res.append([ctx.read_all(oh.TEX_VELOCITY, tile) for tile in range(tiles)])
+        ctx.close()
+    assert np.abs(res[1][1]).max() > 0
+    np.testing.assert_array_equal(res[0], res[1])
 
 
 def test_velocity_4096_is_the_derivative_of_disp():
