@@ -34,13 +34,6 @@
 namespace ocean {
 namespace {
 
-// GetWaterHeight's texel index (WaterBody.cs:195-209), as k_query_reference forms it (query.hip).
-__device__ __forceinline__ int body_reference_texel(float w, int n) {
-    const float a = (float)(-(n / 2)), b = (float)(n / 2);
-    const float u = fminf(fmaxf((w - a) / (b - a), 0.0f), 1.0f);
-    return min(max((int)(u * (float)n), 0), n - 1);
-}
-
 // hull float[P][5] = (rx, ry, rz, h, v); bodies float[M][10] = (c, q, s); out[2 b], out[2 b + 1] = record b.
 template <int W>
 __global__ __launch_bounds__(256) void k_body_buoyancy(DevView v, int tile, int mode, int iterations,
@@ -72,20 +65,13 @@ __global__ __launch_bounds__(256) void k_body_buoyancy(DevView v, int tile, int 
             const float dz = (az + qw * tz) + (ux * ty - uy * tx);
             const float wx = cx + dx, wy = cy + dy, wz = cz + dz;
             float eta, r = 0.0f, nx = 0.0f, ny = 1.0f, nz = 0.0f;
-            if (mode == OCEAN_QUERY_REFERENCE) {
-                const int px = body_reference_texel(wx, v.n), py = body_reference_texel(wz, v.n);
-                eta = (v.disp + (size_t)tile * v.C * v.n * v.n)[(size_t)py * v.n + px].y;  // cascade 0 of the tile
+            if (mode != OCEAN_QUERY_REFERENCE) {
+                const float2 p = surface_fixed_point(v, tile, wx, wz, iterations);
+                const SurfaceRecord rec = surface_record(sample_cascades(v, tile, p.x, p.y, 0.0f), p, wx, wz);
+                eta = rec.at.x, r = rec.at.w, nx = rec.nf.x, ny = rec.nf.y, nz = rec.nf.z;
             } else {
-                float px = wx, pz = wz;
-                for (int k = 0; k < iterations; ++k) {  // k_query_surface's fixed point
-                    const float4 d = sample_disp(v, tile, px, pz);
-                    px = wx - d.x;
-                    pz = wz - d.z;
-                }
-                const WorldSample s = sample_cascades(v, tile, px, pz, 0.0f);
-                r = fmaxf(fabsf((px + s.disp.x) - wx), fabsf((pz + s.disp.z) - wz));
-                const float4 nrm = normal_from_deriv(s.deriv.x, s.deriv.y, s.deriv.z, s.deriv.w);  // (0, 1, 0) without DERIV
-                eta = s.disp.y, nx = nrm.x, ny = nrm.y, nz = nrm.z;
+                const int px = reference_texel(wx, v.n), py = reference_texel(wz, v.n);
+                eta = (v.disp + (size_t)tile * v.C * v.n * v.n)[(size_t)py * v.n + px].y;  // cascade 0 of the tile
             }
             const float hs = h * sy, vs = ((vol * sx) * sy) * sz;
             const float bottom = wy - 0.5f * hs;

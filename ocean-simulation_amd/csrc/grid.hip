@@ -50,22 +50,15 @@ __global__ __launch_bounds__(256) void k_surface_grid(DevView v, int tile, int i
         o[1] = normal_from_deriv(s.deriv.x, s.deriv.y, s.deriv.z, s.deriv.w);
         return;
     }
-    float px = qx, pz = qz;
-    for (int it = 0; it < iterations; ++it) {  // k_query_surface's fixed point
-        const float4 d = sample_disp(v, tile, px, pz);
-        px = qx - d.x;
-        pz = qz - d.z;
-    }
+    const float2 p = surface_fixed_point(v, tile, qx, qz, iterations);
     if (MODE == OCEAN_GRID_HEIGHTFIELD) {
-        out[k] = sample_disp(v, tile, px, pz).y;  // bit-identical to sample_cascades(...).disp.y
+        out[k] = sample_disp(v, tile, p.x, p.y).y;  // bit-identical to sample_cascades(...).disp.y
         return;
     }
-    const WorldSample s = sample_cascades(v, tile, px, pz, 0.0f);
-    const float r = fmaxf(fabsf((px + s.disp.x) - qx), fabsf((pz + s.disp.z) - qz));
-    const float4 nrm = normal_from_deriv(s.deriv.x, s.deriv.y, s.deriv.z, s.deriv.w);  // (0, 1, 0) without DERIV
+    const SurfaceRecord rec = surface_record(sample_cascades(v, tile, p.x, p.y, 0.0f), p, qx, qz);
     float4* o = reinterpret_cast<float4*>(out) + 2 * k;
-    o[0] = make_float4(s.disp.y, px, pz, r);
-    o[1] = make_float4(nrm.x, nrm.y, nrm.z, s.turb);
+    o[0] = rec.at;
+    o[1] = rec.nf;
 }
 
 template <int TW>

@@ -99,7 +99,7 @@ namespace ocean {
 void generate_noise_host(int n, uint64_t seed, float* out);
 }
 
-// Staging slots of ocean_read_async / ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async / ocean_query_velocity_async.  A slot is device memory as large as one
+// Staging slots of the readback requests (every *_async entry).  A slot is device memory as large as one
 // slice of the largest texture plus the events of the request holding it, created once with the slot: no
 // event is created per request.  `after` and `done` disable timing; the timed pair `tstart` / `tdone`
 // (ocean_readback_copy_ms) is created on the slot's first request made with readback timing on
@@ -107,18 +107,19 @@ void generate_noise_host(int n, uint64_t seed, float* out);
 // when it is released (after its host copy has landed), so a slot is never rewritten while a copy out of
 // it is pending, and no allocation or free sits between the context stream and the copy stream.  Shared
 // with the requests: it outlives a context destroyed before its requests are released.
-// A slot also holds the points and results of an ocean_query_surface_async request: results at its
-// base, the points behind them (kQueryPointsOffset), and, from the slot's first such request on, a
-// pinned host copy of the points (`pts_host`): the caller's buffer is consumed inside the call, and
-// the upload reads memory that stays put until the request is released.  An ocean_body_buoyancy_async
-// request uses the same places: its records at the base, its bodies and hull where the points go.
+// A request that runs a kernel over inputs of the caller's (start_staged_readback) lays the slot out in one
+// way: the kernel's results at the base, which is what the host copy reads; the inputs, back to back, from
+// kQueryPointsOffset on; and, from the slot's first such request on, a pinned host copy of the inputs
+// (`pts_host`), so that the caller's buffers are consumed inside the call and the upload reads memory that
+// stays put until the request is released.  Sized by the largest point query; the other consumers assert
+// that they fit.
 constexpr size_t kQueryPointsOffset = (size_t)OCEAN_QUERY_MAX_POINTS * 8 * sizeof(float);
 constexpr size_t kQuerySlotBytes = kQueryPointsOffset + (size_t)OCEAN_QUERY_MAX_POINTS * 2 * sizeof(float);
 // Workgroup tile of the grid kernel (grid.hip), nodes along x: the fastest of the shapes measured.
 constexpr int kGridTileDefault = 32;
 struct StageSlot {
     void* mem = nullptr;
-    void* pts_host = nullptr;    // pinned, OCEAN_QUERY_MAX_POINTS points (ocean_query_surface_async only)
+    void* pts_host = nullptr;    // pinned, kQuerySlotBytes - kQueryPointsOffset: the inputs of the request holding the slot
     hipEvent_t after = nullptr;  // the snapshot is in the slot (the copy stream waits for it)
     hipEvent_t done = nullptr;   // the host copy has landed (untimed requests)
     hipEvent_t tstart = nullptr, tdone = nullptr;  // timed requests: around the host copy itself
@@ -246,7 +247,7 @@ struct ocean_ctx {
     float4* deriv_mips = nullptr;  // OCEAN_F_MIPS chains (levels 1..log2 N per slice)
     float4* turb_mips = nullptr;
     size_t mip_chain = 0;
-    hipStream_t copy_stream = nullptr;  // ocean_read_async / _height_async / ocean_query_surface_async / ocean_surface_grid_async
+    hipStream_t copy_stream = nullptr;  // the host copies of the readback requests (every *_async entry)
     std::shared_ptr<StagePool> stage_pool;  // their staging slots
     bool readback_timing = false;           // ocean_set_readback_timing
     // host state.  `params` and the device `casc` are what the kernels run with; set_params
@@ -1111,6 +1112,90 @@ int start_readback(ocean_ctx* ctx, void* dst, size_t bytes, Snapshot&& snapshot,
     *out = rb;
     return OCEAN_OK;
 }
+
+// The three forms of a point consumer (world sampling, the surface and velocity queries, the surface grids,
+// the buoyant bodies) share what follows; each entry keeps its own checks and its own kernel launch, a
+// callable (const float* d_in, float* d_out) over device pointers that returns an OCEAN_* code.
+
+// One array of the caller's that a host or async form stages for its kernel.  The arrays of a request lie
+// back to back in the order given, the first at d_in (floats all: every offset is 4-byte aligned).
+struct HostInput {
+    const void* ptr;
+    size_t bytes;
+};
+
+// The blocking host form: one stream-ordered block holds the inputs from its base and the output at the next
+// 256-byte boundary (float4 output rows stay 16-B aligned); upload, launch, download, free, synchronize.  The
+// launch's own code comes first, then the copies', the free's and the synchronize's.
+template <class Launch>
+int run_staged(ocean_ctx* ctx, const char* entry, std::initializer_list<HostInput> inputs, void* out,
+               size_t out_bytes, Launch&& launch) {
+    size_t in_bytes = 0;
+    for (const HostInput& in : inputs) in_bytes += in.bytes;
+    const size_t out_off = (in_bytes + 255) & ~(size_t)255;
+    void* d = nullptr;
+    OCEAN_HIP(hipMallocAsync(&d, out_off + out_bytes, ctx->stream));
+    char* d_in = static_cast<char*>(d);
+    float* d_out = reinterpret_cast<float*>(d_in + out_off);
+    hipError_t e = hipSuccess;
+    size_t off = 0;
+    for (const HostInput& in : inputs) {
+        if (e == hipSuccess) e = hipMemcpyAsync(d_in + off, in.ptr, in.bytes, hipMemcpyHostToDevice, ctx->stream);
+        off += in.bytes;
+    }
+    int r = OCEAN_OK;
+    if (e == hipSuccess) r = launch(reinterpret_cast<const float*>(d_in), d_out);
+    if (e == hipSuccess && r == OCEAN_OK) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t ef = hipFreeAsync(d, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (r != OCEAN_OK) return r;
+    if (e != hipSuccess) return hip_fail(e, (std::string(entry) + " copy").c_str());
+    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
+    if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
+    return OCEAN_OK;
+}
+
+// The async form, a readback request whose snapshot is the kernel's result (StageSlot has the layout): the
+// caller's inputs are consumed here, into the pinned memory the slot owns, so the one upload that carries
+// them all is truly asynchronous and reads nothing of the caller's after this call returns; the kernel
+// then writes its results at the slot's base.  (start_readback reports a hipError_t, hence the bridge.)
+template <class Launch>
+int start_staged_readback(ocean_ctx* ctx, std::initializer_list<HostInput> inputs, void* dst, size_t out_bytes,
+                          Launch&& launch, ocean_readback** req) {
+    return start_readback(
+        ctx, dst, out_bytes,
+        [&](StageSlot* sl) {
+            char* d_in = static_cast<char*>(sl->mem) + kQueryPointsOffset;
+            if (inputs.size() != 0) {
+                if (!sl->pts_host) {
+                    const hipError_t e = hipHostMalloc(&sl->pts_host, kQuerySlotBytes - kQueryPointsOffset, hipHostMallocDefault);
+                    if (e != hipSuccess) return e;
+                }
+                size_t in_bytes = 0;
+                for (const HostInput& in : inputs) {
+                    std::memcpy(static_cast<char*>(sl->pts_host) + in_bytes, in.ptr, in.bytes);
+                    in_bytes += in.bytes;
+                }
+                const hipError_t e = hipMemcpyAsync(d_in, sl->pts_host, in_bytes, hipMemcpyHostToDevice, ctx->stream);
+                if (e != hipSuccess) return e;
+            }
+            return launch(reinterpret_cast<const float*>(d_in), static_cast<float*>(sl->mem)) == OCEAN_OK
+                       ? hipSuccess
+                       : hipErrorLaunchFailure;
+        },
+        req);
+}
+
+// The _device forms: the kernels read floats and write float4 rows (ocean.h).  `inputs` names the float
+// arrays `in` in the message; an entry without any passes nullptr.
+int check_aligned(const char* entry, const char* inputs, std::initializer_list<const void*> in, const void* out) {
+    bool ok = ((uintptr_t)out & 15) == 0;
+    for (const void* p : in) ok = ok && ((uintptr_t)p & 3) == 0;
+    if (ok) return OCEAN_OK;
+    return fail(OCEAN_E_INVALID_ARG, std::string(entry) + ": " +
+                                         (inputs ? std::string(inputs) + " must be 4-byte and out" : "out must be") +
+                                         " 16-byte aligned");
+}
 }  // namespace
 
 extern "C" {
@@ -1261,9 +1346,7 @@ int ocean_sample_world_device(ocean_ctx* ctx, int tile, const float* points, int
     OCEAN_ENTER(ctx);
     if (int r = check_sample(ctx, tile, points, count, out)) return r;
     if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, "world sampling of a column-parity shard (half the columns)");
-    // k_sample_world reads floats and writes float4 rows (ocean.h)
-    if (((uintptr_t)points & 3) || ((uintptr_t)out & 15))
-        return fail(OCEAN_E_INVALID_ARG, "ocean_sample_world_device: points must be 4-byte and out 16-byte aligned");
+    if (int r = check_aligned("ocean_sample_world_device", "points", {points}, out)) return r;
     const ocean::DevView v = ctx->view();
     return timed(ctx, 2, [&] { return ocean::launch_sample_world(v, tile, points, count, out, ctx->stream); },
                  "sample_world");
@@ -1273,23 +1356,10 @@ int ocean_sample_world(ocean_ctx* ctx, int tile, const float* points, int count,
     OCEAN_ENTER(ctx);
     if (int r = check_sample(ctx, tile, points, count, out)) return r;
     if (count == 0) return OCEAN_OK;
-    const size_t in_bytes = (size_t)count * 3 * 4, out_bytes = (size_t)count * 12 * 4;
-    const size_t out_off = (in_bytes + 255) & ~(size_t)255;  // float4 output rows stay 16-B aligned
-    void* d = nullptr;
-    OCEAN_HIP(hipMallocAsync(&d, out_off + out_bytes, ctx->stream));
-    float* d_in = static_cast<float*>(d);
-    float* d_out = reinterpret_cast<float*>(static_cast<char*>(d) + out_off);
-    hipError_t e = hipMemcpyAsync(d_in, points, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-    int r = OCEAN_OK;
-    if (e == hipSuccess) r = ocean_sample_world_device(ctx, tile, d_in, count, d_out);
-    if (e == hipSuccess && r == OCEAN_OK) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t ef = hipFreeAsync(d, ctx->stream);
-    const hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (r != OCEAN_OK) return r;
-    if (e != hipSuccess) return hip_fail(e, "ocean_sample_world copy");
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
-    if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
-    return OCEAN_OK;
+    return run_staged(ctx, "ocean_sample_world", {{points, (size_t)count * 3 * 4}}, out, (size_t)count * 12 * 4,
+                      [&](const float* d_pts, float* d_out) {
+                          return ocean_sample_world_device(ctx, tile, d_pts, count, d_out);
+                      });
 }
 
 // Argument checks of the surface queries, before any device call (ocean.h); `limit`: the forms that
@@ -1329,9 +1399,7 @@ static int launch_query(ocean_ctx* ctx, int tile, int mode, int iterations, cons
 int ocean_query_surface_device(ocean_ctx* ctx, int tile, int mode, int iterations, const float* points, int count,
                                float* out) {
     if (int r = check_query(ctx, tile, mode, iterations, points, count, out, false)) return r;
-    // the kernels read floats and write float4 rows (ocean.h)
-    if (((uintptr_t)points & 3) || ((uintptr_t)out & 15))
-        return fail(OCEAN_E_INVALID_ARG, "ocean_query_surface_device: points must be 4-byte and out 16-byte aligned");
+    if (int r = check_aligned("ocean_query_surface_device", "points", {points}, out)) return r;
     if (int r = check_query_state(ctx)) return r;
     if (count == 0) return OCEAN_OK;
     OCEAN_ENTER(ctx);
@@ -1344,23 +1412,10 @@ int ocean_query_surface(ocean_ctx* ctx, int tile, int mode, int iterations, cons
     if (int r = check_query_state(ctx)) return r;
     if (count == 0) return OCEAN_OK;
     OCEAN_ENTER(ctx);
-    const size_t in_bytes = (size_t)count * 2 * 4, out_bytes = (size_t)count * 8 * 4;
-    const size_t out_off = (in_bytes + 255) & ~(size_t)255;  // float4 output rows stay 16-B aligned
-    void* d = nullptr;
-    OCEAN_HIP(hipMallocAsync(&d, out_off + out_bytes, ctx->stream));
-    float* d_in = static_cast<float*>(d);
-    float* d_out = reinterpret_cast<float*>(static_cast<char*>(d) + out_off);
-    hipError_t e = hipMemcpyAsync(d_in, points, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-    int r = OCEAN_OK;
-    if (e == hipSuccess) r = launch_query(ctx, tile, mode, iterations, d_in, count, d_out);
-    if (e == hipSuccess && r == OCEAN_OK) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t ef = hipFreeAsync(d, ctx->stream);
-    const hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (r != OCEAN_OK) return r;
-    if (e != hipSuccess) return hip_fail(e, "ocean_query_surface copy");
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
-    if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
-    return OCEAN_OK;
+    return run_staged(ctx, "ocean_query_surface", {{points, (size_t)count * 2 * 4}}, out, (size_t)count * 8 * 4,
+                      [&](const float* d_pts, float* d_out) {
+                          return launch_query(ctx, tile, mode, iterations, d_pts, count, d_out);
+                      });
 }
 
 int ocean_query_surface_async(ocean_ctx* ctx, int tile, int mode, int iterations, const float* points, int count,
@@ -1371,24 +1426,9 @@ int ocean_query_surface_async(ocean_ctx* ctx, int tile, int mode, int iterations
     if (count == 0) return fail(OCEAN_E_INVALID_ARG, "ocean_query_surface_async: no points, so no request");
     if (int r = check_query_state(ctx)) return r;
     OCEAN_ENTER(ctx);
-    const size_t in_bytes = (size_t)count * 2 * 4;
-    return start_readback(
-        ctx, dst, (size_t)count * 8 * 4,
-        [&](StageSlot* sl) {
-            // the caller's points are consumed here, into pinned memory the slot owns: the upload below is
-            // then truly asynchronous and reads nothing of the caller's after this call returns
-            if (!sl->pts_host) {
-                const hipError_t e = hipHostMalloc(&sl->pts_host, kQuerySlotBytes - kQueryPointsOffset, hipHostMallocDefault);
-                if (e != hipSuccess) return e;
-            }
-            std::memcpy(sl->pts_host, points, in_bytes);
-            float* d_pts = reinterpret_cast<float*>(static_cast<char*>(sl->mem) + kQueryPointsOffset);
-            const hipError_t e = hipMemcpyAsync(d_pts, sl->pts_host, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-            if (e != hipSuccess) return e;
-            return launch_query(ctx, tile, mode, iterations, d_pts, count, static_cast<float*>(sl->mem)) == OCEAN_OK
-                       ? hipSuccess
-                       : hipErrorLaunchFailure;
-        },
+    return start_staged_readback(
+        ctx, {{points, (size_t)count * 2 * 4}}, dst, (size_t)count * 8 * 4,
+        [&](const float* d_pts, float* d_out) { return launch_query(ctx, tile, mode, iterations, d_pts, count, d_out); },
         out);
 }
 
@@ -1412,9 +1452,7 @@ static int launch_velocity_query(ocean_ctx* ctx, int tile, int iterations, const
 
 int ocean_query_velocity_device(ocean_ctx* ctx, int tile, int iterations, const float* points, int count, float* out) {
     if (int r = check_query(ctx, tile, OCEAN_QUERY_SURFACE, iterations, points, count, out, false)) return r;
-    // the kernel reads floats and writes float4 rows (ocean.h)
-    if (((uintptr_t)points & 3) || ((uintptr_t)out & 15))
-        return fail(OCEAN_E_INVALID_ARG, "ocean_query_velocity_device: points must be 4-byte and out 16-byte aligned");
+    if (int r = check_aligned("ocean_query_velocity_device", "points", {points}, out)) return r;
     if (int r = check_velocity_state(ctx)) return r;
     if (count == 0) return OCEAN_OK;
     OCEAN_ENTER(ctx);
@@ -1426,23 +1464,10 @@ int ocean_query_velocity(ocean_ctx* ctx, int tile, int iterations, const float* 
     if (int r = check_velocity_state(ctx)) return r;
     if (count == 0) return OCEAN_OK;
     OCEAN_ENTER(ctx);
-    const size_t in_bytes = (size_t)count * 2 * 4, out_bytes = (size_t)count * 8 * 4;
-    const size_t out_off = (in_bytes + 255) & ~(size_t)255;  // float4 output rows stay 16-B aligned
-    void* d = nullptr;
-    OCEAN_HIP(hipMallocAsync(&d, out_off + out_bytes, ctx->stream));
-    float* d_in = static_cast<float*>(d);
-    float* d_out = reinterpret_cast<float*>(static_cast<char*>(d) + out_off);
-    hipError_t e = hipMemcpyAsync(d_in, points, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-    int r = OCEAN_OK;
-    if (e == hipSuccess) r = launch_velocity_query(ctx, tile, iterations, d_in, count, d_out);
-    if (e == hipSuccess && r == OCEAN_OK) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t ef = hipFreeAsync(d, ctx->stream);
-    const hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (r != OCEAN_OK) return r;
-    if (e != hipSuccess) return hip_fail(e, "ocean_query_velocity copy");
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
-    if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
-    return OCEAN_OK;
+    return run_staged(ctx, "ocean_query_velocity", {{points, (size_t)count * 2 * 4}}, out, (size_t)count * 8 * 4,
+                      [&](const float* d_pts, float* d_out) {
+                          return launch_velocity_query(ctx, tile, iterations, d_pts, count, d_out);
+                      });
 }
 
 int ocean_query_velocity_async(ocean_ctx* ctx, int tile, int iterations, const float* points, int count, float* dst,
@@ -1453,23 +1478,9 @@ int ocean_query_velocity_async(ocean_ctx* ctx, int tile, int iterations, const f
     if (count == 0) return fail(OCEAN_E_INVALID_ARG, "ocean_query_velocity_async: no points, so no request");
     if (int r = check_velocity_state(ctx)) return r;
     OCEAN_ENTER(ctx);
-    const size_t in_bytes = (size_t)count * 2 * 4;
-    return start_readback(
-        ctx, dst, (size_t)count * 8 * 4,
-        [&](StageSlot* sl) {
-            // as ocean_query_surface_async: the caller's points are consumed here, into the slot's pinned memory
-            if (!sl->pts_host) {
-                const hipError_t e = hipHostMalloc(&sl->pts_host, kQuerySlotBytes - kQueryPointsOffset, hipHostMallocDefault);
-                if (e != hipSuccess) return e;
-            }
-            std::memcpy(sl->pts_host, points, in_bytes);
-            float* d_pts = reinterpret_cast<float*>(static_cast<char*>(sl->mem) + kQueryPointsOffset);
-            const hipError_t e = hipMemcpyAsync(d_pts, sl->pts_host, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-            if (e != hipSuccess) return e;
-            return launch_velocity_query(ctx, tile, iterations, d_pts, count, static_cast<float*>(sl->mem)) == OCEAN_OK
-                       ? hipSuccess
-                       : hipErrorLaunchFailure;
-        },
+    return start_staged_readback(
+        ctx, {{points, (size_t)count * 2 * 4}}, dst, (size_t)count * 8 * 4,
+        [&](const float* d_pts, float* d_out) { return launch_velocity_query(ctx, tile, iterations, d_pts, count, d_out); },
         req);
 }
 
@@ -1524,8 +1535,8 @@ static int launch_grid(ocean_ctx* ctx, int tile, int mode, int iterations, float
 int ocean_surface_grid_device(ocean_ctx* ctx, int tile, int mode, int iterations, float lod, float x0, float z0,
                               float dx, float dz, int nx, int ny, float* out, size_t bytes) {
     if (int r = check_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out, bytes)) return r;
-    // the kernel writes float4 rows (one float per node in heightfield mode; one rule for all modes, ocean.h)
-    if ((uintptr_t)out & 15) return fail(OCEAN_E_INVALID_ARG, "ocean_surface_grid_device: out must be 16-byte aligned");
+    // one rule for all modes, though heightfield mode writes one float per node (ocean.h)
+    if (int r = check_aligned("ocean_surface_grid_device", nullptr, {}, out)) return r;
     if (int r = check_grid_state(ctx)) return r;
     OCEAN_ENTER(ctx);
     return launch_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out);
@@ -1536,18 +1547,10 @@ int ocean_surface_grid(ocean_ctx* ctx, int tile, int mode, int iterations, float
     if (int r = check_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out, bytes)) return r;
     if (int r = check_grid_state(ctx)) return r;
     OCEAN_ENTER(ctx);
-    void* d = nullptr;
-    OCEAN_HIP(hipMallocAsync(&d, bytes, ctx->stream));
-    const int r = launch_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, static_cast<float*>(d));
-    hipError_t e = hipSuccess;
-    if (r == OCEAN_OK) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t ef = hipFreeAsync(d, ctx->stream);
-    const hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (r != OCEAN_OK) return r;
-    if (e != hipSuccess) return hip_fail(e, "ocean_surface_grid copy");
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
-    if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
-    return OCEAN_OK;
+    // no inputs: the nodes follow from the six numbers
+    return run_staged(ctx, "ocean_surface_grid", {}, out, bytes, [&](const float*, float* d_out) {
+        return launch_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, d_out);
+    });
 }
 
 int ocean_surface_grid_async(ocean_ctx* ctx, int tile, int mode, int iterations, float lod, float x0, float z0,
@@ -1562,14 +1565,9 @@ int ocean_surface_grid_async(ocean_ctx* ctx, int tile, int mode, int iterations,
                                              std::to_string(slot_bytes) + " B");
     if (int r = check_grid_state(ctx)) return r;
     OCEAN_ENTER(ctx);
-    return start_readback(
-        ctx, out, bytes,
-        [&](StageSlot* sl) {
-            return launch_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, static_cast<float*>(sl->mem)) ==
-                           OCEAN_OK
-                       ? hipSuccess
-                       : hipErrorLaunchFailure;
-        },
+    return start_staged_readback(
+        ctx, {}, out, bytes,
+        [&](const float*, float* d_out) { return launch_grid(ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, d_out); },
         req);
 }
 
@@ -1623,9 +1621,7 @@ static_assert((size_t)OCEAN_BODY_MAX_BODIES * 8 * sizeof(float) <= kQueryPointsO
 int ocean_body_buoyancy_device(ocean_ctx* ctx, int tile, int mode, int iterations, const float* hull, int probes,
                                const float* bodies, int count, float* out) {
     if (int r = check_body(ctx, tile, mode, iterations, hull, probes, bodies, count, out, false)) return r;
-    // the kernel reads floats and writes float4 rows (ocean.h)
-    if (((uintptr_t)hull & 3) || ((uintptr_t)bodies & 3) || ((uintptr_t)out & 15))
-        return fail(OCEAN_E_INVALID_ARG, "ocean_body_buoyancy_device: hull and bodies must be 4-byte and out 16-byte aligned");
+    if (int r = check_aligned("ocean_body_buoyancy_device", "hull and bodies", {hull, bodies}, out)) return r;
     if (int r = check_body_state(ctx)) return r;
     if (count == 0) return OCEAN_OK;
     OCEAN_ENTER(ctx);
@@ -1638,25 +1634,10 @@ int ocean_body_buoyancy(ocean_ctx* ctx, int tile, int mode, int iterations, cons
     if (int r = check_body_state(ctx)) return r;
     if (count == 0) return OCEAN_OK;
     OCEAN_ENTER(ctx);
-    const size_t body_bytes = (size_t)count * 10 * 4, hull_bytes = (size_t)probes * 5 * 4, out_bytes = (size_t)count * 8 * 4;
-    const size_t out_off = (body_bytes + hull_bytes + 255) & ~(size_t)255;  // float4 output rows stay 16-B aligned
-    void* d = nullptr;
-    OCEAN_HIP(hipMallocAsync(&d, out_off + out_bytes, ctx->stream));
-    float* d_bodies = static_cast<float*>(d);
-    float* d_hull = reinterpret_cast<float*>(static_cast<char*>(d) + body_bytes);
-    float* d_out = reinterpret_cast<float*>(static_cast<char*>(d) + out_off);
-    hipError_t e = hipMemcpyAsync(d_bodies, bodies, body_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_hull, hull, hull_bytes, hipMemcpyHostToDevice, ctx->stream);
-    int r = OCEAN_OK;
-    if (e == hipSuccess) r = launch_body(ctx, tile, mode, iterations, d_hull, probes, d_bodies, count, d_out);
-    if (e == hipSuccess && r == OCEAN_OK) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t ef = hipFreeAsync(d, ctx->stream);
-    const hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (r != OCEAN_OK) return r;
-    if (e != hipSuccess) return hip_fail(e, "ocean_body_buoyancy copy");
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
-    if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
-    return OCEAN_OK;
+    return run_staged(ctx, "ocean_body_buoyancy", {{bodies, (size_t)count * 10 * 4}, {hull, (size_t)probes * 5 * 4}}, out,
+                      (size_t)count * 8 * 4, [&](const float* d_in, float* d_out) {
+                          return launch_body(ctx, tile, mode, iterations, d_in + (size_t)count * 10, probes, d_in, count, d_out);
+                      });
 }
 
 int ocean_body_buoyancy_async(ocean_ctx* ctx, int tile, int mode, int iterations, const float* hull, int probes,
@@ -1667,27 +1648,10 @@ int ocean_body_buoyancy_async(ocean_ctx* ctx, int tile, int mode, int iterations
     if (count == 0) return fail(OCEAN_E_INVALID_ARG, "ocean_body_buoyancy_async: no bodies, so no request");
     if (int r = check_body_state(ctx)) return r;
     OCEAN_ENTER(ctx);
-    const size_t body_bytes = (size_t)count * 10 * 4, hull_bytes = (size_t)probes * 5 * 4;
-    return start_readback(
-        ctx, out, (size_t)count * 8 * 4,
-        [&](StageSlot* sl) {
-            // as ocean_query_surface_async: the caller's hull and bodies are consumed here, into the pinned memory
-            // the slot owns, and one upload carries both behind the slot's results
-            if (!sl->pts_host) {
-                const hipError_t e = hipHostMalloc(&sl->pts_host, kQuerySlotBytes - kQueryPointsOffset, hipHostMallocDefault);
-                if (e != hipSuccess) return e;
-            }
-            std::memcpy(sl->pts_host, bodies, body_bytes);
-            std::memcpy(static_cast<char*>(sl->pts_host) + body_bytes, hull, hull_bytes);
-            float* d_bodies = reinterpret_cast<float*>(static_cast<char*>(sl->mem) + kQueryPointsOffset);
-            float* d_hull = reinterpret_cast<float*>(static_cast<char*>(sl->mem) + kQueryPointsOffset + body_bytes);
-            const hipError_t e =
-                hipMemcpyAsync(d_bodies, sl->pts_host, body_bytes + hull_bytes, hipMemcpyHostToDevice, ctx->stream);
-            if (e != hipSuccess) return e;
-            return launch_body(ctx, tile, mode, iterations, d_hull, probes, d_bodies, count, static_cast<float*>(sl->mem)) ==
-                           OCEAN_OK
-                       ? hipSuccess
-                       : hipErrorLaunchFailure;
+    return start_staged_readback(
+        ctx, {{bodies, (size_t)count * 10 * 4}, {hull, (size_t)probes * 5 * 4}}, out, (size_t)count * 8 * 4,
+        [&](const float* d_in, float* d_out) {
+            return launch_body(ctx, tile, mode, iterations, d_in + (size_t)count * 10, probes, d_in, count, d_out);
         },
         req);
 }

@@ -1,5 +1,6 @@
-// Internal declarations shared by the C-ABI layer (ocean_abi.cpp) and the HIP
-// kernel translation units (spectrum.hip, fft2/3/4k.hip, mips.hip, sample.hip, query.hip, grid.hip, body.hip, velocity.hip).  Not part of the ABI.
+// Internal declarations shared by the C-ABI layer (ocean_abi.cpp) and the HIP kernel translation
+// units (every csrc/*.hip): the launch wrapper, the device view of a context and one launch_*
+// function per kernel family.  Not part of the ABI.
 #pragma once
 
 #include <hip/hip_ext.h>

@@ -31,24 +31,10 @@ __global__ __launch_bounds__(256) void k_query_surface(DevView v, int tile, int 
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const float qx = pts[2 * (size_t)i], qz = pts[2 * (size_t)i + 1];
-    float px = qx, pz = qz;
-    for (int k = 0; k < iterations; ++k) {
-        const float4 d = sample_disp(v, tile, px, pz);
-        px = qx - d.x;
-        pz = qz - d.z;
-    }
-    const WorldSample s = sample_cascades(v, tile, px, pz, 0.0f);
-    const float r = fmaxf(fabsf((px + s.disp.x) - qx), fabsf((pz + s.disp.z) - qz));
-    const float4 nrm = normal_from_deriv(s.deriv.x, s.deriv.y, s.deriv.z, s.deriv.w);  // (0, 1, 0) without DERIV
-    out[2 * (size_t)i] = make_float4(s.disp.y, px, pz, r);
-    out[2 * (size_t)i + 1] = make_float4(nrm.x, nrm.y, nrm.z, s.turb);
-}
-
-// GetWaterHeight (WaterBody.cs:195-209): InverseLerp(-N/2, N/2, .) is saturate((v - a) / (b - a)).
-__device__ __forceinline__ int reference_texel(float w, int n) {
-    const float a = (float)(-(n / 2)), b = (float)(n / 2);
-    const float u = fminf(fmaxf((w - a) / (b - a), 0.0f), 1.0f);
-    return min(max((int)(u * (float)n), 0), n - 1);
+    const float2 p = surface_fixed_point(v, tile, qx, qz, iterations);
+    const SurfaceRecord rec = surface_record(sample_cascades(v, tile, p.x, p.y, 0.0f), p, qx, qz);
+    out[2 * (size_t)i] = rec.at;
+    out[2 * (size_t)i + 1] = rec.nf;
 }
 
 // Point i: (world x, world z) -> out[2 i] = (DISP[tile * C][py][px].y, px, py, 0), out[2 i + 1] = 0.

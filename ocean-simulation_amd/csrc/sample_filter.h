@@ -1,7 +1,9 @@
-// Texture filtering shared by the world sampler (sample.hip) and the surface queries (query.hip):
-// the bilinear / trilinear taps of ocean_sample_world as include/ocean/ocean.h states them, and the
-// cascade sums built from them.  Device code only; every function is inlined into its kernel, so
-// both kernels run the same fp32 operations in the same order (the build has -ffp-contract=off).
+// Texture filtering and the surface lookup shared by every point consumer of the finished textures (the
+// world sampler, the surface and velocity queries, the surface grids and the buoyant bodies): the bilinear /
+// trilinear taps of ocean_sample_world as include/ocean/ocean.h states them, the cascade sums built from
+// them, and on top of those the surface query's fixed point, its residual and its record.  Device code
+// only; every function is inlined into its kernel, so all kernels run the same fp32 operations in the same
+// order (the build has -ffp-contract=off) and one numpy restatement checks them all bit for bit.
 //   level texture of side m, uv = (x / L, z / L):  sx = u * m - 0.5, sy = v * m - 0.5;
 //   i = floor(s), f = s - floor(s); texel columns i mod m, i + 1 mod m (Repeat), rows alike;
 //   bilinear = lerp(lerp(t00, t10, fx), lerp(t01, t11, fx), fy), lerp(a, b, f) = a + f (b - a);
@@ -11,6 +13,7 @@
 #pragma once
 
 #include "ocean_internal.h"
+#include "spectrum_math.h"
 
 namespace ocean {
 
@@ -109,6 +112,45 @@ __device__ __forceinline__ float4 sample_disp(const DevView& v, int tile, float 
         disp = add4(disp, tap(v.disp + (size_t)slice * v.n * v.n, v.n, bil(u, w, v.n)));
     }
     return disp;
+}
+
+// The surface above a world point q (OCEAN_QUERY_SURFACE, query.hip has the derivation): `iterations` steps
+// of the fixed point p <- q - D_xz(p) from p = q.  Returns p = (px, pz).
+__device__ __forceinline__ float2 surface_fixed_point(const DevView& v, int tile, float qx, float qz, int iterations) {
+    float px = qx, pz = qz;
+    for (int k = 0; k < iterations; ++k) {
+        const float4 d = sample_disp(v, tile, px, pz);
+        px = qx - d.x;
+        pz = qz - d.z;
+    }
+    return make_float2(px, pz);
+}
+
+// r = |p + D_xz(p) - q|_inf for the displacement `disp` sampled at p: what the next step would have started from.
+__device__ __forceinline__ float surface_residual(float4 disp, float2 p, float qx, float qz) {
+    return fmaxf(fabsf((p.x + disp.x) - qx), fabsf((p.y + disp.z) - qz));
+}
+
+// The surface query's record of the full sample `s` taken at p: (height, p.x, p.z, residual), (normal, foam).
+struct SurfaceRecord {
+    float4 at, nf;
+};
+
+__device__ __forceinline__ SurfaceRecord surface_record(const WorldSample& s, float2 p, float qx, float qz) {
+    const float r = surface_residual(s.disp, p, qx, qz);
+    const float4 nrm = normal_from_deriv(s.deriv.x, s.deriv.y, s.deriv.z, s.deriv.w);  // (0, 1, 0) without DERIV
+    SurfaceRecord rec;
+    rec.at = make_float4(s.disp.y, p.x, p.y, r);
+    rec.nf = make_float4(nrm.x, nrm.y, nrm.z, s.turb);
+    return rec;
+}
+
+// GetWaterHeight's texel index (WaterBody.cs:195-209), OCEAN_QUERY_REFERENCE: InverseLerp(-N/2, N/2, .) is
+// saturate((v - a) / (b - a)).
+__device__ __forceinline__ int reference_texel(float w, int n) {
+    const float a = (float)(-(n / 2)), b = (float)(n / 2);
+    const float u = fminf(fmaxf((w - a) / (b - a), 0.0f), 1.0f);
+    return min(max((int)(u * (float)n), 0), n - 1);
 }
 
 }  // namespace ocean

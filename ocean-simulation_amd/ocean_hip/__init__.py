@@ -316,7 +316,10 @@ class OceanContext:
         """The per-frame form (ocean_query_surface_async): the query runs behind the queued steps and its
         float32[M][8] lands in pinned host memory like a read_async slice; `points` is consumed by the call.
         Poll .done() / .wait(), then .data; `buf`: a caller-owned pinned slot of at least M x 32 B."""
-        return Readback(self, TEX_DISP, tile, 0, buf, query=(self._query_points(points), mode, iterations))
+        p = self._query_points(points)
+        return Readback(self, (p.shape[0], 8), p.shape[0] * 32, "ocean_query_surface_async",
+                        lambda dst, req: self.lib.ocean_query_surface_async(self._h, tile, mode, iterations, p.ctypes.data,
+                                                                            p.shape[0], dst, req), buf)
 
     def query_velocity(self, points, tile: int = 0, iterations: int = 4) -> np.ndarray:
         """Surface velocity on the device (ocean.h ocean_query_velocity; F_VELOCITY contexts), blocking: points
@@ -332,7 +335,10 @@ class OceanContext:
     def query_velocity_async(self, points, tile: int = 0, iterations: int = 4, buf: "PinnedBuffer" = None) -> "Readback":
         """The per-frame form (ocean_query_velocity_async), as query_surface_async: the query runs behind the
         queued steps and its float32[M][8] lands in pinned host memory; `points` is consumed by the call."""
-        return Readback(self, TEX_DISP, tile, 0, buf, velocity=(self._query_points(points), iterations))
+        p = self._query_points(points)
+        return Readback(self, (p.shape[0], 8), p.shape[0] * 32, "ocean_query_velocity_async",
+                        lambda dst, req: self.lib.ocean_query_velocity_async(self._h, tile, iterations, p.ctypes.data,
+                                                                             p.shape[0], dst, req), buf)
 
     def query_velocity_device(self, points_ptr: int, count: int, out_ptr: int, tile: int = 0, iterations: int = 4) -> None:
         """The device-pointer form (ocean_query_velocity_device): points float[count][2] and out float[count][8]
@@ -386,8 +392,9 @@ class OceanContext:
         lands in pinned host memory like a read_async slice.  Poll .done() / .wait(), then .data; `buf`: a
         caller-owned pinned slot of at least the result's size."""
         iterations, shape, nbytes = self._grid_args(mode, iterations, nx, ny)
-        return Readback(self, TEX_DISP, tile, 0, buf,
-                        grid=(mode, iterations, lod, x0, z0, dx, dz, nx, ny, shape, nbytes))
+        return Readback(self, shape, nbytes, "ocean_surface_grid_async",
+                        lambda dst, req: self.lib.ocean_surface_grid_async(self._h, tile, mode, iterations, lod, x0, z0, dx,
+                                                                           dz, nx, ny, dst, nbytes, req), buf)
 
     @staticmethod
     def _body_args(hull, bodies):
@@ -417,7 +424,10 @@ class OceanContext:
         float32[M][8] lands in pinned host memory like a read_async slice; `hull` and `bodies` are consumed by
         the call.  Poll .done() / .wait(), then .data; `buf`: a caller-owned pinned slot of at least M x 32 B."""
         h, b = self._body_args(hull, bodies)
-        return Readback(self, TEX_DISP, tile, 0, buf, body=(h, b, mode, iterations))
+        return Readback(self, (b.shape[0], 8), b.shape[0] * 32, "ocean_body_buoyancy_async",
+                        lambda dst, req: self.lib.ocean_body_buoyancy_async(self._h, tile, mode, iterations, h.ctypes.data,
+                                                                            h.shape[0], b.ctypes.data, b.shape[0], dst,
+                                                                            req), buf)
 
     def body_buoyancy_device(self, hull_ptr: int, probes: int, bodies_ptr: int, count: int, out_ptr: int,
                              iterations: int = 4, mode: int = QUERY_SURFACE, tile: int = 0) -> None:
@@ -467,12 +477,17 @@ class OceanContext:
         """AsyncGPUReadback.Request (WaterBody.cs:288-296): copy one slice into pinned
         host memory once the queued steps finish; poll .done() / .wait(), then .data.
         `buf`: a caller-owned pinned slot to land in (else the request allocates its own)."""
-        return Readback(self, tex, tile, cascade, buf)
+        ch = _TEX_CHANNELS[tex]
+        nbytes = self.n * self.n * ch * 4
+        return Readback(self, (self.n, self.n, ch), nbytes, "ocean_read_async",
+                        lambda dst, req: self.lib.ocean_read_async(self._h, tex, tile, cascade, dst, nbytes, req), buf)
 
     def read_height_async(self, tile: int = 0, cascade: int = 0, buf: "PinnedBuffer" = None) -> "Readback":
         """The height-only readback (ocean_read_height_async): DISP.y of one slice as float32[N][N], a
         quarter of read_async(TEX_DISP)'s bytes -- all GetWaterHeight reads (WaterBody.cs:195-209)."""
-        return Readback(self, TEX_DISP, tile, cascade, buf, height=True)
+        nbytes = self.n * self.n * 4
+        return Readback(self, (self.n, self.n), nbytes, "ocean_read_height_async",
+                        lambda dst, req: self.lib.ocean_read_height_async(self._h, tile, cascade, dst, nbytes, req), buf)
 
     def set_readback_timing(self, enable: bool) -> None:
         """Time each new readback's device-to-host copy (Readback.copy_ms); off after create."""
@@ -547,32 +562,15 @@ class PinnedBuffer:
 
 
 class Readback:
-    """One ocean_read_async (or, `height`, ocean_read_height_async; or, `query` = (points float32[M][2],
-    mode, iterations), ocean_query_surface_async; or, `grid` = (mode, iterations, lod, x0, z0, dx, dz, nx, ny,
-    shape, bytes), ocean_surface_grid_async; or, `body` = (hull float32[P][5], bodies float32[M][10], mode,
-    iterations), ocean_body_buoyancy_async; or, `velocity` = (points float32[M][2], iterations),
-    ocean_query_velocity_async) request into pinned host memory: a caller's PinnedBuffer
-    slot, or one of its own (freed by release())."""
+    """One readback request (any ocean_*_async entry) into pinned host memory: a caller's PinnedBuffer slot, or
+    one of its own (freed by release()).  The OceanContext method that makes it knows the result's `shape` and
+    `nbytes` and passes `call(dst, req)`, which issues its entry (named `where` in errors) with the pinned
+    destination and the request handle's address and returns the entry's code."""
 
-    def __init__(self, ctx: "OceanContext", tex: int, tile: int, cascade: int, buf: Optional[PinnedBuffer] = None,
-                 height: bool = False, query: Optional[tuple] = None, grid: Optional[tuple] = None,
-                 body: Optional[tuple] = None, velocity: Optional[tuple] = None):
+    def __init__(self, ctx: "OceanContext", shape: tuple, nbytes: int, where: str, call,
+                 buf: Optional[PinnedBuffer] = None):
         self.lib = ctx.lib
-        if velocity is not None:
-            self.shape = (velocity[0].shape[0], 8)
-            self.nbytes = velocity[0].shape[0] * 32
-        elif body is not None:
-            self.shape = (body[1].shape[0], 8)
-            self.nbytes = body[1].shape[0] * 32
-        elif grid is not None:
-            self.shape, self.nbytes = grid[9], grid[10]
-        elif query is not None:
-            self.shape = (query[0].shape[0], 8)
-            self.nbytes = query[0].shape[0] * 32
-        else:
-            ch = 1 if height else _TEX_CHANNELS[tex]
-            self.shape = (ctx.n, ctx.n) if height else (ctx.n, ctx.n, ch)
-            self.nbytes = ctx.n * ctx.n * ch * 4
+        self.shape, self.nbytes = shape, nbytes
         self._h = ctypes.c_void_p()
         self.slot = buf
         self._own = buf is None
@@ -583,32 +581,7 @@ class Readback:
             raise ValueError(f"pinned slot of {buf.nbytes} B < request {self.nbytes} B")
         self._pinned = buf
         self._buf = buf.ptr
-        if velocity is not None:
-            where = "ocean_query_velocity_async"
-            pts, iterations = velocity
-            rc = self.lib.ocean_query_velocity_async(ctx._h, tile, iterations, pts.ctypes.data, pts.shape[0], self._buf,
-                                                     ctypes.byref(self._h))
-        elif body is not None:
-            where = "ocean_body_buoyancy_async"
-            hull, bodies, mode, iterations = body
-            rc = self.lib.ocean_body_buoyancy_async(ctx._h, tile, mode, iterations, hull.ctypes.data, hull.shape[0],
-                                                    bodies.ctypes.data, bodies.shape[0], self._buf,
-                                                    ctypes.byref(self._h))
-        elif grid is not None:
-            where = "ocean_surface_grid_async"
-            rc = self.lib.ocean_surface_grid_async(ctx._h, tile, *grid[:9], self._buf, self.nbytes,
-                                                   ctypes.byref(self._h))
-        elif query is not None:
-            where = "ocean_query_surface_async"
-            pts, mode, iterations = query
-            rc = self.lib.ocean_query_surface_async(ctx._h, tile, mode, iterations, pts.ctypes.data, pts.shape[0],
-                                                    self._buf, ctypes.byref(self._h))
-        elif height:
-            where = "ocean_read_height_async"
-            rc = self.lib.ocean_read_height_async(ctx._h, tile, cascade, self._buf, self.nbytes, ctypes.byref(self._h))
-        else:
-            where = "ocean_read_async"
-            rc = self.lib.ocean_read_async(ctx._h, tex, tile, cascade, self._buf, self.nbytes, ctypes.byref(self._h))
+        rc = call(self._buf, ctypes.byref(self._h))
         if rc != OK:
             if self._own:
                 buf.release()

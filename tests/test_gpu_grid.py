@@ -11,23 +11,13 @@ import pytest
 
 import ocean_hip as oh
 import oracle as O
+from test_gpu_query import make_ctx
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("require_gpu")]
 
 f32 = np.float32
 KS = (0, 1, 4, 16)
 LODS = (0.0, 0.5, 2.25, 99.0)
-
-
-def make_ctx(n, cas, flags=0, noise=None, times=(0.5, 1.0), tiles=1):
-    ctx = oh.OceanContext(n, len(cas), tiles, flags)
-    ctx.set_params(O.scene_params(), cas)
-    for t in range(tiles):
-        ctx.set_noise(t, O.generate_noise(n, 20251121 + t) if noise is None else noise)
-    ctx.init_spectrum()
-    for t in times:
-        ctx.step(t)
-    return ctx
 
 
 def grids(n, cas):
