@@ -69,7 +69,9 @@ extern "C" {
  *      Added later within version 4 in the same way: ocean_body_buoyancy, ocean_body_buoyancy_device,
  *      ocean_body_buoyancy_async.
  *      Added later within version 4 in the same way: OCEAN_F_VELOCITY, OCEAN_TEX_VELOCITY, ocean_query_velocity,
- *      ocean_query_velocity_device, ocean_query_velocity_async. */
+ *      ocean_query_velocity_device, ocean_query_velocity_async.
+ *      Added later within version 4 in the same way: ocean_surface_bounds, ocean_surface_bounds_device,
+ *      ocean_raycast, ocean_raycast_device, ocean_raycast_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -548,9 +550,105 @@ int ocean_query_velocity_device(ocean_ctx *ctx, int tile, int iterations, const 
 int ocean_query_velocity_async(ocean_ctx *ctx, int tile, int iterations, const float *points, int count,
                                float *dst, ocean_readback **req);
 
+/* Surface bounds: how far the water of a tile can be from rest, per cascade.  A renderer needs them for
+ * the bounding box of its displaced mesh (frustum culling, tessellation range; the reference leaves its
+ * mesh bounds to Unity's defaults), and ocean_raycast below skips the air above them.
+ *
+ * `bytes` must equal C * 32.  Record c of `out` is float[8] = (min x, min y, min z, min w, max x, max y,
+ * max z, max w) over the N * N texels of DISP slice tile * C + c, channel by channel (x = Dx, y = Dy, z = Dz,
+ * w as the frame wrote it).  Min and max do not depend on the order of a reduction, so the numbers are
+ * exact: those of a host that reads the slice back and takes the min and max itself (-0 and +0 compare
+ * equal, and either may be returned).  NaN texels give unspecified numbers.  On a column-band context the
+ * columns the context does not write (zero after ocean_create) take part like any other.
+ * What a host forms from the records: sum_c min_c <= D(p) <= sum_c max_c, channel by channel and up to
+ * rounding (a few ulp of sum_c max(|min_c|, |max_c|)), for the cascade-summed displacement D(p) that
+ * ocean_sample_world returns at any point p, a bilinear tap lying between the texels it blends.  The
+ * displaced mesh of a patch [x0, x1] x [z0, z1] therefore lies inside [x0 + sum min x, x1 + sum max x] x
+ * [sum min y, sum max y] x [z0 + sum min z, z1 + sum max z].
+ *
+ * Cache.  The context keeps the records of a tile until an entry of this library writes DISP: ocean_step,
+ * ocean_fill, ocean_write of OCEAN_TEX_DISP, ocean_set_column_band and ocean_set_column_parity drop them,
+ * and the next use runs the two reduction kernels again (kind 2 of ocean_kernel_stats / ocean_kernel_name).
+ * Once ocean_get_device_ptr(OCEAN_TEX_DISP) has handed the pointer out, the context caches nothing any more
+ * and recomputes at every use, for the life of the context: a foreign writer cannot be seen.
+ *
+ * ocean_surface_bounds: `out` is a host buffer; blocks.  ocean_surface_bounds_device: `out` is a device
+ * pointer, 16-B aligned (else OCEAN_E_INVALID_ARG); async on the ctx stream, ordered after the queued steps.
+ * Both: OCEAN_E_INVALID_ARG, checked before any device call, for a null ctx or `out`, a tile out of range
+ * or a wrong `bytes`; then OCEAN_E_STATE before ocean_init_spectrum and OCEAN_E_UNSUPPORTED on a
+ * column-parity context (as the queries). */
+int ocean_surface_bounds(ocean_ctx *ctx, int tile, float *out, size_t bytes);
+int ocean_surface_bounds_device(ocean_ctx *ctx, int tile, float *out, size_t bytes);
+
+/* Ray casts: where a ray meets the water.  Every entry above starts from a known world (x, z); projectile
+ * and spray impacts, mouse picking, camera and line-of-sight checks and range sensors start from a ray (the
+ * water's analogue of Unity's Physics.Raycast; the reference has none).  Ray i of `rays` is float[8] =
+ * (ox, oy, oz, dx, dy, dz, t0, t1): an origin, a direction and the parameter interval to search; out[i] is
+ * float[8].  The library does not inspect the values: a non-unit direction scales t, and t1 < t0 marches
+ * backwards.
+ *
+ * All arithmetic is fp32, one rounding per operation in the order written (no fused multiply-add).  With
+ * K = `iterations` in [0, 16], S = `steps` in [1, OCEAN_RAY_MAX_STEPS], B = `refine` in [0, 32] and rec(x, z)
+ * the 8-float record of OCEAN_QUERY_SURFACE for the point (x, z) of tile `tile` with K iterations, bit for bit:
+ *
+ *       pos(t) = (ox + t * dx,  oy + t * dy,  oz + t * dz)
+ *       f(t)   = pos(t).y - rec(pos(t).x, pos(t).z)[0]            (height of the ray point over the water)
+ *       dt     = (t1 - t0) / (float)S
+ *       t_j    = t0 + (float)j * dt,   j = 0 .. S
+ *
+ *       if !(f(t_0) > 0):                     status = OCEAN_RAY_SUBMERGED, t* = t_0
+ *       else for the first j in 1 .. S with !(f(t_j) > 0):
+ *              a = t_(j-1), b = t_j;  B times:  m = 0.5f * (a + b);  if f(m) > 0: a = m  else: b = m
+ *                                             status = OCEAN_RAY_HIT, t* = b
+ *       else:                                 status = OCEAN_RAY_MISS, t* = t_S
+ *
+ *       R = rec(pos(t*).x, pos(t*).z)
+ *       out[8i + 0..3] = t*,  pos(t*).y - R[0],  R[3],  (float)status
+ *       out[8i + 4..7] = R[4..7]                                  (normal and foam at the point met)
+ *
+ * After a hit f(t*) <= 0 < f(a) and b - a = dt / 2^B up to rounding; the host forms the point met as
+ * o + t* d.  out[8i + 1] is the ray point's height over the water there (<= 0 after a hit, the clearance at
+ * t_S after a miss) and out[8i + 2] the fixed point's residual, as in the queries.
+ * Limits of the method.  The march sees the surface only at its S + 1 nodes: a crest thinner than dt along
+ * the ray can be stepped over, and S is the caller's resolution.  K has the meaning and the convergence
+ * caveats of ocean_query_surface.  Non-finite inputs give unspecified numbers, never an access outside the
+ * textures.
+ * Air skip.  A node higher than every wave has f > 0 without a sample, and only the sign of f is used at a
+ * node.  The kernel takes the height no wave reaches from ocean_surface_bounds' records of the tile (the sum
+ * of the cascades' max y plus a derived rounding margin) and samples only the nodes at or below it; every
+ * result bit is as defined above, only the time differs.  A ray cast on a context whose bounds are stale
+ * (see their cache rule) first enqueues the two bounds kernels on the ctx stream.  OCEAN_RAY_BOUNDS=0 in the
+ * environment (read by ocean_create) turns the skip and those launches off.
+ *
+ * The three forms, their ordering and `*req` are those of ocean_query_surface, ocean_query_surface_device and
+ * ocean_query_surface_async: ocean_raycast takes host buffers and blocks; ocean_raycast_device takes device
+ * pointers (rays 4-B aligned, out 16-B aligned, else OCEAN_E_INVALID_ARG) and is async on the ctx stream,
+ * ordered after the queued steps; ocean_raycast_async consumes the host buffer `rays` before it returns, runs
+ * on the ctx stream after the steps queued so far and before later ones, and lands count x 32 B in `dst` on
+ * the copy stream through the same readback slots, with the same ocean_readback_status / _wait / _release /
+ * _copy_ms.  *req is NULL after every failure.
+ * All three: OCEAN_E_INVALID_ARG, checked before any device call, for a null ctx, rays, out or req, count < 0,
+ * count > OCEAN_RAY_MAX_RAYS (host and async forms, which stage the rays), steps outside
+ * [1, OCEAN_RAY_MAX_STEPS], count * steps > OCEAN_RAY_MAX_SAMPLES (in 64 bits, all forms), iterations outside
+ * [0, 16], refine outside [0, 32] or a tile out of range; then OCEAN_E_STATE before ocean_init_spectrum and
+ * OCEAN_E_UNSUPPORTED on a column-parity context (as the queries).  count = 0 is a no-op in the blocking and
+ * device forms and OCEAN_E_INVALID_ARG in the async form (there is no request to hand back). */
+#define OCEAN_RAY_MISS 0
+#define OCEAN_RAY_HIT 1
+#define OCEAN_RAY_SUBMERGED 2
+#define OCEAN_RAY_MAX_RAYS 16384
+#define OCEAN_RAY_MAX_STEPS 1024
+#define OCEAN_RAY_MAX_SAMPLES (1 << 24)
+int ocean_raycast(ocean_ctx *ctx, int tile, int iterations, int steps, int refine, const float *rays, int count,
+                  float *out);
+int ocean_raycast_device(ocean_ctx *ctx, int tile, int iterations, int steps, int refine, const float *rays,
+                         int count, float *out);
+int ocean_raycast_async(ocean_ctx *ctx, int tile, int iterations, int steps, int refine, const float *rays,
+                        int count, float *dst, ocean_readback **req);
+
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
  * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async /
- * ocean_body_buoyancy_async / ocean_query_velocity_async request records HIP timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it
+ * ocean_body_buoyancy_async / ocean_query_velocity_async / ocean_raycast_async request records HIP timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it
  * is off record only untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 

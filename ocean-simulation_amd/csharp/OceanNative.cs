@@ -144,6 +144,22 @@ namespace OceanHip
         public static extern OceanStatus ocean_query_velocity_device(IntPtr ctx, int tile, int iterations, IntPtr points, int count, IntPtr output);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_query_velocity_async(IntPtr ctx, int tile, int iterations, [In] float[] points, int count, IntPtr dst, out IntPtr request);
+        // Surface bounds (added within ABI 4 in the same way).  8 floats per cascade: min x, y, z, w, max x, y, z, w of
+        // the displacement slice; bytes = cascades * 32.
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_surface_bounds(IntPtr ctx, int tile, [Out] float[] output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_surface_bounds_device(IntPtr ctx, int tile, IntPtr output, UIntPtr bytes);
+        // Ray casts (added within ABI 4 in the same way).  8 floats per ray in (origin, direction, t0, t1) and out
+        // (t*, height over the water, residual, status, normal x, y, z, foam).
+        public const int RayMiss = 0, RayHit = 1, RaySubmerged = 2;
+        public const int RayMaxRays = 16384, RayMaxSteps = 1024, RayMaxSamples = 1 << 24;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_raycast(IntPtr ctx, int tile, int iterations, int steps, int refine, [In] float[] rays, int count, [Out] float[] output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_raycast_device(IntPtr ctx, int tile, int iterations, int steps, int refine, IntPtr rays, int count, IntPtr output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_raycast_async(IntPtr ctx, int tile, int iterations, int steps, int refine, [In] float[] rays, int count, IntPtr dst, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_read_async(IntPtr ctx, OceanTexture tex, int tile, int cascade, IntPtr dst, UIntPtr bytes, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

@@ -227,6 +227,30 @@ namespace OceanHip
             return new[] { output[0], output[1], output[2] };
         }
 
+        // Physics.Raycast for the water (ocean.h ocean_raycast): the ray from `origin` along `direction` (the caller
+        // keeps it unit) searched over [0, maxDistance] in `steps` intervals, then `refine` bisections.  False when
+        // the ray stays above the water; else hit = 8 floats: distance, the ray point's height over the water there,
+        // residual, status (OceanNative.RayHit, or RaySubmerged when the origin is under water), normal x, y, z,
+        // foam.  The point met is origin + hit[0] * direction.  The reference has no counterpart.
+        public bool Raycast(float[] origin, float[] direction, float maxDistance, out float[] hit, int iterations = 4,
+                            int steps = 64, int refine = 8)
+        {
+            var ray = new[] { origin[0], origin[1], origin[2], direction[0], direction[1], direction[2], 0f, maxDistance };
+            hit = new float[8];
+            OceanNative.Check(OceanNative.ocean_raycast(ctx, 0, iterations, steps, refine, ray, 1, hit), "ocean_raycast");
+            return (int)hit[3] != OceanNative.RayMiss;
+        }
+
+        // The per-cascade bounds of the displacement (ocean.h ocean_surface_bounds): 8 floats per cascade, (min x, y,
+        // z, w, max x, y, z, w); their cascade sums bound the displaced mesh (culling, tessellation range).
+        public float[] SurfaceBounds()
+        {
+            var output = new float[cascades.Length * 8];
+            OceanNative.Check(OceanNative.ocean_surface_bounds(ctx, 0, output, (UIntPtr)(ulong)(output.Length * 4)),
+                              "ocean_surface_bounds");
+            return output;
+        }
+
         // Texture-out contract: device pointers for same-process renderers (WaterBody.cs:277-281).
         public IntPtr DeviceTexture(OceanTexture tex, out ulong bytes)
         {

@@ -191,6 +191,7 @@ struct ocean_options {
     int grid_tile = 0;      // OCEAN_GRID_TILE: nodes along x of the grid kernel's workgroup tile, 64 / 32 / 16 (0: kept)
     int vel_nt = 0;         // OCEAN_VEL_NT=1: the velocity pack kernel writes VEL with nontemporal stores
     int prune = 1;          // OCEAN_PRUNE=0: passes AQ / BQ run every row of a band-limited cascade (dense schedule)
+    int ray_bounds = 1;     // OCEAN_RAY_BOUNDS=0: the ray kernel samples every node (no air skip, no bounds launches)
 
     static ocean_options from_env() {
         ocean_options o;
@@ -204,6 +205,7 @@ struct ocean_options {
         if (const char* e = std::getenv("OCEAN_GRID_TILE")) o.grid_tile = std::atoi(e);
         if (const char* e = std::getenv("OCEAN_VEL_NT")) o.vel_nt = std::atoi(e) != 0;
         if (const char* e = std::getenv("OCEAN_PRUNE")) o.prune = std::atoi(e);
+        if (const char* e = std::getenv("OCEAN_RAY_BOUNDS")) o.ray_bounds = std::atoi(e);
         return o;
     }
 };
@@ -244,6 +246,13 @@ struct ocean_ctx {
     int* prune_dev = nullptr;
     ocean::PruneItems prune;
     bool prune_ready = false;
+    // surface bounds (bounds.hip), allocated by the first entry that needs them: the records float[T][C][8],
+    // then pass 1's partials.  bounds_valid[t]: tile t's records match DISP (dropped by every entry that writes
+    // DISP).  disp_exposed: ocean_get_device_ptr has handed DISP out, a foreign writer cannot be seen, so
+    // nothing is cached any more and every use recomputes.
+    float* bounds_dev = nullptr;
+    std::vector<bool> bounds_valid;
+    bool disp_exposed = false;
     float4* deriv_mips = nullptr;  // OCEAN_F_MIPS chains (levels 1..log2 N per slice)
     float4* turb_mips = nullptr;
     size_t mip_chain = 0;
@@ -405,6 +414,9 @@ int timed(ocean_ctx* ctx, int kind, F&& launch, const char* what) {
     return OCEAN_OK;
 }
 
+// Every entry that writes DISP drops the cached surface bounds (ocean.h ocean_surface_bounds).
+void drop_bounds(ocean_ctx* ctx) { ctx->bounds_valid.assign(ctx->bounds_valid.size(), false); }
+
 void* tex_ptr(ocean_ctx* ctx, int tex, size_t* elem_bytes, size_t* slices) {
     *slices = ctx->units();
     switch (tex) {
@@ -444,7 +456,7 @@ int slice_ptr(ocean_ctx* ctx, int tex, int tile, int cascade, size_t bytes, char
 void free_all(ocean_ctx* c) {
     void* ptrs[] = {c->noise, c->h0, c->h0k, c->waves, c->plane[0], c->disp, c->deriv,
                     c->turb,  c->normal, c->tw,    c->casc,     c->tplane, c->foam, c->deriv_mips, c->turb_mips,
-                    c->qside, c->vel, c->vplane, c->prune_dev};
+                    c->qside, c->vel, c->vplane, c->prune_dev, c->bounds_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (auto& t : c->pending) {
@@ -503,6 +515,7 @@ int ocean_create(int device, int n, int n_cascades, int n_tiles, uint32_t flags,
     c->flags = flags;
     c->P = (flags & OCEAN_F_DISPLACEMENT_ONLY) ? 2 : 4;
     c->noise_set.assign(n_tiles, false);
+    c->bounds_valid.assign(n_tiles, false);
     c->band_nx = n;
     c->opt = ocean_options::from_env();
     // Width of the fused path's column tiles.  With fewer tiles than CUs (one 512^2
@@ -798,6 +811,7 @@ int ocean_ifft2d(ocean_ctx* ctx, int plane_mask) {
 
 int ocean_fill(ocean_ctx* ctx) {
     OCEAN_ENTER(ctx);
+    drop_bounds(ctx);
     const ocean::DevView v = ctx->view();
     return timed(ctx, 2, [&] { return ocean::launch_fill(v, ctx->stream); }, "fill");
 }
@@ -832,6 +846,7 @@ int step_velocity(ocean_ctx* ctx, float time) {
 int ocean_step(ocean_ctx* ctx, float time) {
     OCEAN_ENTER(ctx);
     if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, "ocean_init_spectrum must precede ocean_step");
+    drop_bounds(ctx);
     if (ctx->flags & OCEAN_F_UNFUSED) {
         if (int r = ocean_evolve(ctx, time)) return r;
         if (int r = ocean_ifft2d(ctx, (1 << ctx->P) - 1)) return r;
@@ -1297,6 +1312,7 @@ int ocean_write(ocean_ctx* ctx, int texture, int tile, int cascade, const void* 
     OCEAN_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     OCEAN_HIP(hipStreamSynchronize(ctx->stream));
     if (texture == OCEAN_TEX_NOISE) ctx->noise_set[tile] = true;
+    if (texture == OCEAN_TEX_DISP) drop_bounds(ctx);
     if (texture == OCEAN_TEX_H0) {  // the v3 row pass reads h0 (.zw included); the three-plane frame
         ctx->h0k_valid = false;     // needs .zw = conj h0(-k), which an upload need not keep
         ctx->h0_conj = false;
@@ -1315,6 +1331,7 @@ int ocean_get_device_ptr(ocean_ctx* ctx, int texture, void** ptr, size_t* bytes)
     size_t eb = 0, slices = 0;
     void* base = tex_ptr(ctx, texture, &eb, &slices);
     if (!base) return fail(OCEAN_E_INVALID_ARG, "texture not allocated for this context's flags");
+    if (texture == OCEAN_TEX_DISP) ctx->disp_exposed = true;  // a foreign writer: the surface bounds are not cached
     *ptr = base;
     *bytes = ctx->texels() * eb * slices;
     return OCEAN_OK;
@@ -1656,6 +1673,151 @@ int ocean_body_buoyancy_async(ocean_ctx* ctx, int tile, int mode, int iterations
         req);
 }
 
+// Surface bounds and ray casts (ocean.h).
+
+// Tile `tile`'s bounds records on the device, float[C][8], current on the ctx stream once this returns: the
+// two bounds launches (kind 2 of ocean_kernel_stats) are enqueued unless the cached records still match DISP.
+// (the caller has entered: OCEAN_ENTER)
+static int ensure_bounds(ocean_ctx* ctx, int tile, const float** records) {
+    const size_t rec_floats = ctx->units() * 8;
+    if (!ctx->bounds_dev)
+        OCEAN_HIP(hipMalloc((void**)&ctx->bounds_dev, (rec_floats + ocean::bounds_partial_floats(ctx->C)) * sizeof(float)));
+    float* rec = ctx->bounds_dev + (size_t)tile * ctx->C * 8;
+    *records = rec;
+    if (ctx->bounds_valid[tile] && !ctx->disp_exposed) return OCEAN_OK;
+    const ocean::DevView v = ctx->view();
+    if (int r = timed(ctx, 2,
+                      [&] { return ocean::launch_surface_bounds(v, tile, ctx->bounds_dev + rec_floats, rec, ctx->stream); },
+                      "surface_bounds"))
+        return r;
+    ctx->bounds_valid[tile] = !ctx->disp_exposed;
+    return OCEAN_OK;
+}
+
+static int check_bounds(ocean_ctx* ctx, int tile, const float* out, size_t bytes) {
+    if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+    if (!out) return fail(OCEAN_E_INVALID_ARG, "null output");
+    if (tile < 0 || tile >= ctx->T) return fail(OCEAN_E_INVALID_ARG, "tile out of range");
+    if (bytes != (size_t)ctx->C * 32)
+        return fail(OCEAN_E_INVALID_ARG, "byte count " + std::to_string(bytes) + " != cascades * 32 = " +
+                                             std::to_string((size_t)ctx->C * 32));
+    return OCEAN_OK;
+}
+
+static int check_bounds_state(const ocean_ctx* ctx) {
+    if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, "ocean_init_spectrum must precede ocean_surface_bounds");
+    if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, "surface bounds of a column-parity shard (half the columns)");
+    return OCEAN_OK;
+}
+
+int ocean_surface_bounds_device(ocean_ctx* ctx, int tile, float* out, size_t bytes) {
+    if (int r = check_bounds(ctx, tile, out, bytes)) return r;
+    if (int r = check_aligned("ocean_surface_bounds_device", nullptr, {}, out)) return r;
+    if (int r = check_bounds_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    const float* rec = nullptr;
+    if (int r = ensure_bounds(ctx, tile, &rec)) return r;
+    OCEAN_HIP(hipMemcpyAsync(out, rec, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return OCEAN_OK;
+}
+
+int ocean_surface_bounds(ocean_ctx* ctx, int tile, float* out, size_t bytes) {
+    if (int r = check_bounds(ctx, tile, out, bytes)) return r;
+    if (int r = check_bounds_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    const float* rec = nullptr;
+    if (int r = ensure_bounds(ctx, tile, &rec)) return r;
+    OCEAN_HIP(hipMemcpyAsync(out, rec, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    OCEAN_HIP(hipStreamSynchronize(ctx->stream));
+    return OCEAN_OK;
+}
+
+// Argument checks of the ray casts, before any device call (ocean.h); `limit`: the forms that stage the
+// rays (host and async) take at most OCEAN_RAY_MAX_RAYS.
+static int check_ray(ocean_ctx* ctx, int tile, int iterations, int steps, int refine, const float* rays, int count,
+                     const float* out, bool limit) {
+    if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+    if (!rays || !out) return fail(OCEAN_E_INVALID_ARG, "null rays or output");
+    if (count < 0) return fail(OCEAN_E_INVALID_ARG, "negative ray count");
+    if (limit && count > OCEAN_RAY_MAX_RAYS)
+        return fail(OCEAN_E_INVALID_ARG, "ray count " + std::to_string(count) + " > OCEAN_RAY_MAX_RAYS");
+    if (steps < 1 || steps > OCEAN_RAY_MAX_STEPS)
+        return fail(OCEAN_E_INVALID_ARG, "steps = " + std::to_string(steps) + " outside [1, OCEAN_RAY_MAX_STEPS]");
+    const uint64_t samples = (uint64_t)count * (uint64_t)steps;
+    if (samples > (uint64_t)OCEAN_RAY_MAX_SAMPLES)
+        return fail(OCEAN_E_INVALID_ARG, "count * steps = " + std::to_string(samples) + " > OCEAN_RAY_MAX_SAMPLES");
+    if (iterations < 0 || iterations > 16) return fail(OCEAN_E_INVALID_ARG, "iterations must be in [0, 16]");
+    if (refine < 0 || refine > 32) return fail(OCEAN_E_INVALID_ARG, "refine must be in [0, 32]");
+    if (tile < 0 || tile >= ctx->T) return fail(OCEAN_E_INVALID_ARG, "tile out of range");
+    return OCEAN_OK;
+}
+
+// ... and of the context's state, as the queries.
+static int check_ray_state(const ocean_ctx* ctx) {
+    if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, "ocean_init_spectrum must precede ocean_raycast");
+    if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, "ray cast on a column-parity shard (half the columns)");
+    return OCEAN_OK;
+}
+
+// The ray kernel on the ctx stream (device pointers; kind 2 of ocean_kernel_stats), behind the bounds
+// launches where the air skip is on and the tile's bounds are stale.
+static int launch_ray(ocean_ctx* ctx, int tile, int iterations, int steps, int refine, const float* d_rays, int count,
+                      float* d_out) {
+    const float* bounds = nullptr;
+    if (ctx->opt.ray_bounds)
+        if (int r = ensure_bounds(ctx, tile, &bounds)) return r;
+    const ocean::DevView v = ctx->view();
+    return timed(ctx, 2,
+                 [&] {
+                     return ocean::launch_raycast(v, tile, iterations, steps, refine, bounds, d_rays, count, d_out,
+                                                  ctx->stream);
+                 },
+                 "raycast");
+}
+
+// The staged rays and their records, 32 B each way, fill a slot's two regions exactly.
+static_assert((size_t)OCEAN_RAY_MAX_RAYS * 8 * sizeof(float) <= kQuerySlotBytes - kQueryPointsOffset,
+              "a slot's pinned input copy holds every ray request");
+static_assert((size_t)OCEAN_RAY_MAX_RAYS * 8 * sizeof(float) <= kQueryPointsOffset, "the records end before the inputs");
+
+int ocean_raycast_device(ocean_ctx* ctx, int tile, int iterations, int steps, int refine, const float* rays, int count,
+                         float* out) {
+    if (int r = check_ray(ctx, tile, iterations, steps, refine, rays, count, out, false)) return r;
+    if (int r = check_aligned("ocean_raycast_device", "rays", {rays}, out)) return r;
+    if (int r = check_ray_state(ctx)) return r;
+    if (count == 0) return OCEAN_OK;
+    OCEAN_ENTER(ctx);
+    return launch_ray(ctx, tile, iterations, steps, refine, rays, count, out);
+}
+
+int ocean_raycast(ocean_ctx* ctx, int tile, int iterations, int steps, int refine, const float* rays, int count,
+                  float* out) {
+    if (int r = check_ray(ctx, tile, iterations, steps, refine, rays, count, out, true)) return r;
+    if (int r = check_ray_state(ctx)) return r;
+    if (count == 0) return OCEAN_OK;
+    OCEAN_ENTER(ctx);
+    return run_staged(ctx, "ocean_raycast", {{rays, (size_t)count * 8 * 4}}, out, (size_t)count * 8 * 4,
+                      [&](const float* d_rays, float* d_out) {
+                          return launch_ray(ctx, tile, iterations, steps, refine, d_rays, count, d_out);
+                      });
+}
+
+int ocean_raycast_async(ocean_ctx* ctx, int tile, int iterations, int steps, int refine, const float* rays, int count,
+                        float* dst, ocean_readback** req) {
+    if (!req) return fail(OCEAN_E_INVALID_ARG, "req is null");
+    *req = nullptr;
+    if (int r = check_ray(ctx, tile, iterations, steps, refine, rays, count, dst, true)) return r;
+    if (count == 0) return fail(OCEAN_E_INVALID_ARG, "ocean_raycast_async: no rays, so no request");
+    if (int r = check_ray_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    return start_staged_readback(
+        ctx, {{rays, (size_t)count * 8 * 4}}, dst, (size_t)count * 8 * 4,
+        [&](const float* d_rays, float* d_out) {
+            return launch_ray(ctx, tile, iterations, steps, refine, d_rays, count, d_out);
+        },
+        req);
+}
+
 int ocean_set_column_band(ocean_ctx* ctx, int x_begin, int x_count) {
     OCEAN_ENTER(ctx);
     const int n = ctx->n;
@@ -1668,6 +1830,7 @@ int ocean_set_column_band(ocean_ctx* ctx, int x_begin, int x_count) {
                                              std::to_string(g));
     if (x_count != n && (ctx->flags & (OCEAN_F_UNFUSED | OCEAN_F_MIPS)))
         return fail(OCEAN_E_UNSUPPORTED, "a column band needs the fused schedule and no mip chains");
+    drop_bounds(ctx);
     ctx->band_x0 = x_begin;
     ctx->band_nx = x_count;
     ctx->col_par = -1;  // a band replaces a column parity
@@ -1679,6 +1842,7 @@ int ocean_set_column_parity(ocean_ctx* ctx, int parity) {
     if ((ctx->flags & OCEAN_F_VELOCITY) && parity != -1)
         return fail(OCEAN_E_UNSUPPORTED, "a velocity context (OCEAN_F_VELOCITY) takes no column parity");
     if (parity < -1 || parity > 1) return fail(OCEAN_E_INVALID_ARG, "parity must be -1 (off), 0 or 1");
+    drop_bounds(ctx);
     if (parity < 0) {
         ctx->col_par = -1;
         ctx->band_x0 = 0;

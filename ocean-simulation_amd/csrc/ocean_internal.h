@@ -156,6 +156,17 @@ hipError_t launch_pack_velocity(const DevView& v, const float2* scratch, float4*
 hipError_t launch_query_velocity(const DevView& v, const float4* vel, int tile, int iterations, const float* pts,
                                  int count, float* out, hipStream_t s);
 
+// bounds.hip: surface bounds (ocean_surface_bounds*), device pointers: out float[C][8], the channel-wise
+// (min xyzw, max xyzw) of the DISP slices of tile `tile`; partial: scratch of bounds_partial_floats(C) floats
+// (pass 1 writes at most kBoundsMaxGroups records per slice there, pass 2 folds them).  Both 16-B aligned.
+constexpr int kBoundsMaxGroups = 256;
+size_t bounds_partial_floats(int C);
+hipError_t launch_surface_bounds(const DevView& v, int tile, float* partial, float* out, hipStream_t s);
+// ray.hip: ray casts (ocean_raycast*), device pointers: rays float[count][8], out float[count][8]; bounds:
+// the tile's float[C][8] of launch_surface_bounds for the air skip, or null to sample every node
+hipError_t launch_raycast(const DevView& v, int tile, int iterations, int steps, int refine, const float* bounds,
+                          const float* rays, int count, float* out, hipStream_t s);
+
 // fft4k.hip (N = 2048, 4096): four-step column passes C1 (in place on the
 // 16-wide tile-major intermediate) + C2 (with the pass-B epilogue); replace pass B.
 bool pass_c4_supported(int n);

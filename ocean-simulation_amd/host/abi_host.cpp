@@ -4,8 +4,12 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays]
 //
+// With rays the host reads nothing back per frame: it runs F steps, then one WaterBody::Raycast for six rays (4
+// fixed-point steps, 32 march steps, 8 bisections) and one WaterBody::SurfaceBounds, and writes rays.bin (float32
+// [6][8]), raycast.bin (float32 [6][8]) and bounds.bin (float32 [cascades][8]); the summary line carries both
+// results too ("records", "bounds", %.9g: exact for fp32); tests/test_gpu_ray_host.py checks them.
 // With velocity the host reads nothing back per frame either: it creates the context with OCEAN_F_VELOCITY, runs F
 // steps, then one WaterBody::Velocity for five points (4 steps) and writes velocity_points.bin (float32 [5][2]) and
 // velocity.bin (float32 [5][8]); the summary line carries the records too ("records", %.9g: exact for fp32);
@@ -44,12 +48,13 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
-    if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy or velocity\n");
+    if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity" &&
+        mode != "rays") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity or rays\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -113,6 +118,32 @@ int main(int argc, char** argv) {
             std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"points\": %zu, \"records\": [", F, n,
                         (int)wb.cascades.size(), points.size() / 2);
             for (size_t i = 0; i < rec.size(); ++i) std::printf("%s%.9g", i ? ", " : "", rec[i]);
+            std::printf("]}\n");
+            wb.OnDisable();
+            return 0;
+        }
+        if (mode == "rays") {
+            // six rays (origin, direction, t0, t1): straight down, two slanted, one level, one upwards, one from below
+            const std::vector<float> rays = {
+                0.0f,    40.0f,  0.0f,     0.0f,  -1.0f,  0.0f,  0.0f, 80.0f,
+                37.5f,   25.0f,  -12.25f,  0.6f,  -0.8f,  0.0f,  0.0f, 100.0f,
+                -410.0f, 30.0f,  250.75f,  -2.0f, -1.0f,  3.0f,  0.0f, 60.0f,
+                1e4f,    35.0f,  -3333.0f, 1.0f,  0.0f,   0.0f,  0.0f, 500.0f,
+                -0.5f,   20.0f,  (float)n, 0.0f,  1.0f,   0.5f,  0.0f, 50.0f,
+                12.0f,   -50.0f, 7.0f,     0.0f,  1.0f,   0.0f,  0.0f, 10.0f};
+            wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
+            wb.Awake();
+            for (int f = 0; f < F; ++f) wb.Update((float)f / 60.0f);
+            const std::vector<float> rec = wb.Raycast(rays, 4, 32, 8);
+            const std::vector<float> bounds = wb.SurfaceBounds();
+            write_bin(out + "/rays.bin", rays.data(), rays.size());
+            write_bin(out + "/raycast.bin", rec.data(), rec.size());
+            write_bin(out + "/bounds.bin", bounds.data(), bounds.size());
+            std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"rays\": %zu, \"records\": [", F, n,
+                        (int)wb.cascades.size(), rays.size() / 8);
+            for (size_t i = 0; i < rec.size(); ++i) std::printf("%s%.9g", i ? ", " : "", rec[i]);
+            std::printf("], \"bounds\": [");
+            for (size_t i = 0; i < bounds.size(); ++i) std::printf("%s%.9g", i ? ", " : "", bounds[i]);
             std::printf("]}\n");
             wb.OnDisable();
             return 0;

@@ -206,6 +206,25 @@ public:
         return out;
     }
 
+    // Ray casts against the surface (ocean.h ocean_raycast): rays [M][8] = (origin x, y, z, direction x, y, z, t0,
+    // t1) -> 8 floats per ray: t*, the ray point's height over the water there, the fixed point's residual, the
+    // status (OCEAN_RAY_MISS / _HIT / _SUBMERGED), the normal and the foam at the point met, origin + t* direction.
+    // The water's Physics.Raycast; the reference has none.
+    std::vector<float> Raycast(const std::vector<float>& rays, int iterations = 4, int steps = 64, int refine = 8) const {
+        std::vector<float> out(rays.size() / 8 * 8);
+        check(ocean_raycast(ctx_, 0, iterations, steps, refine, rays.data(), (int)(rays.size() / 8), out.data()),
+              "ocean_raycast");
+        return out;
+    }
+
+    // The per-cascade bounds of the displacement (ocean.h ocean_surface_bounds): 8 floats per cascade, (min x, y,
+    // z, w, max x, y, z, w); their cascade sums bound the displaced mesh.
+    std::vector<float> SurfaceBounds() const {
+        std::vector<float> out(cascades.size() * 8);
+        check(ocean_surface_bounds(ctx_, 0, out.data(), out.size() * sizeof(float)), "ocean_surface_bounds");
+        return out;
+    }
+
     std::vector<float> ReadSlice(int texture, int cascade) const {
         std::vector<float> out(SliceBytes() / 4);
         check(ocean_read(ctx_, texture, 0, cascade, out.data(), SliceBytes()), "ocean_read");

@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = (
     "ocean_surface_grid", "ocean_surface_grid_device", "ocean_surface_grid_async",
     "ocean_body_buoyancy", "ocean_body_buoyancy_device", "ocean_body_buoyancy_async",
     "ocean_query_velocity", "ocean_query_velocity_device", "ocean_query_velocity_async",
+    "ocean_surface_bounds", "ocean_surface_bounds_device",
+    "ocean_raycast", "ocean_raycast_device", "ocean_raycast_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -81,6 +83,11 @@ GRID_MAX_NODES = 1 << 22
 BODY_MAX_BODIES = 8192
 BODY_MAX_PROBES = 4096
 BODY_MAX_SAMPLES = 1 << 22
+# ocean_raycast* statuses and limits (ocean.h)
+RAY_MISS, RAY_HIT, RAY_SUBMERGED = 0, 1, 2
+RAY_MAX_RAYS = 16384
+RAY_MAX_STEPS = 1024
+RAY_MAX_SAMPLES = 1 << 24
 
 
 class OceanError(RuntimeError):
@@ -164,6 +171,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_query_velocity": ([P, i, i, P, i, P], i),
         "ocean_query_velocity_device": ([P, i, i, P, i, P], i),
         "ocean_query_velocity_async": ([P, i, i, P, i, P, ctypes.POINTER(P)], i),
+        "ocean_surface_bounds": ([P, i, P, sz], i),
+        "ocean_surface_bounds_device": ([P, i, P, sz], i),
+        "ocean_raycast": ([P, i, i, i, i, P, i, P], i),
+        "ocean_raycast_device": ([P, i, i, i, i, P, i, P], i),
+        "ocean_raycast_async": ([P, i, i, i, i, P, i, P, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -347,6 +359,57 @@ class OceanContext:
         vp = ctypes.c_void_p
         _check(self.lib.ocean_query_velocity_device(self._h, tile, iterations, vp(points_ptr), count, vp(out_ptr)),
                "ocean_query_velocity_device")
+
+    def surface_bounds(self, tile: int = 0) -> np.ndarray:
+        """Per-cascade bounds of the displacement (ocean.h ocean_surface_bounds), blocking: float32[C][8] =
+        (min x, y, z, w, max x, y, z, w) over the texels of each DISP slice of `tile`, exact.  The cascade sum of
+        the records bounds sample_world's displacement, up to rounding: a displaced mesh's bounding box."""
+        out = np.empty((self.C, 8), np.float32)
+        _check(self.lib.ocean_surface_bounds(self._h, tile, out.ctypes.data, out.nbytes), "ocean_surface_bounds")
+        return out
+
+    def surface_bounds_device(self, out_ptr: int, tile: int = 0) -> None:
+        """The device-pointer form (ocean_surface_bounds_device): out float[C][8] on this context's device, 16-B
+        aligned; async on the context's stream, after the queued steps."""
+        _check(self.lib.ocean_surface_bounds_device(self._h, tile, ctypes.c_void_p(out_ptr), self.C * 32),
+               "ocean_surface_bounds_device")
+
+    @staticmethod
+    def _rays(rays) -> np.ndarray:
+        r = np.ascontiguousarray(rays, np.float32)
+        if r.ndim != 2 or r.shape[1] != 8:
+            raise ValueError(f"rays must be float32[M][8] = (origin xyz, direction xyz, t0, t1), got {r.shape}")
+        return r
+
+    def raycast(self, rays, tile: int = 0, iterations: int = 4, steps: int = 64, refine: int = 8) -> np.ndarray:
+        """Ray casts against the surface (ocean.h ocean_raycast), blocking: rays float[M][8] = (origin x, y, z,
+        direction x, y, z, t0, t1) -> float32[M][8]: (t*, the ray point's height over the water there, the
+        fixed point's residual, status RAY_MISS / RAY_HIT / RAY_SUBMERGED, normal x, y, z, foam).  A march over
+        `steps` intervals of [t0, t1], then `refine` bisections of the first one that crosses; `iterations` as
+        query_surface.  The point met is origin + t* direction."""
+        r = self._rays(rays)
+        out = np.empty((r.shape[0], 8), np.float32)
+        _check(self.lib.ocean_raycast(self._h, tile, iterations, steps, refine, r.ctypes.data, r.shape[0],
+                                      out.ctypes.data), "ocean_raycast")
+        return out
+
+    def raycast_async(self, rays, tile: int = 0, iterations: int = 4, steps: int = 64, refine: int = 8,
+                      buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_raycast_async), as query_surface_async: the rays are cast behind the queued
+        steps and their float32[M][8] lands in pinned host memory; `rays` is consumed by the call."""
+        r = self._rays(rays)
+        return Readback(self, (r.shape[0], 8), r.shape[0] * 32, "ocean_raycast_async",
+                        lambda dst, req: self.lib.ocean_raycast_async(self._h, tile, iterations, steps, refine,
+                                                                      r.ctypes.data, r.shape[0], dst, req), buf)
+
+    def raycast_device(self, rays_ptr: int, count: int, out_ptr: int, tile: int = 0, iterations: int = 4,
+                       steps: int = 64, refine: int = 8) -> None:
+        """The device-pointer form (ocean_raycast_device): rays float[count][8] and out float[count][8] live on
+        this context's device (rays 4-B, out 16-B aligned); async on the context's stream, after the queued
+        steps; count is bounded by RAY_MAX_SAMPLES / steps alone."""
+        vp = ctypes.c_void_p
+        _check(self.lib.ocean_raycast_device(self._h, tile, iterations, steps, refine, vp(rays_ptr), count,
+                                             vp(out_ptr)), "ocean_raycast_device")
 
     @staticmethod
     def grid_points(x0: float, z0: float, dx: float, dz: float, nx: int, ny: int) -> np.ndarray:
@@ -653,6 +716,16 @@ class WaterCascade:
 
 
 @dataclass
+class WaterHit:
+    """What WaterBody.Raycast met (the RaycastHit of Unity's Physics.Raycast, for the water)."""
+    distance: float       # along the normalised direction
+    point: np.ndarray     # origin + distance * direction, float32[3]
+    normal: np.ndarray    # the surface normal there, float32[3]
+    foam: float
+    submerged: bool       # the origin is under water: distance 0
+
+
+@dataclass
 class WaterBody:
     """WaterBody.cs public surface over the HIP library.
 
@@ -893,6 +966,30 @@ class WaterBody:
         drags against still water.  Blocking, and exact at the last step's time."""
         q = np.float32([[worldPosition[0], worldPosition[2]]])
         return self.ctx.query_velocity(q, tile, iterations)[0, :3].copy()
+
+    def Raycast(self, origin, direction, max_distance: float, iterations: int = 4, steps: int = 64, refine: int = 8,
+                tile: int = 0) -> Optional["WaterHit"]:
+        """Physics.Raycast for the water (OceanContext.raycast): the ray from `origin` along `direction`
+        (normalised here, as Unity does) searched over [0, max_distance] in `steps` intervals.  Returns None when
+        it stays above the water, else a WaterHit: distance, point, normal, foam, and `submerged` when the
+        origin itself is under water (distance 0).  The reference has no counterpart.  Blocking."""
+        o, d = np.asarray(origin, np.float64), np.asarray(direction, np.float64)
+        norm = float(np.sqrt((d * d).sum()))
+        if not norm > 0.0:
+            raise ValueError("direction must be non-zero")
+        d = d / norm
+        ray = np.float32([[o[0], o[1], o[2], d[0], d[1], d[2], 0.0, max_distance]])
+        rec = self.ctx.raycast(ray, tile, iterations, steps, refine)[0]
+        if int(rec[3]) == RAY_MISS:
+            return None
+        point = ray[0, :3] + rec[0] * ray[0, 3:6]  # fp32: pos(t*) of ocean.h
+        return WaterHit(float(rec[0]), point, rec[4:7].copy(), float(rec[7]), int(rec[3]) == RAY_SUBMERGED)
+
+    def SurfaceBounds(self, tile: int = 0) -> np.ndarray:
+        """(min xyz, max xyz) float32[2][3] of the cascade-summed displacement, from the per-cascade records
+        (OceanContext.surface_bounds): what a renderer adds to a patch's corners for its bounding box."""
+        rec = self.ctx.surface_bounds(tile)
+        return np.stack([rec[:, 0:3].sum(axis=0, dtype=np.float32), rec[:, 4:7].sum(axis=0, dtype=np.float32)])
 
     # texture-out contract (material properties, WaterBody.cs:277-281)
     def DisplacementsTextures(self, tile: int = 0) -> np.ndarray:
