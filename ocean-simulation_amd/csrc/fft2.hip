@@ -281,10 +281,15 @@ __global__ __launch_bounds__(W * (N / 2) / kElems) void k_colsf_ip(float2* plane
 }
 
 // --------------------------------------------------------------- launch
+// group > 1 (XCD-grouped column launches): a multiple of `group` workgroups, so that the pieces of a tile sit on
+// blocks b, b + 8, ... at every step of the item loop (their items are a multiple of it too).  That placement
+// is speed only (k_cols2), so the OCEAN_MAX_GROUPS cap applies after it and need not keep it.
 template <class K>
-int persistent_grid(K kernel, int threads, int items) {
-    const int g = device_cus() * resident_per_cu((const void*)kernel, threads);
-    return items < g ? items : g;
+int persistent_grid(K kernel, int threads, int items, int max_groups, int group = 1) {
+    int g = device_cus() * resident_per_cu((const void*)kernel, threads);
+    if (items < g) g = items;
+    g -= g % group;
+    return capped_grid(g, max_groups);
 }
 
 template <template <int> class F, class... A>
@@ -312,7 +317,7 @@ struct Rows2 {
         constexpr int T = B * N / kElems;
         const int total = ups * N;
         const int items = (total + B - 1) / B;
-        const int g = persistent_grid(k_rows2<N, B>, T, items);
+        const int g = persistent_grid(k_rows2<N, B>, T, items, v->max_groups);
         launch((k_rows2<N, B>), dim3(g), dim3(T), 0, s, (const float2*)base, base, total, v->tw);
         return hipGetLastError();
     }
@@ -326,8 +331,7 @@ struct Cols2 {
     static hipError_t go_w(const DevView* v, float2* base, int ups, hipStream_t s) {
         constexpr int T = W * N / kElems;
         const int items = ups * (N / W);
-        int g = persistent_grid(k_cols2<N, W, G>, T, items);
-        if (G > 1) g -= g % (8 * G);  // pieces of a tile on blocks b, b + 8, ... at every step of the item loop
+        const int g = persistent_grid(k_cols2<N, W, G>, T, items, v->max_groups, G > 1 ? 8 * G : 1);
         launch((k_cols2<N, W, G>), dim3(g), dim3(T), 0, s, base, items, v->tw);
         return hipGetLastError();
     }
@@ -349,13 +353,12 @@ struct OpFold {
         if (part == 0) {
             constexpr int T = N / kElems;
             const int items = ups * (N / F);
-            const int g = persistent_grid(k_rowsf<N>, T, items);
+            const int g = persistent_grid(k_rowsf<N>, T, items, v->max_groups);
             launch((k_rowsf<N>), dim3(g), dim3(T), 0, s, planes, items, v->tw);
         } else {
             constexpr int T = W * (N / F) / kElems;
             const int items = ups * (N / W);
-            int g = persistent_grid(k_colsf_ip<N, W, G>, T, items);
-            g -= g % (8 * G);  // the pieces of a tile on blocks b, b + 8, ... at every step of the item loop
+            const int g = persistent_grid(k_colsf_ip<N, W, G>, T, items, v->max_groups, 8 * G);
             launch((k_colsf_ip<N, W, G>), dim3(g), dim3(T), 0, s, planes, items, v->tw);
         }
         return hipGetLastError();

@@ -702,9 +702,9 @@ __global__ __launch_bounds__(N / 2) void k_pass_a8(DevView v, float time, int it
 }
 
 template <class K>
-int grid3(K kernel, int threads, int items) {
+int grid3(K kernel, int threads, int items, int max_groups) {
     const int g = device_cus() * resident_per_cu((const void*)kernel, threads);
-    return items < g ? items : g;
+    return capped_grid(items < g ? items : g, max_groups);
 }
 
 // EPF at N = 4096: the next row's h0 in flight across the stages (641 against 658 us, docs/MEASUREMENTS.md)
@@ -721,7 +721,7 @@ hipError_t go_a3k(const DevView& v, float t, hipStream_t s) {
     const int total = v.units * N;
     const int items = (total + RB - 1) / RB;
     constexpr bool EPF = (N == 4096);
-    const int g = grid3(k_pass_a3<N, P, RS, PF, BAND, WT, EPF>, T, items);
+    const int g = grid3(k_pass_a3<N, P, RS, PF, BAND, WT, EPF>, T, items, v.max_groups);
     launch((k_pass_a3<N, P, RS, PF, BAND, WT, EPF>), dim3(g), dim3(T), 0, s, v, t, total);
     return hipGetLastError();
 }
@@ -742,7 +742,7 @@ hipError_t go_b3k(const DevView& v, hipStream_t s) {
     constexpr int W = WT ? WT : b3_w(N);
     constexpr int T = W * N / kElems;
     const int items = v.units * (v.nx / W);
-    const int g = grid3(k_pass_b3<N, P, PFD, WT>, T, items);
+    const int g = grid3(k_pass_b3<N, P, PFD, WT>, T, items, v.max_groups);
     launch((k_pass_b3<N, P, PFD, WT>), dim3(g), dim3(T), 0, s, v, items);
     return hipGetLastError();
 }
@@ -753,7 +753,7 @@ hipError_t go_b2d(const DevView& v, hipStream_t s) {
     constexpr int W = 4;
     constexpr int T = 2 * W * N / kElems;
     const int items = v.units * (v.nx / W);
-    const int g = grid3(k_pass_b2d<N, W>, T, items);
+    const int g = grid3(k_pass_b2d<N, W>, T, items, v.max_groups);
     launch((k_pass_b2d<N, W>), dim3(g), dim3(T), 0, s, v, items);
     return hipGetLastError();
 }
@@ -763,7 +763,7 @@ hipError_t go_b8(const DevView& v, hipStream_t s) {
     constexpr int W = 4;
     constexpr int T = 2 * W * N / 8;
     const int items = v.units * (v.nx / W);
-    const int g = grid3(k_pass_b8<N, W>, T, items);
+    const int g = grid3(k_pass_b8<N, W>, T, items, v.max_groups);
     launch((k_pass_b8<N, W>), dim3(g), dim3(T), 0, s, v, items);
     return hipGetLastError();
 }
@@ -794,7 +794,7 @@ hipError_t go_a4(const DevView& v, float t, hipStream_t s) {
     constexpr int T = N / 4;
     const int ipu = N / 2;
     const int items = v.units * ipu;
-    const int g = grid3(k_pass_a4<N, BAND, WT, P>, T, items);
+    const int g = grid3(k_pass_a4<N, BAND, WT, P>, T, items, v.max_groups);
     launch((k_pass_a4<N, BAND, WT, P>), dim3(g), dim3(T), 0, s, v, t, ipu, items);
     return hipGetLastError();
 }
@@ -804,7 +804,7 @@ hipError_t go_a8(const DevView& v, float t, hipStream_t s) {
     constexpr int T = N / 2;
     const int ipu = N / 2;
     const int items = v.units * ipu;
-    const int g = grid3(k_pass_a8<N, WT>, T, items);
+    const int g = grid3(k_pass_a8<N, WT>, T, items, v.max_groups);
     launch((k_pass_a8<N, WT>), dim3(g), dim3(T), 0, s, v, t, ipu, items);
     return hipGetLastError();
 }

@@ -192,6 +192,8 @@ struct ocean_options {
     int vel_nt = 0;         // OCEAN_VEL_NT=1: the velocity pack kernel writes VEL with nontemporal stores
     int prune = 1;          // OCEAN_PRUNE=0: passes AQ / BQ run every row of a band-limited cascade (dense schedule)
     int ray_bounds = 1;     // OCEAN_RAY_BOUNDS=0: the ray kernel samples every node (no air skip, no bounds launches)
+    int max_groups = 0;     // OCEAN_MAX_GROUPS: at most this many workgroups per persistent launch (the transform passes
+                            // of fftq / fft3 / fft4k / fft2.hip), so that their item loops iterate at small shapes; 0: no cap
 
     static ocean_options from_env() {
         ocean_options o;
@@ -206,6 +208,7 @@ struct ocean_options {
         if (const char* e = std::getenv("OCEAN_VEL_NT")) o.vel_nt = std::atoi(e) != 0;
         if (const char* e = std::getenv("OCEAN_PRUNE")) o.prune = std::atoi(e);
         if (const char* e = std::getenv("OCEAN_RAY_BOUNDS")) o.ray_bounds = std::atoi(e);
+        if (const char* e = std::getenv("OCEAN_MAX_GROUPS")) o.max_groups = std::max(0, std::atoi(e));
         return o;
     }
 };
@@ -289,6 +292,7 @@ struct ocean_ctx {
         v.units = T * C;
         v.planes = P;
         v.normals = (flags & OCEAN_F_NORMALS) != 0;
+        v.max_groups = opt.max_groups;
         v.noise = noise;
         v.h0 = h0;
         v.h0k = h0k;

@@ -46,6 +46,8 @@ struct DevView {
     int units;   // T * C
     int planes;  // 4 (full) or 2 (displacement only)
     bool normals;
+    int max_groups;  // OCEAN_MAX_GROUPS: cap of every persistent launch grid (capped_grid), 0 = none.  Host only;
+                     // it lies in the padding after `normals`, so the kernels' argument layout is unchanged
     const float2* noise;  // [T][N][N]
     float4* h0;           // [U][N][N]
     float2* h0k;          // [U][N][N] h0(k) alone (= h0.xy); the mirror-pair row pass reads h0(k) and h0(-k) here
@@ -85,6 +87,8 @@ struct DevView {
     bool disp_cached;
 };
 
+static_assert(sizeof(DevView) == 240, "DevView is a kernel argument: a new field changes every kernel's argument layout");
+
 struct SpectrumParams {
     float wind_speed, wind_dir_x, wind_dir_y, gravity, fetch, depth;
 };
@@ -95,6 +99,10 @@ struct SpectrumParams {
 // of host time, paid once instead of per launch (small jobs issue a launch every few microseconds).
 int resident_per_cu(const void* kernel, int threads);
 int device_cus();
+// The grid of a persistent launch under OCEAN_MAX_GROUPS: at most max_groups workgroups when the cap is
+// positive.  Every persistent kernel walks item = blockIdx.x, += gridDim.x and no kernel synchronises across
+// workgroups, so any grid >= 1 computes the same texels; a small one makes every workgroup's loop iterate.
+inline int capped_grid(int g, int max_groups) { return max_groups > 0 && g > max_groups ? max_groups : g; }
 
 hipError_t launch_init_spectrum(const DevView& v, const SpectrumParams& p, hipStream_t s);
 hipError_t launch_conjugate(const DevView& v, hipStream_t s);

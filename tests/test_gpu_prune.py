@@ -80,12 +80,12 @@ def test_on_equals_off(tile_w, monkeypatch):
     off.close()
 
 
-def _edge_ctxs(n, m):
+def _edge_ctxs(n, m, tile_w=None):
     """One cascade with L = 100 whose band ends at (m + 0.5) dk: rows |y - N/2| <= m are live.  m = 0: no
     texel but k = 0 lies within 0.5 dk, so the band ends at 1.5 dk and the noise of the rows N/2 +- 1 is
     zero, which leaves the centre row alone live.  A flat second cascade shares the chunk: the library runs
     the pruned kernels only for a chunk with at least an eighth of its items dead, and with the flat unit
-    beside it every extent, 255 and the dense 256 included, goes through them."""
+    beside it every extent, 255 and the dense 256 included, goes through them.  tile_w: OCEAN_TILE_W of both."""
     dk = 2 * math.pi / 100.0
     cas = [dict(wavelength=100.0, cutoff_low=1e-6, cutoff_high=(max(m, 1) + 0.5) * dk, swell=0.3, fade=0.1), FLAT]
     noise = O.generate_noise(n, 20251121)
@@ -94,19 +94,25 @@ def _edge_ctxs(n, m):
         noise[n // 2 + 1] = 0
     ctxs = []
     for env in ({}, {"OCEAN_PRUNE": "0"}):
-        c, _ = _ctx_with_env(env, n, cas)
+        c, _ = _ctx_with_env(dict(env, OCEAN_TILE_W=tile_w) if tile_w else env, n, cas)
         c.set_noise(0, noise)
         c.init_spectrum()
         ctxs.append(c)
     return ctxs
 
 
-@pytest.mark.parametrize("n,m", [(512, 0), (512, 1), (512, 31), (512, 32), (512, 33), (512, 255), (512, 256),
-                                 (1024, 63), (1024, 64), (1024, 65)])
-def test_extent_on_every_edge(n, m):
+EDGES = [(512, 0), (512, 1), (512, 31), (512, 32), (512, 33), (512, 255), (512, 256), (1024, 63), (1024, 64), (1024, 65)]
+# two units are a small job, so N = 512 takes 4-column tiles and N = 1024 its 8-column ones: the row groups again
+# on the wide tiles of 512 (CT::in_dy of a 16-column tile) and on the narrow ones of 1024
+EDGES_W = [(512, 31, "16"), (512, 32, "16"), (512, 33, "16"), (1024, 63, "4"), (1024, 64, "4"), (1024, 65, "4")]
+
+
+@pytest.mark.parametrize("n,m,tile_w", [pytest.param(n, m, None, id=f"{n}-{m}") for n, m in EDGES] +
+                         [pytest.param(n, m, w, id=f"{n}-{m}-w{w}") for n, m, w in EDGES_W])
+def test_extent_on_every_edge(n, m, tile_w):
     """Live extents on either side of pass BQ's stage-0 row groups (32 rows at N = 512, 64 at 1024), the
     centre row alone, every row but row 0 (255) and the dense unit (256)."""
-    on, off = _edge_ctxs(n, m)
+    on, off = _edge_ctxs(n, m, tile_w)
     assert [live_extent(on.read(oh.TEX_H0, 0, c)) for c in range(2)] == [m, -1]
     assert_frames_equal(frames(on), frames(off), f"extent {m}")
     assert_pruned_against_dense(on, off)
