@@ -71,7 +71,9 @@ extern "C" {
  *      Added later within version 4 in the same way: OCEAN_F_VELOCITY, OCEAN_TEX_VELOCITY, ocean_query_velocity,
  *      ocean_query_velocity_device, ocean_query_velocity_async.
  *      Added later within version 4 in the same way: ocean_surface_bounds, ocean_surface_bounds_device,
- *      ocean_raycast, ocean_raycast_device, ocean_raycast_async. */
+ *      ocean_raycast, ocean_raycast_device, ocean_raycast_async.
+ *      Added later within version 4 in the same way: OCEAN_DRAG_LINEAR, OCEAN_DRAG_QUADRATIC, ocean_body_dynamics,
+ *      ocean_body_dynamics_device, ocean_body_dynamics_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -550,6 +552,73 @@ int ocean_query_velocity_device(ocean_ctx *ctx, int tile, int iterations, const 
 int ocean_query_velocity_async(ocean_ctx *ctx, int tile, int iterations, const float *points, int count,
                                float *dst, ocean_readback **req);
 
+/* Body dynamics: ocean_body_buoyancy with the drag against the water's own velocity beside it, reduced on the
+ * device to 64 B per body, whatever P is.  The reference drags against still water (BuoyantObject.FixedUpdate:
+ * -rb.velocity * drag); a host that damps a hull against the water that carries it (surge with a crest, drift
+ * down-wave, roll damping) would, with the entries above, transform M x P probes on the CPU, upload them, read
+ * M x P x 32 B of ocean_query_velocity back, form the relative velocity at every probe and reduce it itself.
+ * Quadratic drag is not linear in a probe's relative velocity, so no per-body sum of the other entries yields it.
+ * Needs a context created with OCEAN_F_VELOCITY.
+ *
+ *   hull:   float[P][5], exactly as ocean_body_buoyancy takes it.
+ *   bodies: float[M][10], exactly as ocean_body_buoyancy takes it.
+ *   motion: body b is float[6] = (vx, vy, vz, ox, oy, oz): the world-frame linear velocity of the body origin
+ *           and the world-frame angular velocity (rad/s).
+ *   out:    record b is float[16].
+ *
+ * All arithmetic is fp32, each line one rounding per operation in the order written (no fused multiply-add);
+ * sqrtf and / are correctly rounded.  Per probe j of body b: a, t, d, w, h', v', rec, eta, r, n, f, g and e are
+ * exactly as ocean_body_buoyancy defines them, and p_K = rec[1..2] is the point the fixed point ends on.  Then
+ *       mode OCEAN_QUERY_SURFACE:   Vs = ocean_query_velocity's Vs(p_K)   (cascade-summed bilinear VEL at p_K: the
+ *                                                                          same taps in the same order)
+ *       mode OCEAN_QUERY_REFERENCE: Vs = VEL[tile * C + 0][py][px]        (the texel GetWaterHeight's pick chose,
+ *                                                                          cascade 0)
+ *       vb  = (vx + (oy * e.z - oz * e.y),  vy + (oz * e.x - ox * e.z),  vz + (ox * e.y - oy * e.x))
+ *                                                                         (the body's velocity at the point e)
+ *       u   = (Vs.x - vb.x, Vs.y - vb.y, Vs.z - vb.z)                     (the water relative to the hull)
+ *       m   = sqrtf((u.x * u.x + u.y * u.y) + u.z * u.z)
+ *       s   = g           (law OCEAN_DRAG_LINEAR)
+ *       s   = g * m       (law OCEAN_DRAG_QUADRATIC)
+ *       F   = (s * u.x, s * u.y, s * u.z)
+ *       T   = (e.y * F.z - e.z * F.y,  e.z * F.x - e.x * F.z,  e.x * F.y - e.y * F.x)
+ *       wet = f > 0 ? 1.0f : 0.0f
+ * The fourteen summed terms are the seven of ocean_body_buoyancy, then F.x, F.y, F.z, T.x, T.y, T.z, wet, each
+ * summed exactly as ocean_body_buoyancy sums: W lanes (the smallest power of two >= P, capped at 64), lane l
+ * accumulating from +0 over j = l, l + W, ... in ascending order, then the xor butterfly for s = W/2, ..., 1.
+ *       out[16b + 0..7]   = the record of ocean_body_buoyancy for the same hull, body, mode and K, bit for bit
+ *       out[16b + 8..10]  = sum F          out[16b + 11..13] = sum T  (about the body origin c)
+ *       out[16b + 14]     = fmaxf over the body's probes with f > 0 of m, from 0  (the largest relative speed on
+ *                                                                                  the wet hull)
+ *       out[16b + 15]     = sum wet        (the number of wet probes; exact: P <= 4096 < 2^24)
+ * What a host does with a record: the drag force is k out[8..10] and the drag torque about c is k out[11..13],
+ * k being the host's coefficient (density and wetted area per unit volume are folded into it, or into the
+ * hull's v); out[14] against a threshold is a slam or spray trigger; out[15] = 0 means airborne.
+ * Dry probes contribute g = 0 through the formulas as written, with no special case.  The library does not
+ * inspect hull, body or motion values: non-finite inputs give unspecified numbers (never an access outside the
+ * textures).  Before the first ocean_step VEL and DISP are zero and the entry is valid.
+ *
+ * The three forms are those of ocean_body_buoyancy: ocean_body_dynamics takes host buffers and blocks;
+ * ocean_body_dynamics_device takes device pointers (hull, bodies and motion 4-B aligned, out 16-B aligned, else
+ * OCEAN_E_INVALID_ARG), is async on the ctx stream and bounds count by OCEAN_BODY_MAX_SAMPLES alone;
+ * ocean_body_dynamics_async consumes `hull`, `bodies` and `motion` before it returns, runs behind the steps
+ * queued so far and lands count x 64 B in `out` through the readback slots, with the same
+ * ocean_readback_status / _wait / _release / _copy_ms.  *req is NULL after every failure.
+ * All three: OCEAN_E_INVALID_ARG, checked before any device call, for everything ocean_body_buoyancy refuses
+ * (the same OCEAN_BODY_MAX_* limits), a null `motion` or a `law` that is neither OCEAN_DRAG_*; then
+ * OCEAN_E_UNSUPPORTED on a context without OCEAN_F_VELOCITY, OCEAN_E_STATE before ocean_init_spectrum and
+ * OCEAN_E_UNSUPPORTED on a column-parity context (as ocean_query_velocity).  count = 0 is a no-op in the
+ * blocking and device forms and OCEAN_E_INVALID_ARG in the async form.  The launch counts as kind 2 of
+ * ocean_kernel_stats / ocean_kernel_name. */
+#define OCEAN_DRAG_LINEAR 0
+#define OCEAN_DRAG_QUADRATIC 1
+int ocean_body_dynamics(ocean_ctx *ctx, int tile, int mode, int iterations, int law, const float *hull, int probes,
+                        const float *bodies, const float *motion, int count, float *out);
+int ocean_body_dynamics_device(ocean_ctx *ctx, int tile, int mode, int iterations, int law, const float *hull,
+                               int probes, const float *bodies, const float *motion, int count, float *out);
+int ocean_body_dynamics_async(ocean_ctx *ctx, int tile, int mode, int iterations, int law, const float *hull,
+                              int probes, const float *bodies, const float *motion, int count, float *out,
+                              ocean_readback **req);
+
 /* Surface bounds: how far the water of a tile can be from rest, per cascade.  A renderer needs them for
  * the bounding box of its displaced mesh (frustum culling, tessellation range; the reference leaves its
  * mesh bounds to Unity's defaults), and ocean_raycast below skips the air above them.
@@ -648,7 +717,7 @@ int ocean_raycast_async(ocean_ctx *ctx, int tile, int iterations, int steps, int
 
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
  * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async /
- * ocean_body_buoyancy_async / ocean_query_velocity_async / ocean_raycast_async request records HIP timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it
+ * ocean_body_buoyancy_async / ocean_query_velocity_async / ocean_raycast_async / ocean_body_dynamics_async request records HIP timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it
  * is off record only untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 

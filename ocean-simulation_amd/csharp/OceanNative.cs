@@ -136,6 +136,17 @@ namespace OceanHip
         public static extern OceanStatus ocean_body_buoyancy_device(IntPtr ctx, int tile, int mode, int iterations, IntPtr hull, int probes, IntPtr bodies, int count, IntPtr output);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_body_buoyancy_async(IntPtr ctx, int tile, int mode, int iterations, [In] float[] hull, int probes, [In] float[] bodies, int count, IntPtr dst, out IntPtr request);
+        // Body dynamics (added within ABI 4 in the same way; OceanFlags.Velocity contexts).  hull and bodies as the buoyant
+        // bodies, motion [count][6] = (world linear velocity of the origin, world angular velocity); 16 floats per body:
+        // the buoyancy record, then sum F xyz, sum T xyz about the origin, the largest relative speed over the wet
+        // probes, the number of wet probes.  law: F = g u (DragLinear) or g |u| u (DragQuadratic) per probe.
+        public const int DragLinear = 0, DragQuadratic = 1;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_dynamics(IntPtr ctx, int tile, int mode, int iterations, int law, [In] float[] hull, int probes, [In] float[] bodies, [In] float[] motion, int count, [Out] float[] output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_dynamics_device(IntPtr ctx, int tile, int mode, int iterations, int law, IntPtr hull, int probes, IntPtr bodies, IntPtr motion, int count, IntPtr output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_dynamics_async(IntPtr ctx, int tile, int mode, int iterations, int law, [In] float[] hull, int probes, [In] float[] bodies, [In] float[] motion, int count, IntPtr dst, out IntPtr request);
         // Surface velocity (added within ABI 4 in the same way; OceanFlags.Velocity contexts).  8 floats per point: velocity
         // x, y, z of the water particle on the surface above the point, residual, height, p.x, p.z, dDxz/dt.
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

@@ -216,6 +216,20 @@ namespace OceanHip
             return output;
         }
 
+        // Buoyancy's records with the drag against the water's own velocity beside them (ocean.h ocean_body_dynamics;
+        // `velocity` set before Awake): motion is [M][6] = (world linear velocity of the body origin, world angular
+        // velocity); per body 16 floats: Buoyancy's 8, then sum F, sum T about the origin, the largest relative speed
+        // over the wet probes and their number.  Drag force k out[8..10], torque k out[11..13] for the host's k; the
+        // reference drags against still water (BuoyantObject.FixedUpdate: -rb.velocity * drag).
+        public float[] Dynamics(float[] hull, float[] bodies, float[] motion, int iterations = 4,
+                                int mode = OceanNative.QuerySurface, int law = OceanNative.DragLinear)
+        {
+            var output = new float[bodies.Length / 10 * 16];
+            OceanNative.Check(OceanNative.ocean_body_dynamics(ctx, 0, mode, iterations, law, hull, hull.Length / 5, bodies,
+                                                              motion, bodies.Length / 10, output), "ocean_body_dynamics");
+            return output;
+        }
+
         // The velocity (x, y, z) of the water particle on the surface above (worldX, worldZ), at the last step's time
         // (ocean.h ocean_query_velocity; `velocity` set before Awake): what drag relative to the water and particle
         // advection need.  The reference has no counterpart: BuoyantObject drags against still water.

@@ -27,12 +27,68 @@
 // step through L1 / L2 / Infinity Cache, each step depending on the one before (latency bound, no
 // roofline claimed); one body of 4 096 probes is 64 sequential chunks on one wave, by definition of
 // the summation order.
+//
+// ocean_body_dynamics* (k_body_dynamics<W>) is the same kernel with the water's velocity joined in: at the
+// point p_K the fixed point ends on, the VEL taps share each cascade's Bil with the DISP and DERIV taps (4 more
+// texels per cascade, no second address computation); with the body's motion (v, omega) per probe
+//     vb = v + omega x e;  u = Vs(p_K) - vb;  m = |u|;  F = g u  or  g m u;  T = e x F;  wet = f > 0
+// and the sums of F, T and wet and the largest m over the wet probes ride the same lanes, trip count and
+// butterfly as the seven buoyancy terms; lane 0 stores four float4 (64 B per body, the first 32 B being the
+// buoyancy record bit for bit).
 #include "ocean_internal.h"
 #include "sample_filter.h"
 #include "spectrum_math.h"
 
 namespace ocean {
 namespace {
+
+// Body b's pose, float[10] = (c, q, s); a lane without a body keeps the identity and loads nothing.
+struct Pose {
+    float cx, cy, cz, ux, uy, uz, qw, sx, sy, sz;
+};
+
+__device__ __forceinline__ Pose load_pose(const float* __restrict__ bodies, size_t b, bool live) {
+    Pose q = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 1.0f, 1.0f};
+    if (live) {
+        const float* B = bodies + 10 * b;
+        q.cx = B[0], q.cy = B[1], q.cz = B[2];
+        q.ux = B[3], q.uy = B[4], q.uz = B[5], q.qw = B[6];
+        q.sx = B[7], q.sy = B[8], q.sz = B[9];
+    }
+    return q;
+}
+
+// Probe j of a body: d (scaled, rotated), w = c + d, and the scaled cell h', v'.
+struct Placed {
+    float dx, dy, dz, wx, wy, wz, hs, vs;
+};
+
+__device__ __forceinline__ Placed place_probe(const Pose& q, const float* __restrict__ H) {
+    const float rx = H[0], ry = H[1], rz = H[2], h = H[3], vol = H[4];
+    const float ax = q.sx * rx, ay = q.sy * ry, az = q.sz * rz;
+    const float tx = 2.0f * (q.uy * az - q.uz * ay), ty = 2.0f * (q.uz * ax - q.ux * az), tz = 2.0f * (q.ux * ay - q.uy * ax);
+    Placed p;
+    p.dx = (ax + q.qw * tx) + (q.uy * tz - q.uz * ty);
+    p.dy = (ay + q.qw * ty) + (q.uz * tx - q.ux * tz);
+    p.dz = (az + q.qw * tz) + (q.ux * ty - q.uy * tx);
+    p.wx = q.cx + p.dx, p.wy = q.cy + p.dy, p.wz = q.cz + p.dz;
+    p.hs = h * q.sy, p.vs = ((vol * q.sx) * q.sy) * q.sz;
+    return p;
+}
+
+// The submerged part of the probe's cell under the height eta: f, g = v' f and e.y of its centroid.
+struct Wet {
+    float f, g, ey;
+};
+
+__device__ __forceinline__ Wet submerge(const Placed& p, float eta) {
+    const float bottom = p.wy - 0.5f * p.hs;
+    Wet w;
+    w.f = fminf(fmaxf((eta - bottom) / p.hs, 0.0f), 1.0f);
+    w.g = p.vs * w.f;
+    w.ey = (p.dy - 0.5f * p.hs) + 0.5f * (w.f * p.hs);
+    return w;
+}
 
 // hull float[P][5] = (rx, ry, rz, h, v); bodies float[M][10] = (c, q, s); out[2 b], out[2 b + 1] = record b.
 template <int W>
@@ -44,47 +100,30 @@ __global__ __launch_bounds__(256) void k_body_buoyancy(DevView v, int tile, int 
     const int l = (int)(threadIdx.x % W);
     const size_t b = (size_t)blockIdx.x * kBodies + threadIdx.x / W;
     const bool live = b < (size_t)count;
-    float cx = 0.0f, cy = 0.0f, cz = 0.0f, ux = 0.0f, uy = 0.0f, uz = 0.0f, qw = 1.0f, sx = 1.0f, sy = 1.0f, sz = 1.0f;
-    if (live) {
-        const float* B = bodies + 10 * b;
-        cx = B[0], cy = B[1], cz = B[2];
-        ux = B[3], uy = B[4], uz = B[5], qw = B[6];
-        sx = B[7], sy = B[8], sz = B[9];
-    }
+    const Pose pose = load_pose(bodies, b, live);
     float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f, t3 = 0.0f, t4 = 0.0f, t5 = 0.0f, t6 = 0.0f, rmax = 0.0f;
     const int trips = (probes + W - 1) / W;  // the same for every lane of the launch
     for (int it = 0; it < trips; ++it) {
         const int j = it * W + l;
         if (live && j < probes) {
-            const float* H = hull + 5 * (size_t)j;
-            const float rx = H[0], ry = H[1], rz = H[2], h = H[3], vol = H[4];
-            const float ax = sx * rx, ay = sy * ry, az = sz * rz;
-            const float tx = 2.0f * (uy * az - uz * ay), ty = 2.0f * (uz * ax - ux * az), tz = 2.0f * (ux * ay - uy * ax);
-            const float dx = (ax + qw * tx) + (uy * tz - uz * ty);
-            const float dy = (ay + qw * ty) + (uz * tx - ux * tz);
-            const float dz = (az + qw * tz) + (ux * ty - uy * tx);
-            const float wx = cx + dx, wy = cy + dy, wz = cz + dz;
+            const Placed pr = place_probe(pose, hull + 5 * (size_t)j);
             float eta, r = 0.0f, nx = 0.0f, ny = 1.0f, nz = 0.0f;
             if (mode != OCEAN_QUERY_REFERENCE) {
-                const float2 p = surface_fixed_point(v, tile, wx, wz, iterations);
-                const SurfaceRecord rec = surface_record(sample_cascades(v, tile, p.x, p.y, 0.0f), p, wx, wz);
+                const float2 p = surface_fixed_point(v, tile, pr.wx, pr.wz, iterations);
+                const SurfaceRecord rec = surface_record(sample_cascades(v, tile, p.x, p.y, 0.0f), p, pr.wx, pr.wz);
                 eta = rec.at.x, r = rec.at.w, nx = rec.nf.x, ny = rec.nf.y, nz = rec.nf.z;
             } else {
-                const int px = reference_texel(wx, v.n), py = reference_texel(wz, v.n);
+                const int px = reference_texel(pr.wx, v.n), py = reference_texel(pr.wz, v.n);
                 eta = (v.disp + (size_t)tile * v.C * v.n * v.n)[(size_t)py * v.n + px].y;  // cascade 0 of the tile
             }
-            const float hs = h * sy, vs = ((vol * sx) * sy) * sz;
-            const float bottom = wy - 0.5f * hs;
-            const float f = fminf(fmaxf((eta - bottom) / hs, 0.0f), 1.0f);
-            const float g = vs * f;
-            const float ey = (dy - 0.5f * hs) + 0.5f * (f * hs);
-            t0 = t0 + g;
-            t1 = t1 + g * dx;
-            t2 = t2 + g * ey;
-            t3 = t3 + g * dz;
-            t4 = t4 + g * nx;
-            t5 = t5 + g * ny;
-            t6 = t6 + g * nz;
+            const Wet w = submerge(pr, eta);
+            t0 = t0 + w.g;
+            t1 = t1 + w.g * pr.dx;
+            t2 = t2 + w.g * w.ey;
+            t3 = t3 + w.g * pr.dz;
+            t4 = t4 + w.g * nx;
+            t5 = t5 + w.g * ny;
+            t6 = t6 + w.g * nz;
             rmax = fmaxf(rmax, r);
         }
     }
@@ -105,6 +144,120 @@ __global__ __launch_bounds__(256) void k_body_buoyancy(DevView v, int tile, int 
     }
 }
 
+// The full sample at the fixed point's end p with the VEL taps beside it: per cascade one Bil serves the DISP,
+// DERIV and VEL texels.  disp and deriv are sample_cascades(v, tile, x, z, 0)'s bit for bit (lod 0 is level 0
+// with and without mip chains), vs is k_query_velocity's Vs(p); TURB, which no body term reads, is not tapped.
+__device__ __forceinline__ void sample_cascades_vel(const DevView& v, const float4* __restrict__ vel, int tile, float x,
+                                                    float z, WorldSample& s, float4& vs) {
+    s.disp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    s.deriv = s.disp;
+    s.turb = 0.0f;
+    vs = s.disp;
+    for (int c = 0; c < v.C; ++c) {
+        const float L = v.casc[c * 5];
+        const size_t slice = (size_t)(tile * v.C + c) * v.n * v.n;
+        const Bil b = bil(x / L, z / L, v.n);
+        s.disp = add4(s.disp, tap(v.disp + slice, v.n, b));
+        if (v.deriv) s.deriv = add4(s.deriv, tap(v.deriv + slice, v.n, b));
+        vs = add4(vs, tap(vel + slice, v.n, b));
+    }
+}
+
+// ocean_body_dynamics*: the buoyancy record and, beside it, the drag of the water's velocity relative to the
+// hull, summed over the wet probes.  motion float[M][6] = (v, omega); out[4 b .. 4 b + 3] = record b (64 B).
+// The same mapping, trip count and butterfly as k_body_buoyancy<W>: fourteen sums and two maxima per lane.
+template <int W>
+__global__ __launch_bounds__(256) void k_body_dynamics(DevView v, const float4* __restrict__ vel, int tile, int mode,
+                                                       int iterations, int law, const float* __restrict__ hull,
+                                                       int probes, const float* __restrict__ bodies,
+                                                       const float* __restrict__ motion, int count,
+                                                       float4* __restrict__ out) {
+    constexpr int kBodies = 256 / W;  // bodies per workgroup
+    const int l = (int)(threadIdx.x % W);
+    const size_t b = (size_t)blockIdx.x * kBodies + threadIdx.x / W;
+    const bool live = b < (size_t)count;
+    const Pose pose = load_pose(bodies, b, live);
+    float vx = 0.0f, vy = 0.0f, vz = 0.0f, ox = 0.0f, oy = 0.0f, oz = 0.0f;
+    if (live) {
+        const float* Mo = motion + 6 * b;
+        vx = Mo[0], vy = Mo[1], vz = Mo[2];
+        ox = Mo[3], oy = Mo[4], oz = Mo[5];
+    }
+    float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f, t3 = 0.0f, t4 = 0.0f, t5 = 0.0f, t6 = 0.0f, rmax = 0.0f;
+    float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f, q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, wet = 0.0f, mmax = 0.0f;
+    const int trips = (probes + W - 1) / W;  // the same for every lane of the launch
+    for (int it = 0; it < trips; ++it) {
+        const int j = it * W + l;
+        if (live && j < probes) {
+            const Placed pr = place_probe(pose, hull + 5 * (size_t)j);
+            float eta, r = 0.0f, nx = 0.0f, ny = 1.0f, nz = 0.0f;
+            float4 vs;
+            if (mode != OCEAN_QUERY_REFERENCE) {
+                const float2 p = surface_fixed_point(v, tile, pr.wx, pr.wz, iterations);
+                WorldSample s;
+                sample_cascades_vel(v, vel, tile, p.x, p.y, s, vs);
+                const SurfaceRecord rec = surface_record(s, p, pr.wx, pr.wz);
+                eta = rec.at.x, r = rec.at.w, nx = rec.nf.x, ny = rec.nf.y, nz = rec.nf.z;
+            } else {
+                const int px = reference_texel(pr.wx, v.n), py = reference_texel(pr.wz, v.n);
+                const size_t at = (size_t)tile * v.C * v.n * v.n + (size_t)py * v.n + px;  // cascade 0 of the tile
+                eta = v.disp[at].y;
+                vs = vel[at];
+            }
+            const Wet w = submerge(pr, eta);
+            const float ex = pr.dx, ey = w.ey, ez = pr.dz;
+            const float bx = vx + (oy * ez - oz * ey), by = vy + (oz * ex - ox * ez), bz = vz + (ox * ey - oy * ex);
+            const float ux = vs.x - bx, uy = vs.y - by, uz = vs.z - bz;
+            const float m = sqrtf((ux * ux + uy * uy) + uz * uz);
+            const float sc = law == OCEAN_DRAG_QUADRATIC ? w.g * m : w.g;
+            const float Fx = sc * ux, Fy = sc * uy, Fz = sc * uz;
+            t0 = t0 + w.g;
+            t1 = t1 + w.g * pr.dx;
+            t2 = t2 + w.g * w.ey;
+            t3 = t3 + w.g * pr.dz;
+            t4 = t4 + w.g * nx;
+            t5 = t5 + w.g * ny;
+            t6 = t6 + w.g * nz;
+            rmax = fmaxf(rmax, r);
+            f0 = f0 + Fx;
+            f1 = f1 + Fy;
+            f2 = f2 + Fz;
+            q0 = q0 + (ey * Fz - ez * Fy);
+            q1 = q1 + (ez * Fx - ex * Fz);
+            q2 = q2 + (ex * Fy - ey * Fx);
+            if (w.f > 0.0f) {
+                wet = wet + 1.0f;
+                mmax = fmaxf(mmax, m);
+            }
+        }
+    }
+#pragma unroll
+    for (int s = W / 2; s > 0; s >>= 1) {  // every lane of the wave takes part; l xor s stays in the segment
+        t0 = t0 + __shfl_xor(t0, s);
+        t1 = t1 + __shfl_xor(t1, s);
+        t2 = t2 + __shfl_xor(t2, s);
+        t3 = t3 + __shfl_xor(t3, s);
+        t4 = t4 + __shfl_xor(t4, s);
+        t5 = t5 + __shfl_xor(t5, s);
+        t6 = t6 + __shfl_xor(t6, s);
+        rmax = fmaxf(rmax, __shfl_xor(rmax, s));
+        f0 = f0 + __shfl_xor(f0, s);
+        f1 = f1 + __shfl_xor(f1, s);
+        f2 = f2 + __shfl_xor(f2, s);
+        q0 = q0 + __shfl_xor(q0, s);
+        q1 = q1 + __shfl_xor(q1, s);
+        q2 = q2 + __shfl_xor(q2, s);
+        mmax = fmaxf(mmax, __shfl_xor(mmax, s));
+        wet = wet + __shfl_xor(wet, s);
+    }
+    if (live && l == 0) {
+        out[4 * b] = make_float4(t0, t1, t2, t3);
+        out[4 * b + 1] = make_float4(t4, t5, t6, rmax);
+        out[4 * b + 2] = make_float4(f0, f1, f2, q0);
+        out[4 * b + 3] = make_float4(q1, q2, mmax, wet);
+    }
+}
+
 template <int W>
 void launch_w(const DevView& v, int tile, int mode, int iterations, const float* hull, int probes,
               const float* bodies, int count, float* out, hipStream_t s) {
@@ -113,6 +266,15 @@ void launch_w(const DevView& v, int tile, int mode, int iterations, const float*
     const unsigned g = (unsigned)(((size_t)count + kBodies - 1) / kBodies);
     launch(k_body_buoyancy<W>, dim3(g), dim3(256), 0, s, v, tile, mode, iterations, hull, probes, bodies, count,
            reinterpret_cast<float4*>(out));
+}
+
+template <int W>
+void launch_dynamics_w(const DevView& v, const float4* vel, int tile, int mode, int iterations, int law, const float* hull,
+                       int probes, const float* bodies, const float* motion, int count, float* out, hipStream_t s) {
+    constexpr int kBodies = 256 / W;
+    const unsigned g = (unsigned)(((size_t)count + kBodies - 1) / kBodies);  // as launch_w
+    launch(k_body_dynamics<W>, dim3(g), dim3(256), 0, s, v, vel, tile, mode, iterations, law, hull, probes, bodies, motion,
+           count, reinterpret_cast<float4*>(out));
 }
 
 }  // namespace
@@ -136,6 +298,26 @@ hipError_t launch_body_buoyancy(const DevView& v, int tile, int mode, int iterat
         case 32: launch_w<32>(v, tile, mode, iterations, hull, probes, bodies, count, out, s); break;
         default: launch_w<64>(v, tile, mode, iterations, hull, probes, bodies, count, out, s); break;
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_body_dynamics(const DevView& v, const float4* vel, int tile, int mode, int iterations, int law,
+                                const float* hull, int probes, const float* bodies, const float* motion, int count,
+                                float* out, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    if (probes < 1 || !vel) return hipErrorInvalidValue;
+#define OCEAN_DYNAMICS_W(w) \
+    launch_dynamics_w<w>(v, vel, tile, mode, iterations, law, hull, probes, bodies, motion, count, out, s)
+    switch (body_segment_width(probes)) {
+        case 1: OCEAN_DYNAMICS_W(1); break;
+        case 2: OCEAN_DYNAMICS_W(2); break;
+        case 4: OCEAN_DYNAMICS_W(4); break;
+        case 8: OCEAN_DYNAMICS_W(8); break;
+        case 16: OCEAN_DYNAMICS_W(16); break;
+        case 32: OCEAN_DYNAMICS_W(32); break;
+        default: OCEAN_DYNAMICS_W(64); break;
+    }
+#undef OCEAN_DYNAMICS_W
     return hipGetLastError();
 }
 

@@ -112,14 +112,20 @@ void generate_noise_host(int n, uint64_t seed, float* out);
 // kQueryPointsOffset on; and, from the slot's first such request on, a pinned host copy of the inputs
 // (`pts_host`), so that the caller's buffers are consumed inside the call and the upload reads memory that
 // stays put until the request is released.  Sized by the largest point query; the other consumers assert
-// that they fit.
+// that they fit.  One consumer's inputs outgrow the 512 KiB behind kQueryPointsOffset: ocean_body_dynamics_async
+// stages 592 KiB at its limits, so its inputs start at kDynamicsInputOffset, right behind its own smaller
+// results (the arithmetic is at the entry), and the pinned copy is sized for it (kStageInputBytes).
 constexpr size_t kQueryPointsOffset = (size_t)OCEAN_QUERY_MAX_POINTS * 8 * sizeof(float);
 constexpr size_t kQuerySlotBytes = kQueryPointsOffset + (size_t)OCEAN_QUERY_MAX_POINTS * 2 * sizeof(float);
+constexpr size_t kDynamicsInputOffset = (size_t)OCEAN_BODY_MAX_BODIES * 16 * sizeof(float);
+constexpr size_t kDynamicsInputBytes = (size_t)OCEAN_BODY_MAX_BODIES * (10 + 6) * sizeof(float) +
+                                       (size_t)OCEAN_BODY_MAX_PROBES * 5 * sizeof(float);
+constexpr size_t kStageInputBytes = std::max(kQuerySlotBytes - kQueryPointsOffset, kDynamicsInputBytes);
 // Workgroup tile of the grid kernel (grid.hip), nodes along x: the fastest of the shapes measured.
 constexpr int kGridTileDefault = 32;
 struct StageSlot {
     void* mem = nullptr;
-    void* pts_host = nullptr;    // pinned, kQuerySlotBytes - kQueryPointsOffset: the inputs of the request holding the slot
+    void* pts_host = nullptr;    // pinned, kStageInputBytes: the inputs of the request holding the slot
     hipEvent_t after = nullptr;  // the snapshot is in the slot (the copy stream waits for it)
     hipEvent_t done = nullptr;   // the host copy has landed (untimed requests)
     hipEvent_t tstart = nullptr, tdone = nullptr;  // timed requests: around the host copy itself
@@ -1178,16 +1184,17 @@ int run_staged(ocean_ctx* ctx, const char* entry, std::initializer_list<HostInpu
 // caller's inputs are consumed here, into the pinned memory the slot owns, so the one upload that carries
 // them all is truly asynchronous and reads nothing of the caller's after this call returns; the kernel
 // then writes its results at the slot's base.  (start_readback reports a hipError_t, hence the bridge.)
+// in_offset: where the inputs start in the slot (behind the results; the caller asserts that both fit).
 template <class Launch>
 int start_staged_readback(ocean_ctx* ctx, std::initializer_list<HostInput> inputs, void* dst, size_t out_bytes,
-                          Launch&& launch, ocean_readback** req) {
+                          Launch&& launch, ocean_readback** req, size_t in_offset = kQueryPointsOffset) {
     return start_readback(
         ctx, dst, out_bytes,
         [&](StageSlot* sl) {
-            char* d_in = static_cast<char*>(sl->mem) + kQueryPointsOffset;
+            char* d_in = static_cast<char*>(sl->mem) + in_offset;
             if (inputs.size() != 0) {
                 if (!sl->pts_host) {
-                    const hipError_t e = hipHostMalloc(&sl->pts_host, kQuerySlotBytes - kQueryPointsOffset, hipHostMallocDefault);
+                    const hipError_t e = hipHostMalloc(&sl->pts_host, kStageInputBytes, hipHostMallocDefault);
                     if (e != hipSuccess) return e;
                 }
                 size_t in_bytes = 0;
@@ -1675,6 +1682,89 @@ int ocean_body_buoyancy_async(ocean_ctx* ctx, int tile, int mode, int iterations
             return launch_body(ctx, tile, mode, iterations, d_in + (size_t)count * 10, probes, d_in, count, d_out);
         },
         req);
+}
+
+// Body dynamics (ocean.h): the checks of the buoyant bodies, then its own two arguments, all before any device
+// call; then the context's flag and state, as the velocity queries.
+static int check_dynamics(ocean_ctx* ctx, int tile, int mode, int iterations, int law, const float* hull, int probes,
+                          const float* bodies, const float* motion, int count, const float* out, bool limit) {
+    if (int r = check_body(ctx, tile, mode, iterations, hull, probes, bodies, count, out, limit)) return r;
+    if (!motion) return fail(OCEAN_E_INVALID_ARG, "null motion");
+    if (law != OCEAN_DRAG_LINEAR && law != OCEAN_DRAG_QUADRATIC) return fail(OCEAN_E_INVALID_ARG, "unknown drag law");
+    return OCEAN_OK;
+}
+
+static int check_dynamics_state(const ocean_ctx* ctx) {
+    if (!(ctx->flags & OCEAN_F_VELOCITY))
+        return fail(OCEAN_E_UNSUPPORTED, "ocean_body_dynamics needs a context created with OCEAN_F_VELOCITY");
+    if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, "ocean_init_spectrum must precede ocean_body_dynamics");
+    if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, "body dynamics on a column-parity shard (half the columns)");
+    return OCEAN_OK;
+}
+
+// The dynamics kernel on the ctx stream (device pointers; kind 2 of ocean_kernel_stats).
+static int launch_dynamics(ocean_ctx* ctx, int tile, int mode, int iterations, int law, const float* d_hull, int probes,
+                           const float* d_bodies, const float* d_motion, int count, float* d_out) {
+    const ocean::DevView v = ctx->view();
+    return timed(ctx, 2,
+                 [&] {
+                     return ocean::launch_body_dynamics(v, ctx->vel, tile, mode, iterations, law, d_hull, probes, d_bodies,
+                                                        d_motion, count, d_out, ctx->stream);
+                 },
+                 "body_dynamics");
+}
+
+// The staged inputs of the host and async forms: the bodies, the motion behind them, then the hull (floats all).
+// The async form at the limits: 8192 x 40 B = 320 KiB of bodies + 8192 x 24 B = 192 KiB of motion + 4096 x 20 B =
+// 80 KiB of hull = 592 KiB staged, and 8192 x 64 B = 512 KiB of records.  A slot is max(N N 16,
+// OCEAN_QUERY_MAX_POINTS 40) >= 2560 KiB, so records and inputs fit it with room to spare (1104 KiB), but not
+// in the point queries' layout, whose inputs start at 2048 KiB and have 512 KiB: here the records take the
+// slot's first 512 KiB and the inputs follow them at kDynamicsInputOffset, ending at 1104 KiB.
+static_assert(kDynamicsInputBytes == 592 * 1024 && kDynamicsInputOffset == 512 * 1024, "the arithmetic above");
+static_assert(kDynamicsInputOffset + kDynamicsInputBytes <= kQuerySlotBytes, "records and inputs fit the smallest slot");
+static_assert(kDynamicsInputBytes <= kStageInputBytes, "a slot's pinned input copy holds every dynamics request");
+static_assert(kDynamicsInputOffset % 16 == 0, "the inputs start float4-aligned");
+
+int ocean_body_dynamics_device(ocean_ctx* ctx, int tile, int mode, int iterations, int law, const float* hull, int probes,
+                               const float* bodies, const float* motion, int count, float* out) {
+    if (int r = check_dynamics(ctx, tile, mode, iterations, law, hull, probes, bodies, motion, count, out, false)) return r;
+    if (int r = check_aligned("ocean_body_dynamics_device", "hull, bodies and motion", {hull, bodies, motion}, out)) return r;
+    if (int r = check_dynamics_state(ctx)) return r;
+    if (count == 0) return OCEAN_OK;
+    OCEAN_ENTER(ctx);
+    return launch_dynamics(ctx, tile, mode, iterations, law, hull, probes, bodies, motion, count, out);
+}
+
+int ocean_body_dynamics(ocean_ctx* ctx, int tile, int mode, int iterations, int law, const float* hull, int probes,
+                        const float* bodies, const float* motion, int count, float* out) {
+    if (int r = check_dynamics(ctx, tile, mode, iterations, law, hull, probes, bodies, motion, count, out, true)) return r;
+    if (int r = check_dynamics_state(ctx)) return r;
+    if (count == 0) return OCEAN_OK;
+    OCEAN_ENTER(ctx);
+    return run_staged(ctx, "ocean_body_dynamics",
+                      {{bodies, (size_t)count * 10 * 4}, {motion, (size_t)count * 6 * 4}, {hull, (size_t)probes * 5 * 4}}, out,
+                      (size_t)count * 16 * 4, [&](const float* d_in, float* d_out) {
+                          return launch_dynamics(ctx, tile, mode, iterations, law, d_in + (size_t)count * 16, probes, d_in,
+                                                 d_in + (size_t)count * 10, count, d_out);
+                      });
+}
+
+int ocean_body_dynamics_async(ocean_ctx* ctx, int tile, int mode, int iterations, int law, const float* hull, int probes,
+                              const float* bodies, const float* motion, int count, float* out, ocean_readback** req) {
+    if (!req) return fail(OCEAN_E_INVALID_ARG, "req is null");
+    *req = nullptr;
+    if (int r = check_dynamics(ctx, tile, mode, iterations, law, hull, probes, bodies, motion, count, out, true)) return r;
+    if (count == 0) return fail(OCEAN_E_INVALID_ARG, "ocean_body_dynamics_async: no bodies, so no request");
+    if (int r = check_dynamics_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    return start_staged_readback(
+        ctx, {{bodies, (size_t)count * 10 * 4}, {motion, (size_t)count * 6 * 4}, {hull, (size_t)probes * 5 * 4}}, out,
+        (size_t)count * 16 * 4,
+        [&](const float* d_in, float* d_out) {
+            return launch_dynamics(ctx, tile, mode, iterations, law, d_in + (size_t)count * 16, probes, d_in,
+                                   d_in + (size_t)count * 10, count, d_out);
+        },
+        req, kDynamicsInputOffset);
 }
 
 // Surface bounds and ray casts (ocean.h).

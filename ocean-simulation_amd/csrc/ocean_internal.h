@@ -154,6 +154,11 @@ hipError_t launch_surface_grid(const DevView& v, int tile, int mode, int iterati
 int body_segment_width(int probes);
 hipError_t launch_body_buoyancy(const DevView& v, int tile, int mode, int iterations, const float* hull, int probes,
                                 const float* bodies, int count, float* out, hipStream_t s);
+// body.hip: the buoyancy record and the drag against the water's velocity (ocean_body_dynamics*), device pointers:
+// vel = the context's VEL float4 [U][N][N], motion float[count][6], law OCEAN_DRAG_*, out float[count][16]
+hipError_t launch_body_dynamics(const DevView& v, const float4* vel, int tile, int mode, int iterations, int law,
+                                const float* hull, int probes, const float* bodies, const float* motion, int count,
+                                float* out, hipStream_t s);
 // velocity.hip: surface velocity (OCEAN_F_VELOCITY).  `scratch` is the context's two velocity planes, float2
 // [2][U][N][N] plane-major: launch_evolve_velocity writes the packed planes of dh/dt at t there (from v.h0 and
 // v.waves), the operator IFFT transforms them in place as 2 U unit-planes, launch_pack_velocity interleaves them

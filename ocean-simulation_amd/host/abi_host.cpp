@@ -4,12 +4,16 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics]
 //
 // With rays the host reads nothing back per frame: it runs F steps, then one WaterBody::Raycast for six rays (4
 // fixed-point steps, 32 march steps, 8 bisections) and one WaterBody::SurfaceBounds, and writes rays.bin (float32
 // [6][8]), raycast.bin (float32 [6][8]) and bounds.bin (float32 [cascades][8]); the summary line carries both
 // results too ("records", "bounds", %.9g: exact for fp32); tests/test_gpu_ray_host.py checks them.
+// With dynamics the host runs the buoyancy mode's five boxes on a velocity context (OCEAN_F_VELOCITY): F steps, then
+// one WaterBody::Dynamics with five fixed motions (surface mode, 4 steps, linear drag), and writes hull.bin,
+// bodies.bin, motion.bin (float32 [5][6]) and dynamics.bin (float32 [5][16]); the summary line carries the records
+// too ("records", %.9g: exact for fp32); tests/test_gpu_dynamics_host.py checks them.
 // With velocity the host reads nothing back per frame either: it creates the context with OCEAN_F_VELOCITY, runs F
 // steps, then one WaterBody::Velocity for five points (4 steps) and writes velocity_points.bin (float32 [5][2]) and
 // velocity.bin (float32 [5][8]); the summary line carries the records too ("records", %.9g: exact for fp32);
@@ -48,13 +52,13 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
     if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity" &&
-        mode != "rays") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity or rays\n");
+        mode != "rays" && mode != "dynamics") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays or dynamics\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -75,7 +79,7 @@ int main(int argc, char** argv) {
         wb.texturesSize = n;
         wb.cascades.assign(scene, scene + (C < 4 ? C : 4));
         wb.seed = 42;
-        if (mode == "buoyancy") {
+        if (mode == "buoyancy" || mode == "dynamics") {
             // a box of 4 x 3 cells (x fastest, then z), one layer: cell centres of [-1/2, 1/2]^3
             std::vector<float> hull;
             for (int k = 0; k < 3; ++k)
@@ -91,13 +95,23 @@ int main(int argc, char** argv) {
                 -410.0f, -0.5f,  250.75f,  0.0f,  0.0f,  0.6f,  0.8f,  6.0f, 1.5f,  2.5f,
                 1e4f,    0.125f, -3333.0f, 0.28f, 0.0f,  0.0f,  0.96f, 2.0f, 0.75f, 8.0f,
                 -0.5f,   -0.25f, (float)n, 0.0f,  -0.6f, 0.0f,  0.8f,  5.0f, 3.0f,  1.0f};
+            // five motions: world linear velocity of the origin, world angular velocity (dynamics mode)
+            const std::vector<float> motion = {
+                0.0f,  0.0f,   0.0f,  0.0f,  0.0f,   0.0f,
+                1.0f,  2.0f,   -3.0f, 0.0f,  0.0f,   0.0f,
+                0.0f,  0.0f,   0.0f,  0.0f,  1.0f,   0.0f,
+                -2.5f, 0.125f, 4.0f,  0.25f, -0.5f,  0.75f,
+                0.5f,  -1.0f,  0.25f, -1.5f, 0.125f, 0.0f};
+            const bool dynamics = mode == "dynamics";
+            wb.velocity = dynamics;
             wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
             wb.Awake();
             for (int f = 0; f < F; ++f) wb.Update((float)f / 60.0f);
-            const std::vector<float> rec = wb.Buoyancy(hull, bodies);
+            const std::vector<float> rec = dynamics ? wb.Dynamics(hull, bodies, motion) : wb.Buoyancy(hull, bodies);
             write_bin(out + "/hull.bin", hull.data(), hull.size());
             write_bin(out + "/bodies.bin", bodies.data(), bodies.size());
-            write_bin(out + "/buoyancy.bin", rec.data(), rec.size());
+            if (dynamics) write_bin(out + "/motion.bin", motion.data(), motion.size());
+            write_bin(out + (dynamics ? "/dynamics.bin" : "/buoyancy.bin"), rec.data(), rec.size());
             std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"probes\": %zu, \"bodies\": %zu, \"records\": [", F, n,
                         (int)wb.cascades.size(), hull.size() / 5, bodies.size() / 10);
             for (size_t i = 0; i < rec.size(); ++i) std::printf("%s%.9g", i ? ", " : "", rec[i]);

@@ -195,6 +195,21 @@ public:
         return out;
     }
 
+    // Buoyancy's records with the drag against the water's own velocity beside them (ocean.h ocean_body_dynamics;
+    // `velocity` set before Awake): motion [M][6] = (world linear velocity of the body origin, world angular
+    // velocity) -> 16 floats per body: Buoyancy's 8, then sum F, sum T about the origin, the largest relative speed
+    // over the wet probes and their number.  Drag force k out[8..10], torque k out[11..13] for the host's k.
+    std::vector<float> Dynamics(const std::vector<float>& hull, const std::vector<float>& bodies,
+                                const std::vector<float>& motion, int iterations = 4, int mode = OCEAN_QUERY_SURFACE,
+                                int law = OCEAN_DRAG_LINEAR) const {
+        if (motion.size() / 6 != bodies.size() / 10) throw std::runtime_error("Dynamics: one motion per body");
+        std::vector<float> out(bodies.size() / 10 * 16);
+        check(ocean_body_dynamics(ctx_, 0, mode, iterations, law, hull.data(), (int)(hull.size() / 5), bodies.data(),
+                                  motion.data(), (int)(bodies.size() / 10), out.data()),
+              "ocean_body_dynamics");
+        return out;
+    }
+
     // The water's velocity at M world positions (ocean.h ocean_query_velocity; `velocity` set before Awake):
     // points [M][2] = (world x, world z) -> 8 floats per point: velocity x, y, z of the water particle on the
     // surface above the point, residual, height, p.x, p.z, dDxz/dt.  What drag relative to the water and particle

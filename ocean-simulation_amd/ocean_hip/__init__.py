@@ -71,6 +71,7 @@ EXPORTED_SYMBOLS = (
     "ocean_query_velocity", "ocean_query_velocity_device", "ocean_query_velocity_async",
     "ocean_surface_bounds", "ocean_surface_bounds_device",
     "ocean_raycast", "ocean_raycast_device", "ocean_raycast_async",
+    "ocean_body_dynamics", "ocean_body_dynamics_device", "ocean_body_dynamics_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -83,6 +84,8 @@ GRID_MAX_NODES = 1 << 22
 BODY_MAX_BODIES = 8192
 BODY_MAX_PROBES = 4096
 BODY_MAX_SAMPLES = 1 << 22
+# ocean_body_dynamics* drag laws (ocean.h); modes and limits are the bodies'
+DRAG_LINEAR, DRAG_QUADRATIC = 0, 1
 # ocean_raycast* statuses and limits (ocean.h)
 RAY_MISS, RAY_HIT, RAY_SUBMERGED = 0, 1, 2
 RAY_MAX_RAYS = 16384
@@ -176,6 +179,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_raycast": ([P, i, i, i, i, P, i, P], i),
         "ocean_raycast_device": ([P, i, i, i, i, P, i, P], i),
         "ocean_raycast_async": ([P, i, i, i, i, P, i, P, ctypes.POINTER(P)], i),
+        "ocean_body_dynamics": ([P, i, i, i, i, P, i, P, P, i, P], i),
+        "ocean_body_dynamics_device": ([P, i, i, i, i, P, i, P, P, i, P], i),
+        "ocean_body_dynamics_async": ([P, i, i, i, i, P, i, P, P, i, P, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -500,6 +506,50 @@ class OceanContext:
         vp = ctypes.c_void_p
         _check(self.lib.ocean_body_buoyancy_device(self._h, tile, mode, iterations, vp(hull_ptr), probes, vp(bodies_ptr),
                                                    count, vp(out_ptr)), "ocean_body_buoyancy_device")
+
+    @staticmethod
+    def _motion_arg(motion, count: int) -> np.ndarray:
+        m = np.ascontiguousarray(motion, np.float32)
+        if m.ndim != 2 or m.shape != (count, 6):
+            raise ValueError(f"motion must be float32[M][6] = (velocity, angular velocity) for M = {count}, got {m.shape}")
+        return m
+
+    def body_dynamics(self, hull, bodies, motion, iterations: int = 4, mode: int = QUERY_SURFACE,
+                      law: int = DRAG_LINEAR, tile: int = 0) -> np.ndarray:
+        """Buoyancy and drag against the water's velocity on the device (ocean.h ocean_body_dynamics; F_VELOCITY
+        contexts), blocking: hull and bodies as body_buoyancy, motion float[M][6] = (world linear velocity of the
+        body origin, world angular velocity) -> float32[M][16]: body_buoyancy's record, then (sum F xyz, sum T xyz
+        about the origin, largest relative speed over the wet probes, number of wet probes) with F = g u
+        (DRAG_LINEAR) or g |u| u (DRAG_QUADRATIC) per probe, u = water - hull velocity, g the submerged volume.
+        The drag force is k out[8:11] and its torque k out[11:14] for the host's coefficient k."""
+        h, b = self._body_args(hull, bodies)
+        m = self._motion_arg(motion, b.shape[0])
+        out = np.empty((b.shape[0], 16), np.float32)
+        _check(self.lib.ocean_body_dynamics(self._h, tile, mode, iterations, law, h.ctypes.data, h.shape[0], b.ctypes.data,
+                                            m.ctypes.data, b.shape[0], out.ctypes.data), "ocean_body_dynamics")
+        return out
+
+    def body_dynamics_async(self, hull, bodies, motion, iterations: int = 4, mode: int = QUERY_SURFACE,
+                            law: int = DRAG_LINEAR, tile: int = 0, buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_body_dynamics_async), as body_buoyancy_async: float32[M][16] lands in pinned
+        host memory; `hull`, `bodies` and `motion` are consumed by the call.  `buf`: a caller-owned pinned slot of
+        at least M x 64 B."""
+        h, b = self._body_args(hull, bodies)
+        m = self._motion_arg(motion, b.shape[0])
+        return Readback(self, (b.shape[0], 16), b.shape[0] * 64, "ocean_body_dynamics_async",
+                        lambda dst, req: self.lib.ocean_body_dynamics_async(self._h, tile, mode, iterations, law,
+                                                                            h.ctypes.data, h.shape[0], b.ctypes.data,
+                                                                            m.ctypes.data, b.shape[0], dst, req), buf)
+
+    def body_dynamics_device(self, hull_ptr: int, probes: int, bodies_ptr: int, motion_ptr: int, count: int, out_ptr: int,
+                             iterations: int = 4, mode: int = QUERY_SURFACE, law: int = DRAG_LINEAR, tile: int = 0) -> None:
+        """The device-pointer form (ocean_body_dynamics_device): hull float[probes][5], bodies float[count][10],
+        motion float[count][6] and out float[count][16] live on this context's device (inputs 4-B, out 16-B
+        aligned); async on the context's stream, after the queued steps."""
+        vp = ctypes.c_void_p
+        _check(self.lib.ocean_body_dynamics_device(self._h, tile, mode, iterations, law, vp(hull_ptr), probes,
+                                                   vp(bodies_ptr), vp(motion_ptr), count, vp(out_ptr)),
+               "ocean_body_dynamics_device")
 
     @staticmethod
     def box_hull(nx: int, nz: int, ny: int = 1) -> np.ndarray:
@@ -958,6 +1008,13 @@ class WaterBody:
         """BuoyantObject.FixedUpdate's lookup for M bodies of P probes each (OceanContext.body_buoyancy): the
         displaced volume, where it acts and the water plane under every hull, float32[M][8]."""
         return self.ctx.body_buoyancy(hull, bodies, iterations, mode, tile)
+
+    def Dynamics(self, hull, bodies, motion, iterations: int = 4, mode: int = QUERY_SURFACE, law: int = DRAG_LINEAR,
+                 tile: int = 0) -> np.ndarray:
+        """Buoyancy's records with the drag against the water's own velocity beside them, float32[M][16]
+        (OceanContext.body_dynamics; `velocity=True`).  The reference drags against still water
+        (BuoyantObject.FixedUpdate: -rb.velocity * drag)."""
+        return self.ctx.body_dynamics(hull, bodies, motion, iterations, mode, law, tile)
 
     def GetWaterVelocity(self, worldPosition, iterations: int = 4, tile: int = 0) -> np.ndarray:
         """The velocity (x, y, z) of the water particle on the surface above worldPosition (x and z are used, as

@@ -16,6 +16,10 @@ figure is its mean per launch, the reported figure the median over the rounds, t
 rounds.  B is "no slower" when its median does not exceed A's by more than A's spread.  Also: the round trip
 of the largest request, 8192 bodies of 64 probes, through ocean_body_buoyancy_async (call to landed data, wall
 clock, and the copy's own time from ocean_readback_copy_ms).
+The dynamics line (ocean_body_dynamics_device, k_body_dynamics) runs on a second context with OCEAN_F_VELOCITY over
+the same bodies and hulls, with random motions: D is the dynamics kernel, and against it stands what a host issues
+today for the same numbers, B + V in the same run: the body kernel and ocean_query_velocity_device over the same
+M x P probe positions (before the host's own transform and its reduction of M x P x 32 B).
 Prints one JSON line; --markdown appends the tables of docs/MEASUREMENTS.md.  A record, not a gate."""
 import argparse
 import ctypes
@@ -124,6 +128,55 @@ def kernel_table(ctx, launches, rounds):
     return table
 
 
+def dynamics_table(ctx, launches, rounds):
+    """D = ocean_body_dynamics_device against B + V = ocean_body_buoyancy_device + ocean_query_velocity_device over
+    the same probe positions, on a velocity context: alternating rounds B, V, D."""
+    dev = torch.device("cuda", ctx.device)
+    rng = np.random.default_rng(20251121)
+    bodies = random_bodies(rng, BODIES)
+    motion = np.concatenate([rng.uniform(-2.0, 2.0, (BODIES, 3)), rng.uniform(-1.0, 1.0, (BODIES, 3))], axis=1).astype(f32)
+    d_bodies, d_motion = torch.from_numpy(bodies).to(dev), torch.from_numpy(motion).to(dev)
+    out_b = torch.empty(BODIES * 8, dtype=torch.float32, device=dev)
+    out_d = torch.empty(BODIES * 16, dtype=torch.float32, device=dev)
+    table = []
+    for p, (nx, nz) in HULLS:
+        hull = oh.OceanContext.box_hull(nx, nz)
+        q = probe_positions(hull, bodies)
+        m = len(q)
+        d_hull, d_q = torch.from_numpy(hull).to(dev), torch.from_numpy(q).to(dev)
+        out_v = torch.empty(m * 8, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        variants = (
+            ("B", lambda: ctx.lib.ocean_body_buoyancy_device(ctx._h, 0, oh.QUERY_SURFACE, K, vp(d_hull.data_ptr()), p,
+                                                             vp(d_bodies.data_ptr()), BODIES, vp(out_b.data_ptr()))),
+            ("V", lambda: ctx.lib.ocean_query_velocity_device(ctx._h, 0, K, vp(d_q.data_ptr()), m, vp(out_v.data_ptr()))),
+            ("D", lambda: ctx.lib.ocean_body_dynamics_device(ctx._h, 0, oh.QUERY_SURFACE, K, oh.DRAG_QUADRATIC,
+                                                             vp(d_hull.data_ptr()), p, vp(d_bodies.data_ptr()),
+                                                             vp(d_motion.data_ptr()), BODIES, vp(out_d.data_ptr()))),
+        )
+        for _, fn in variants:  # warm-up
+            run(ctx, fn, launches)
+        torch.cuda.synchronize()
+        assert torch.equal(out_d.view(BODIES, 16)[:, :8], out_b.view(BODIES, 8)), p  # the same buoyancy record
+        times, symbols = {"B": [], "V": [], "D": []}, {}
+        for _ in range(rounds):  # alternating rounds
+            for label, fn in variants:
+                us, symbols[label] = run(ctx, fn, launches)
+                times[label].append(us)
+        rec = {"probes": p, "bodies": BODIES, "samples": m, "launches_per_round": launches}
+        for label in times:
+            rec[label] = summarize(times[label])
+            rec[label]["symbol"] = symbols[label]
+        both = [b + v for b, v in zip(times["B"], times["V"])]
+        rec["B_plus_V"] = summarize(both)
+        d = rec["D"]
+        d["below_B_plus_V"] = d["median_us"] < rec["B_plus_V"]["median_us"]
+        d["ratio_BV_over_D"] = round(rec["B_plus_V"]["median_us"] / d["median_us"], 3)
+        d["ratio_D_over_B"] = round(d["median_us"] / rec["B"]["median_us"], 3)
+        table.append(rec)
+    return table
+
+
 def async_round_trip(ctx, repeats=20):
     """8192 bodies of 64 probes through ocean_body_buoyancy_async: 320 KiB of bodies and 1.25 KiB of hull up,
     256 KiB down; wall clock from the call to the landed copy, and the copy's own time."""
@@ -155,6 +208,15 @@ def markdown(res):
         a, b = rec["A"], rec["B"]
         lines.append(f"| {rec['probes']} | {rec['samples']} | {a['median_us']:.1f} ± {a['spread_us']:.1f} | "
                      f"{b['median_us']:.1f} ± {b['spread_us']:.1f} | {b['ratio_A_over_B']} | {b['no_slower_than_A']} |")
+    if "dynamics" in res:
+        lines += ["", "| P | samples | B body kernel (us) | V velocity query (us) | B + V (us) | D dynamics kernel (us) | "
+                  "(B + V) / D | D / B | D below B + V |", "|---|---|---|---|---|---|---|---|---|"]
+        for rec in res["dynamics"]:
+            b, v, s, d = rec["B"], rec["V"], rec["B_plus_V"], rec["D"]
+            lines.append(f"| {rec['probes']} | {rec['samples']} | {b['median_us']:.1f} ± {b['spread_us']:.1f} | "
+                         f"{v['median_us']:.1f} ± {v['spread_us']:.1f} | {s['median_us']:.1f} ± {s['spread_us']:.1f} | "
+                         f"{d['median_us']:.1f} ± {d['spread_us']:.1f} | {d['ratio_BV_over_D']} | {d['ratio_D_over_B']} | "
+                         f"{d['below_B_plus_V']} |")
     r = res["async_8192x64"]
     lines += ["", "| 8192 x 64 async | bytes up / down | round trip median / min (us) | copy median (us) |", "|---|---|---|---|",
               f"| K = {K} | {r['bytes_up']} / {r['bytes_down']} | {r['round_trip_us_median']} / {r['round_trip_us_min']} | "
@@ -181,6 +243,14 @@ def main():
                "async_8192x64": async_round_trip(wb.ctx)}
     finally:
         wb.OnDisable()
+    wv = oh.scene_water_body(n=N, n_cascades=CASCADES, seed=20251121, mips=False, readback="height", velocity=True).Awake()
+    wv.ctx.step(0.5)
+    wv.ctx.step(1.0)
+    wv.ctx.synchronize()
+    try:
+        res["dynamics"] = dynamics_table(wv.ctx, launches, rounds)
+    finally:
+        wv.OnDisable()
     print(json.dumps(res))
     if args.markdown:
         print(markdown(res))
