@@ -281,17 +281,6 @@ __global__ __launch_bounds__(W * (N / 2) / kElems) void k_colsf_ip(float2* plane
 }
 
 // --------------------------------------------------------------- launch
-// group > 1 (XCD-grouped column launches): a multiple of `group` workgroups, so that the pieces of a tile sit on
-// blocks b, b + 8, ... at every step of the item loop (their items are a multiple of it too).  That placement
-// is speed only (k_cols2), so the OCEAN_MAX_GROUPS cap applies after it and need not keep it.
-template <class K>
-int persistent_grid(K kernel, int threads, int items, int max_groups, int group = 1) {
-    int g = device_cus() * resident_per_cu((const void*)kernel, threads);
-    if (items < g) g = items;
-    g -= g % group;
-    return capped_grid(g, max_groups);
-}
-
 template <template <int> class F, class... A>
 hipError_t dispatch_n(int n, A... a) {
     switch (n) {
@@ -317,9 +306,7 @@ struct Rows2 {
         constexpr int T = B * N / kElems;
         const int total = ups * N;
         const int items = (total + B - 1) / B;
-        const int g = persistent_grid(k_rows2<N, B>, T, items, v->max_groups);
-        launch((k_rows2<N, B>), dim3(g), dim3(T), 0, s, (const float2*)base, base, total, v->tw);
-        return hipGetLastError();
+        return launch_items(k_rows2<N, B>, T, {items, v->max_groups}, s, (const float2*)base, base, total, v->tw);
     }
     static hipError_t go(const DevView* v, float2* base, int ups, hipStream_t s) {
         return go_b<rows_per_item(N)>(v, base, ups, s);
@@ -331,9 +318,7 @@ struct Cols2 {
     static hipError_t go_w(const DevView* v, float2* base, int ups, hipStream_t s) {
         constexpr int T = W * N / kElems;
         const int items = ups * (N / W);
-        const int g = persistent_grid(k_cols2<N, W, G>, T, items, v->max_groups, G > 1 ? 8 * G : 1);
-        launch((k_cols2<N, W, G>), dim3(g), dim3(T), 0, s, base, items, v->tw);
-        return hipGetLastError();
+        return launch_items(k_cols2<N, W, G>, T, {items, v->max_groups, G > 1 ? 8 * G : 1}, s, base, items, v->tw);
     }
     static hipError_t go(const DevView* v, float2* base, int ups, hipStream_t s) {
         // 8-column halves paired on one XCD at N = 1024 (45.6 against 49.7 us for 4 x 1024^2 x 4 planes
@@ -353,15 +338,11 @@ struct OpFold {
         if (part == 0) {
             constexpr int T = N / kElems;
             const int items = ups * (N / F);
-            const int g = persistent_grid(k_rowsf<N>, T, items, v->max_groups);
-            launch((k_rowsf<N>), dim3(g), dim3(T), 0, s, planes, items, v->tw);
-        } else {
-            constexpr int T = W * (N / F) / kElems;
-            const int items = ups * (N / W);
-            const int g = persistent_grid(k_colsf_ip<N, W, G>, T, items, v->max_groups, 8 * G);
-            launch((k_colsf_ip<N, W, G>), dim3(g), dim3(T), 0, s, planes, items, v->tw);
+            return launch_items(k_rowsf<N>, T, {items, v->max_groups}, s, planes, items, v->tw);
         }
-        return hipGetLastError();
+        constexpr int T = W * (N / F) / kElems;
+        const int items = ups * (N / W);
+        return launch_items(k_colsf_ip<N, W, G>, T, {items, v->max_groups, 8 * G}, s, planes, items, v->tw);
     }
 };
 

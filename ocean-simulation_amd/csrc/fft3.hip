@@ -701,12 +701,6 @@ __global__ __launch_bounds__(N / 2) void k_pass_a8(DevView v, float time, int it
     }
 }
 
-template <class K>
-int grid3(K kernel, int threads, int items, int max_groups) {
-    const int g = device_cus() * resident_per_cu((const void*)kernel, threads);
-    return capped_grid(items < g ? items : g, max_groups);
-}
-
 // EPF at N = 4096: the next row's h0 in flight across the stages (641 against 658 us, docs/MEASUREMENTS.md)
 template <int N, int P, int RS, bool PF, bool BAND = false, int WT = 0>
 hipError_t go_a3k(const DevView& v, float t, hipStream_t s) {
@@ -721,9 +715,7 @@ hipError_t go_a3k(const DevView& v, float t, hipStream_t s) {
     const int total = v.units * N;
     const int items = (total + RB - 1) / RB;
     constexpr bool EPF = (N == 4096);
-    const int g = grid3(k_pass_a3<N, P, RS, PF, BAND, WT, EPF>, T, items, v.max_groups);
-    launch((k_pass_a3<N, P, RS, PF, BAND, WT, EPF>), dim3(g), dim3(T), 0, s, v, t, total);
-    return hipGetLastError();
+    return launch_items(k_pass_a3<N, P, RS, PF, BAND, WT, EPF>, T, {items, v.max_groups}, s, v, t, total);
 }
 
 // N = 1024, 4 planes: 2 rows per workgroup (512 lanes) with the next item's h0
@@ -742,9 +734,7 @@ hipError_t go_b3k(const DevView& v, hipStream_t s) {
     constexpr int W = WT ? WT : b3_w(N);
     constexpr int T = W * N / kElems;
     const int items = v.units * (v.nx / W);
-    const int g = grid3(k_pass_b3<N, P, PFD, WT>, T, items, v.max_groups);
-    launch((k_pass_b3<N, P, PFD, WT>), dim3(g), dim3(T), 0, s, v, items);
-    return hipGetLastError();
+    return launch_items(k_pass_b3<N, P, PFD, WT>, T, {items, v.max_groups}, s, v, items);
 }
 
 // narrow (4-column) tiles only: two images of a wide tile exceed the CU's LDS
@@ -753,9 +743,7 @@ hipError_t go_b2d(const DevView& v, hipStream_t s) {
     constexpr int W = 4;
     constexpr int T = 2 * W * N / kElems;
     const int items = v.units * (v.nx / W);
-    const int g = grid3(k_pass_b2d<N, W>, T, items, v.max_groups);
-    launch((k_pass_b2d<N, W>), dim3(g), dim3(T), 0, s, v, items);
-    return hipGetLastError();
+    return launch_items(k_pass_b2d<N, W>, T, {items, v.max_groups}, s, v, items);
 }
 
 template <int N>
@@ -763,9 +751,7 @@ hipError_t go_b8(const DevView& v, hipStream_t s) {
     constexpr int W = 4;
     constexpr int T = 2 * W * N / 8;
     const int items = v.units * (v.nx / W);
-    const int g = grid3(k_pass_b8<N, W>, T, items, v.max_groups);
-    launch((k_pass_b8<N, W>), dim3(g), dim3(T), 0, s, v, items);
-    return hipGetLastError();
+    return launch_items(k_pass_b8<N, W>, T, {items, v.max_groups}, s, v, items);
 }
 
 // Two planes in flight at N = 1024 (one workgroup per CU, registers to spare).  Displacement-only
@@ -794,9 +780,7 @@ hipError_t go_a4(const DevView& v, float t, hipStream_t s) {
     constexpr int T = N / 4;
     const int ipu = N / 2;
     const int items = v.units * ipu;
-    const int g = grid3(k_pass_a4<N, BAND, WT, P>, T, items, v.max_groups);
-    launch((k_pass_a4<N, BAND, WT, P>), dim3(g), dim3(T), 0, s, v, t, ipu, items);
-    return hipGetLastError();
+    return launch_items(k_pass_a4<N, BAND, WT, P>, T, {items, v.max_groups}, s, v, t, ipu, items);
 }
 
 template <int N, int WT>
@@ -804,18 +788,10 @@ hipError_t go_a8(const DevView& v, float t, hipStream_t s) {
     constexpr int T = N / 2;
     const int ipu = N / 2;
     const int items = v.units * ipu;
-    const int g = grid3(k_pass_a8<N, WT>, T, items, v.max_groups);
-    launch((k_pass_a8<N, WT>), dim3(g), dim3(T), 0, s, v, t, ipu, items);
-    return hipGetLastError();
+    return launch_items(k_pass_a8<N, WT>, T, {items, v.max_groups}, s, v, t, ipu, items);
 }
 
 }  // namespace
-
-// N = 512 / 1024 with four planes; N = 256 / 512 displacement-only (two planes)
-bool pass_a4_supported(int n, int planes) {
-    if (planes == 2) return n == 256 || n == 512;
-    return planes == 4 && (n == 512 || n == 1024);
-}
 
 // P = 2 at N = 512: pass A8 (256 lanes, 8 values each; 6.64 against 7.47 us for pass A4's two-plane
 // layout at cfg2, docs/MEASUREMENTS.md section 6)

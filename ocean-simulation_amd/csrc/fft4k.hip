@@ -226,37 +226,23 @@ __global__ __launch_bounds__(kSeq * kL1 / kElems) void k_col4s2(DevView v, int i
     }
 }
 
-template <class K>
-int grid4(K kernel, int threads, int items, int max_groups, int max_per_cu = 0) {
-    int per_cu = resident_per_cu((const void*)kernel, threads);
-    if (max_per_cu > 0 && per_cu > max_per_cu) per_cu = max_per_cu;
-    const int g = device_cus() * per_cu;
-    return capped_grid(items < g ? items : g, max_groups);
-}
-
 template <int N, bool Q = false>
 hipError_t go_c1(const DevView& v, hipStream_t s) {
     constexpr int T = kSeq * (N / kL1) / kElems;
     const int items = (Q ? 3 : v.planes) * v.units * (v.nx / kWT) * (kL1 / (kSeq / kWT));
     // two workgroups per CU, not the four that fit: cfg5 column passes 1.72 -> 1.67 ms
     // (three per CU: 1.70 ms), docs/MEASUREMENTS.md section 3
-    const int g = grid4(k_col4s1<N, Q>, T, items, v.max_groups, 2);
-    launch((k_col4s1<N, Q>), dim3(g), dim3(T), 0, s, v, items);
-    return hipGetLastError();
+    return launch_items(k_col4s1<N, Q>, T, {items, v.max_groups, 1, 2}, s, v, items);
 }
 
 template <int N, int P, bool Q = false>
 hipError_t go_c2(const DevView& v, hipStream_t s) {
     constexpr int T = kSeq * kL1 / kElems;
     const int items = v.units * (v.nx / kWT) * ((N / kL1) / (kSeq / kWT));
-    const int g = grid4(k_col4s2<N, P, Q>, T, items, v.max_groups);
-    launch((k_col4s2<N, P, Q>), dim3(g), dim3(T), 0, s, v, items);
-    return hipGetLastError();
+    return launch_items(k_col4s2<N, P, Q>, T, {items, v.max_groups}, s, v, items);
 }
 
 }  // namespace
-
-bool pass_c4_supported(int n) { return n == 2048 || n == 4096; }
 
 hipError_t launch_pass_c4q(const DevView& v, hipStream_t s) {
     if (v.planes != 4 || !v.qside) return hipErrorInvalidValue;

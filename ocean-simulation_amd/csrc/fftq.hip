@@ -776,12 +776,6 @@ __global__ __launch_bounds__((WT ? WT : b3_w(N)) * N / kElems) void k_pass_bq(De
     }
 }
 
-template <class K>
-int grid_q(K kernel, int threads, int items, int max_groups) {
-    const int g = device_cus() * resident_per_cu((const void*)kernel, threads);
-    return capped_grid(items < g ? items : g, max_groups);
-}
-
 // Byte offsets of a store into the chunk's intermediate planes 0..2 fit 32 bits (k_pass_aq /
 // k_pass_a3pp OFF32): the last byte of plane 2 lies below 4 GiB from the base.
 bool inter_off32(const DevView& v) { return ((size_t)2 * v.inter_stride + v.inter_stride) * 8 <= ((size_t)1 << 32); }
@@ -805,14 +799,12 @@ hipError_t go_aq(const DevView& v, float t, hipStream_t s, const PruneView* pv) 
         if (pv->items <= 0) return hipErrorInvalidValue;  // the caller launches nothing for an empty chunk
         // min(items, resident slots), as the dense launch: the balanced grid ceil(items / rounds) measured
         // 5.6 % slower at cfg3 (532 workgroups against 768; docs/MEASUREMENTS.md section 13)
-        const int g = grid_q(k_pass_aq<N, BAND, WT, OFF32, true>, T, pv->items, v.max_groups);
-        launch((k_pass_aq<N, BAND, WT, OFF32, true>), dim3(g), dim3(T), 0, s, v, t, pv->items, AqTable<true>{pv->tab, pv->ubase});
+        return launch_items(k_pass_aq<N, BAND, WT, OFF32, true>, T, {pv->items, v.max_groups}, s, v, t, pv->items,
+                            AqTable<true>{pv->tab, pv->ubase});
     } else {
         const int items = v.units * (N / 2 + 1);
-        const int g = grid_q(k_pass_aq<N, BAND, WT, OFF32>, T, items, v.max_groups);
-        launch((k_pass_aq<N, BAND, WT, OFF32>), dim3(g), dim3(T), 0, s, v, t, items, AqTable<false>{});
+        return launch_items(k_pass_aq<N, BAND, WT, OFF32>, T, {items, v.max_groups}, s, v, t, items, AqTable<false>{});
     }
-    return hipGetLastError();
 }
 
 template <int N, bool BAND = false>
@@ -822,9 +814,7 @@ hipError_t go_a3q(const DevView& v, float t, hipStream_t s) {
     }
     constexpr int T = N / 4;
     const int total = v.units * N;
-    const int g = grid_q(k_pass_a3q<N, BAND>, T, total, v.max_groups);
-    launch((k_pass_a3q<N, BAND>), dim3(g), dim3(T), 0, s, v, t, total);
-    return hipGetLastError();
+    return launch_items(k_pass_a3q<N, BAND>, T, {total, v.max_groups}, s, v, t, total);
 }
 
 template <int N, bool BAND = false, int WT = 0, bool DC = false, bool PRUNE = false>
@@ -844,18 +834,12 @@ hipError_t go_bq(const DevView& v, hipStream_t s, const PruneView* pv) {
     constexpr int W = WT ? WT : b3_w(N);
     constexpr int T = W * N / kElems;
     const int items = v.units * (v.nx / W);
-    const int g = grid_q(k_pass_bq<N, BAND, WT, DC, PRUNE>, T, items, v.max_groups);
     BqExtents<PRUNE> pe;
     if constexpr (PRUNE) pe.ext = pv->ext;
-    launch((k_pass_bq<N, BAND, WT, DC, PRUNE>), dim3(g), dim3(T), 0, s, v, items, pe);
-    return hipGetLastError();
+    return launch_items(k_pass_bq<N, BAND, WT, DC, PRUNE>, T, {items, v.max_groups}, s, v, items, pe);
 }
 
 }  // namespace
-
-// N = 2048 keeps the four-plane passes: pass A3Q's idle fourth sequence slot costs more there
-// than the column passes save (4 x 2048^2: 612 against 599 us per frame; docs/MEASUREMENTS.md section 3).
-bool pass_q_supported(int n, int planes) { return planes == 4 && (n == 512 || n == 1024 || n == 4096); }
 
 hipError_t launch_pass_a_q(const DevView& v, float t, hipStream_t s, const PruneView* pv) {
     if (!pass_q_supported(v.n, v.planes) || !v.qside) return hipErrorInvalidValue;
@@ -864,14 +848,8 @@ hipError_t launch_pass_a_q(const DevView& v, float t, hipStream_t s, const Prune
         if (v.n != 4096 || v.x0 != 0 || v.nx != v.n / 2 || !v.h0k) return hipErrorInvalidValue;
         constexpr int T = 4096 / 4;
         const int items = v.units * (4096 / 2 + 1);
-        if (inter_off32(v)) {
-            const int g = grid_q(k_pass_a3pp<4096, true>, T, items, v.max_groups);
-            launch((k_pass_a3pp<4096, true>), dim3(g), dim3(T), 0, s, v, t, items);
-        } else {
-            const int g = grid_q(k_pass_a3pp<4096, false>, T, items, v.max_groups);
-            launch((k_pass_a3pp<4096, false>), dim3(g), dim3(T), 0, s, v, t, items);
-        }
-        return hipGetLastError();
+        if (inter_off32(v)) return launch_items(k_pass_a3pp<4096, true>, T, {items, v.max_groups}, s, v, t, items);
+        return launch_items(k_pass_a3pp<4096, false>, T, {items, v.max_groups}, s, v, t, items);
     }
     switch (v.n) {
         case 512: return v.h0k ? go_aq<512>(v, t, s, pv) : hipErrorInvalidValue;

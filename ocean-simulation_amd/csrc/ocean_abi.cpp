@@ -19,8 +19,8 @@
 
 #include "fft_core.h"
 #include "device_scope.h"
+#include "frame_plan.h"
 #include "ocean_internal.h"
-#include "prune_items.h"
 
 namespace {
 
@@ -289,6 +289,13 @@ struct ocean_ctx {
     size_t texels() const { return (size_t)n * n; }
     size_t units() const { return (size_t)T * C; }
 
+    // what the frame schedule reads of a context (frame_plan.h)
+    ocean::FrameInputs frame_inputs() const {
+        return {{n, C, T, P, inter_units, band_x0, band_nx, col_par},
+                {opt.q, opt.a4, opt.chunk_mib, opt.c4_bands, opt.disp_cached},
+                {h0k != nullptr, qside != nullptr, h0k_valid, h0_conj, prune_ready, &prune}};
+    }
+
     ocean::DevView view() const {
         ocean::DevView v{};
         v.n = n;
@@ -480,12 +487,6 @@ void free_all(ocean_ctx* c) {
 
 }  // namespace
 
-namespace {
-int chunk_units(const ocean_ctx* ctx, int planes);
-// intermediate planes of the three-plane frame: Q1..Q3, plus the four-step column passes' R[Q4]
-int q_planes(const ocean_ctx* ctx) { return ctx->n >= 2048 ? 4 : 3; }
-}  // namespace
-
 extern "C" {
 
 const char* ocean_last_error(void) { return g_last_error.c_str(); }
@@ -564,13 +565,11 @@ int ocean_create(int device, int n, int n_cascades, int n_tiles, uint32_t flags,
         ok = ok && alloc((void**)&c->turb, tex * U * 16);
         ok = ok && alloc((void**)&c->foam, tex * U * 4);
     }
-    // the intermediate holds a chunk of either schedule: P planes, or (three-plane frame) planes
-    // Q1..Q3 plus the per-unit side arrays in the fourth plane's room (fftq.hip)
-    c->inter_units = (size_t)std::max(chunk_units(c, c->P),
-                                      ocean::pass_q_supported(n, c->P) ? chunk_units(c, q_planes(c)) : 1);
+    // the intermediate holds a chunk of either schedule (frame_plan.h)
+    c->inter_units = ocean::inter_units(c->frame_inputs());
     ok = ok && alloc((void**)&c->tplane, tex * c->inter_units * 8 * c->P);
     if (ocean::pass_q_supported(n, c->P)) ok = ok && alloc((void**)&c->qside, c->inter_units * 2 * n * 8);
-    if (c->opt.prune && c->qside && c->h0k && n <= 1024 && U < (size_t)ocean::kPruneMaxUnits)
+    if (c->opt.prune && ocean::prune_tables(c->frame_inputs()))
         ok = ok && alloc((void**)&c->prune_dev, (U + U * (n / 2 + 1)) * sizeof(int));
     if (flags & OCEAN_F_NORMALS) ok = ok && alloc((void**)&c->normal, tex * U * 16);
     if (flags & OCEAN_F_MIPS) {
@@ -759,41 +758,26 @@ namespace {
 // kind `kind_rows`, its column launches as `kind_cols`.
 int ifft_unit_planes(ocean_ctx* ctx, const ocean::DevView& v, float2* base0, int ups, int kind_rows, int kind_cols) {
     const size_t up_elems = ctx->texels();  // one unit-plane
-    if (ctx->n == 4096) {
-        // Folded columns, in place (fft2.hip k_rowsf / k_colsf_ip): per chunk of unit-planes, rows +
-        // the decimation-in-frequency fold onto the planes' own rows (z_b at rows b L + n), then
-        // 2048-point column tiles of both sub-planes per item, back into the planes, permuted.  A chunk
-        // of at most OCEAN_OP_CHUNK_MIB stays in the Infinity Cache between the two launches (auto 256
-        // MiB: two unit-planes; docs/MEASUREMENTS.md section 8).
-        const long mib = ctx->opt.op_chunk_mib > 0 ? ctx->opt.op_chunk_mib : 256;
-        const int k = (int)std::max<size_t>(1, ((size_t)mib << 20) / (up_elems * 8));
-        for (int c0 = 0; c0 < ups; c0 += k) {
-            const int kc = std::min(k, ups - c0);
-            float2* planes = base0 + (size_t)c0 * up_elems;
-            if (int r = timed(ctx, kind_rows, [&] { return ocean::launch_ifft_fold(v, planes, kc, 0, ctx->stream); },
-                              "ifft_rows"))
-                return r;
-            if (int r = timed(ctx, kind_cols, [&] { return ocean::launch_ifft_fold(v, planes, kc, 1, ctx->stream); },
-                              "ifft_cols"))
-                return r;
-        }
-        return OCEAN_OK;
-    }
     // In-place row and column launches per chunk of at most OCEAN_OP_CHUNK_MIB of unit-planes, so
     // the column launch re-reads the rows' output from the Infinity Cache when the plane set is
     // larger than it.  Auto: 256 MiB (4 x 4 x 1024^2 x 4 planes, 512 MiB, fresh data: 128 / 192 /
     // 256 / 320 / 384 MiB / unchunked 0.69 / 0.69 / 0.736 / 0.63 / 0.60 / 0.57 of peak; cfg3's 128
-    // MiB: one chunk).  At N = 1024 / 2048 the column launch takes XCD-paired halves of 16-column
-    // tiles (fft2.hip Cols2).
+    // MiB: one chunk; at N = 4096 two unit-planes, docs/MEASUREMENTS.md section 8).  At N = 1024 / 2048
+    // the column launch takes XCD-paired halves of 16-column tiles (fft2.hip Cols2).
+    // N = 4096: folded columns (fft2.hip k_rowsf / k_colsf_ip): rows + the decimation-in-frequency fold
+    // onto the planes' own rows (z_b at rows b L + n), then 2048-point column tiles of both sub-planes
+    // per item, back into the planes, permuted.
+    const bool fold = ctx->n == 4096;
+    const hipStream_t s = ctx->stream;
     const long mib = ctx->opt.op_chunk_mib > 0 ? ctx->opt.op_chunk_mib : 256;
     const int k = (int)std::max<size_t>(1, ((size_t)mib << 20) / (up_elems * 8));
     for (int c0 = 0; c0 < ups; c0 += k) {
         const int kc = std::min(k, ups - c0);
         float2* base = base0 + (size_t)c0 * up_elems;
-        if (int r = timed(ctx, kind_rows, [&] { return ocean::launch_ifft_rows_v2(v, base, kc, ctx->stream); }, "ifft_rows"))
-            return r;
-        if (int r = timed(ctx, kind_cols, [&] { return ocean::launch_ifft_cols_v2(v, base, kc, ctx->stream); }, "ifft_cols"))
-            return r;
+        auto rows = [&] { return fold ? ocean::launch_ifft_fold(v, base, kc, 0, s) : ocean::launch_ifft_rows_v2(v, base, kc, s); };
+        auto cols = [&] { return fold ? ocean::launch_ifft_fold(v, base, kc, 1, s) : ocean::launch_ifft_cols_v2(v, base, kc, s); };
+        if (int r = timed(ctx, kind_rows, rows, "ifft_rows")) return r;
+        if (int r = timed(ctx, kind_cols, cols, "ifft_cols")) return r;
     }
     return OCEAN_OK;
 }
@@ -828,7 +812,6 @@ int ocean_fill(ocean_ctx* ctx) {
 
 namespace {
 int step_fused(ocean_ctx* ctx, float time);
-bool use_q(const ocean_ctx* ctx);
 
 // GenerateMips (WaterBody.cs:191-192) when the context has mip chains.
 int generate_mips(ocean_ctx* ctx) {
@@ -869,8 +852,9 @@ int ocean_step(ocean_ctx* ctx, float time) {
 }
 
 namespace {
-// View of units [u0, u0 + nu) (unit u of the view is cascade (c0 + u) % C).
-ocean::DevView sub_view(const ocean::DevView& v, int u0, int nu, bool inter_at_base = false) {
+// View of units [u0, u0 + nu) (unit u of the view is cascade (c0 + u) % C), whose intermediate and side arrays
+// start at unit slot inter_u0 (FrameStep::inter_u0).
+ocean::DevView sub_view(const ocean::DevView& v, int u0, int nu, int inter_u0) {
     ocean::DevView s = v;
     const size_t off = (size_t)u0 * v.n * v.n;
     s.units = nu;
@@ -878,11 +862,10 @@ ocean::DevView sub_view(const ocean::DevView& v, int u0, int nu, bool inter_at_b
     s.h0 = v.h0 + off;
     s.waves = v.waves + off;
     if (v.h0k) s.h0k = v.h0k + off;
-    // plane_stride unchanged: planes stay U * N * N apart.  inter_at_base: the chunk's
-    // intermediate starts at the base of every plane (one region reused by every chunk)
-    s.tplane = inter_at_base ? v.tplane : v.tplane + off;
+    // plane_stride unchanged: planes stay U * N * N apart
+    s.tplane = v.tplane + (size_t)inter_u0 * v.n * v.n;
     if (v.foam) s.foam = v.foam + off;
-    if (v.qside) s.qside = inter_at_base ? v.qside : v.qside + (size_t)u0 * 2 * v.n;
+    if (v.qside) s.qside = v.qside + (size_t)inter_u0 * 2 * v.n;
     s.disp = v.disp + off;
     if (v.deriv) s.deriv = v.deriv + off;
     if (v.turb) s.turb = v.turb + off;
@@ -890,147 +873,36 @@ ocean::DevView sub_view(const ocean::DevView& v, int u0, int nu, bool inter_at_b
     return s;
 }
 
-// Units per chunk: a frame over many units runs pass A and pass B chunk by chunk so
-// that the intermediate pass B re-reads is still in the 256 MiB Infinity Cache
-// (OCEAN_CHUNK_MIB of intermediate per chunk, 0 = whole frame at once; a unit larger than a
-// chunk: whole frame).  Measured on cfg4's 1024 units at 512^2 (8 MiB each): 64 MiB 37.9k,
-// 128 MiB 40.7k, 192 MiB 43.1k, 256 MiB 38.4k, unchunked 40.7k tile-frames/s.
-int chunk_units(const ocean_ctx* ctx, int planes) {
-    const long mib = ctx->opt.chunk_mib;
-    const int U = (int)ctx->units();
-    if (mib <= 0) return U;
-    const size_t per_unit = ctx->texels() * 8 * planes;
-    int k = (int)(((size_t)mib << 20) / per_unit);
-    if (k >= ctx->C) k -= k % ctx->C;  // whole tiles when a chunk holds one
-    if (k < 1) return U;
-    return k >= U ? U : k;
-}
-
-// Column bands per unit for the N >= 2048 column passes: OCEAN_C4_BANDS, or by default
-// as many as keep one band's planes (P * N * width * 8 B) within 256 MiB -- cfg5's 512 MiB
-// units run as 2 bands: 387 -> 412-421 frames/s (3 or 4 bands: 417; per-unit pass A: slower).
-// Band widths stay multiples of the four-step tile width (16).
-int c4_bands(const ocean_ctx* ctx, int nx) {
-    if (!ocean::pass_c4_supported(ctx->n)) return 1;
-    int nb = ctx->opt.c4_bands;
-    if (nb <= 0) {
-        const size_t band_bytes = (size_t)ctx->P * ctx->n * nx * 8;
-        nb = 1;
-        while (band_bytes / nb > ((size_t)256 << 20)) nb *= 2;
-    }
-    while (nb > 1 && (nx % nb || (nx / nb) % 16)) --nb;
-    return nb;
-}
-
-// The three-plane fused frame (fftq.hip) runs where it applies: N = 512 / 1024 with full
-// outputs, the mirror-pair row pass's h0k valid.
-bool use_q(const ocean_ctx* ctx) {
-    if (!ctx->opt.q || !ctx->h0_conj || !ocean::pass_q_supported(ctx->n, ctx->P)) return false;
-    return ctx->n >= 2048 || (ctx->opt.a4 && ctx->h0k_valid);  // N <= 1024: the mirror-pair row pass reads h0k
-}
-
-// Pass BQ may write DISP with default-policy stores (DevView::disp_cached) when the whole frame is one chunk
-// and its cache-resident set plus DISP fits 224 MiB of the 256 MiB Infinity Cache of an MI355X: DISP then
-// waits there and is written back while the next pass A runs, when HBM has headroom.  The resident set is
-// what the three-plane frame re-reads each frame, per texel-cascade: pass AQ's h0k (8 B; the frame runs
-// only with the mirror-pair row pass, use_q), the intermediate Q1..Q3 (24 B) and the foam state (4 B).
-// cfg3 (4 x 1024^2, 208 MiB): 11.83-11.88 -> 12.08-12.11 k frames/s; a cfg4 chunk (32 units of 512^2,
-// 288 MiB) lost 7.5 % the same way, and DISP + TURB at cfg3 lost 7 % (docs/MEASUREMENTS.md section 8).
-// The 224 MiB budget is this part's; OCEAN_DISP_CACHED=0 / 1 overrides the choice (A/B, other parts).
-bool disp_fits_cache(const ocean_ctx* ctx, bool q, int chunk) {
-    if (!q || ctx->n > 1024 || chunk < (int)ctx->units()) return false;
-    if (ctx->opt.disp_cached >= 0) return ctx->opt.disp_cached != 0;
-    constexpr size_t kH0k = 8, kInter = 24, kFoam = 4, kDisp = 16;
-    const size_t bytes = ctx->texels() * ctx->units() * (kH0k + kInter + kFoam + kDisp);
-    return bytes <= ((size_t)224 << 20);
-}
-
+// One frame: the steps of its plan (frame_plan.h), each a view of its units and column band and one launch.
 int step_fused(ocean_ctx* ctx, float time) {
-    // pass A: mirror-pair rows (N = 512, 1024 with 4 planes and h0k valid) or per-texel
-    // rows; pass B: column tiles (N <= 1024) or the four-step column passes (N >= 2048)
     ocean::DevView v = ctx->view();
     if (!ctx->h0k_valid) v.h0k = nullptr;  // stale after an H0 upload: no row pass may read it
-    const bool q = use_q(ctx);
-    if (ctx->col_par >= 0 && !q)
+    const ocean::FrameInputs in = ctx->frame_inputs();
+    if (ctx->col_par >= 0 && !ocean::use_q(in))
         return fail(OCEAN_E_STATE, "a column parity needs the three-plane frame (h0 from ocean_init_spectrum)");
-    const int U = (int)ctx->units(), K = std::min(chunk_units(ctx, q ? q_planes(ctx) : ctx->P), (int)ctx->inter_units);
-    v.disp_cached = disp_fits_cache(ctx, q, K);
-    for (int u0 = 0; u0 < U; u0 += K) {
-        const ocean::DevView c = (K >= U) ? v : sub_view(v, u0, std::min(K, U - u0), ctx->inter_units < ctx->units());
-        if (q && ctx->n >= 2048) {
-            if (int r = timed(ctx, 0, [&] { return ocean::launch_pass_a_q(c, time, ctx->stream); }, "pass_a")) return r;
-            const int nb = c4_bands(ctx, c.nx);
-            if (nb == 1) {
-                if (int r = timed(ctx, 1, [&] { return ocean::launch_pass_c4q(c, ctx->stream); }, "pass_c")) return r;
-                continue;
+    const hipStream_t s = ctx->stream;
+    return ocean::plan_frame(in, [&](const ocean::FrameStep& st) {
+        ocean::DevView c = sub_view(v, st.u0, st.nu, st.inter_u0);
+        c.x0 = st.x0;
+        c.nx = st.nx;
+        c.disp_cached = st.disp_cached;
+        // band-limited cascades: the step's live items and the extents of its units
+        ocean::PruneView pv{};
+        if (st.pruned) pv = {ctx->prune_dev + ctx->units() + st.first, st.items, st.ubase, ctx->prune_dev + st.u0};
+        const ocean::PruneView* pp = st.pruned ? &pv : nullptr;
+        return timed(ctx, st.kind, [&] {
+            switch (st.pass) {
+                case ocean::FramePass::A_Q: return ocean::launch_pass_a_q(c, time, s, pp);
+                case ocean::FramePass::A_V4: return ocean::launch_pass_a_v4(c, time, s);
+                case ocean::FramePass::A_V3: return ocean::launch_pass_a_v3(c, time, s);
+                case ocean::FramePass::B_Q: return ocean::launch_pass_b_q(c, s, pp);
+                case ocean::FramePass::B_V3: return ocean::launch_pass_b_v3(c, s);
+                case ocean::FramePass::C4: return ocean::launch_pass_c4(c, s);
+                case ocean::FramePass::C4Q: return ocean::launch_pass_c4q(c, s);
             }
-            const int w = c.nx / nb;
-            for (int u = 0; u < c.units; ++u)
-                for (int b = 0; b < nb; ++b) {
-                    ocean::DevView cb = sub_view(c, u, 1);
-                    cb.x0 = c.x0 + b * w;
-                    cb.nx = (b == nb - 1) ? c.nx - b * w : w;
-                    if (int r = timed(ctx, 1, [&] { return ocean::launch_pass_c4q(cb, ctx->stream); }, "pass_c"))
-                        return r;
-                }
-            continue;
-        }
-        if (q) {
-            // band-limited cascades: the chunk's live items.  The pruned kernels measured 2.2 % of a frame
-            // slower than the dense ones where 1.8 % of the items are dead (a scene whose amplitudes underflow
-            // in a few outer rows) and 4.7-6.6 % faster where 22 % are (docs/MEASUREMENTS.md section 13); in
-            // between nothing is measured.  A chunk runs them when at least 1 / kPruneMinDeadShare of its items
-            // is dead, else (a fully dense context included) the dense kernels.  Both passes of a chunk take the
-            // same choice.  The choice is per chunk, so dense and pruned chunks may alternate over the same
-            // intermediate region: a dense pass AQ writes every row its pass BQ reads, and a pruned pass BQ reads
-            // no row its pass AQ did not write, so neither depends on what the other left there.
-            constexpr long kPruneMinDeadShare = 8;
-            ocean::PruneView pv{};
-            bool prune = ctx->prune_ready && !ctx->prune.dense && c.nx == ctx->n;
-            if (prune) {
-                int first = 0;
-                ctx->prune.chunk(u0, c.units, &first, &pv.items);
-                pv.tab = ctx->prune_dev + U + first;
-                pv.ubase = u0;
-                pv.ext = ctx->prune_dev + u0;
-                prune = (long)pv.items * kPruneMinDeadShare <= (long)c.units * (ctx->n / 2 + 1) * (kPruneMinDeadShare - 1);
-            }
-            const ocean::PruneView* pp = prune ? &pv : nullptr;
-            if (!prune || pv.items > 0)  // a chunk with no live item launches no pass A
-                if (int r = timed(ctx, 0, [&] { return ocean::launch_pass_a_q(c, time, ctx->stream, pp); }, "pass_a"))
-                    return r;
-            if (int r = timed(ctx, 1, [&] { return ocean::launch_pass_b_q(c, ctx->stream, pp); }, "pass_b")) return r;
-            continue;
-        }
-        if (int r = timed(ctx, 0, [&] {
-                // h0k also exists at 4096 (pass A3PP), where the mirror-pair pass A4 does not
-                if (ctx->opt.a4 && ctx->h0k_valid && ocean::pass_a4_supported(ctx->n, ctx->P))
-                    return ocean::launch_pass_a_v4(c, time, ctx->stream);
-                return ocean::launch_pass_a_v3(c, time, ctx->stream);
-            }, "pass_a"))
-            return r;
-        const int nb = c4_bands(ctx, c.nx);
-        if (nb > 1) {
-            // four-step column passes per (unit, column band): pass C2 re-reads what C1
-            // just wrote while it is still in the Infinity Cache (256 MiB)
-            const int w = c.nx / nb;
-            for (int u = 0; u < c.units; ++u)
-                for (int b = 0; b < nb; ++b) {
-                    ocean::DevView cb = sub_view(c, u, 1);
-                    cb.x0 = c.x0 + b * w;
-                    cb.nx = (b == nb - 1) ? c.nx - b * w : w;
-                    if (int r = timed(ctx, 1, [&] { return ocean::launch_pass_c4(cb, ctx->stream); }, "pass_c"))
-                        return r;
-                }
-            continue;
-        }
-        if (int r = timed(ctx, 1, [&] {
-                if (ocean::pass_c4_supported(ctx->n)) return ocean::launch_pass_c4(c, ctx->stream);
-                return ocean::launch_pass_b_v3(c, ctx->stream);
-            }, "pass_b"))
-            return r;
-    }
-    return OCEAN_OK;
+            return hipErrorInvalidValue;
+        }, st.name);
+    });
 }
 }  // namespace
 
@@ -2001,7 +1873,7 @@ int ocean_step_bytes(ocean_ctx* ctx, uint64_t* pass_a, uint64_t* pass_b) {
         const bool a4 = ctx->opt.a4 && ctx->h0k_valid && ocean::pass_a4_supported(ctx->n, ctx->P);
         // column band: h0 is read whole (rows are transformed whole), the rest scales with the band
         const uint64_t bt = tex / ctx->n * ctx->band_nx;
-        if (use_q(ctx)) {
+        if (ocean::use_q(ctx->frame_inputs())) {
             // three-plane frame (the side arrays, 16 B per row, not counted): pass A h0k (h0 at
             // N >= 2048) -> Q1..Q3; pass B Q1..Q3 + foam state -> outputs, or at N >= 2048 the
             // four-step passes: C1 reads Q1..Q3 and writes them with R[Q4], C2 reads four planes

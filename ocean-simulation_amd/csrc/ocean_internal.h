@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "frame_plan.h"  // pass_*_supported: which sizes each pass family is built for
 #include "ocean/ocean.h"
 
 namespace ocean {
@@ -64,7 +65,7 @@ struct DevView {
     float gravity;        // for the per-frame wave-data recompute (fused row pass)
     int tile_w;           // width W of the tile-major layouts below: inter_w(N), or 4 for small jobs
     float2* tplane;       // fused intermediate, P planes x [K][N/W][N][W] (tile-major), stride inter_stride;
-                          // K = the units of one chunk of a frame (ocean_abi.cpp chunk_units): every chunk
+                          // K = the units of one chunk of a frame (frame_plan.h chunk_units): every chunk
                           // reuses the same region, so its lines are rewritten in the Infinity Cache
                           // instead of being written back to HBM once per unit
     size_t inter_stride;  // elements between consecutive planes of tplane (K * N * N)
@@ -83,7 +84,7 @@ struct DevView {
     int xstr, xpar;
     // pass BQ writes DISP with default-policy stores instead of nontemporal ones: the slice stays in the
     // Infinity Cache and is written back while the next pass A runs, when HBM has headroom.  Set by the host
-    // where the frame's re-read set plus DISP fits the cache (ocean_abi.cpp disp_fits_cache).
+    // where the frame's re-read set plus DISP fits the cache (frame_plan.h disp_fits_cache).
     bool disp_cached;
 };
 
@@ -103,6 +104,24 @@ int device_cus();
 // positive.  Every persistent kernel walks item = blockIdx.x, += gridDim.x and no kernel synchronises across
 // workgroups, so any grid >= 1 computes the same texels; a small one makes every workgroup's loop iterate.
 inline int capped_grid(int g, int max_groups) { return max_groups > 0 && g > max_groups ? max_groups : g; }
+// The item loop of a persistent kernel and the grid that runs it: min(items, resident slots of the device),
+// where a CU holds what the kernel's occupancy allows or at most max_per_cu (> 0) workgroups.
+// group > 1 (XCD-grouped column launches, fft2.hip): a multiple of `group` workgroups, so that the pieces of a
+// tile sit on blocks b, b + 8, ... at every step of the item loop (their items are a multiple of it too).  That
+// placement is speed only (k_cols2), so the OCEAN_MAX_GROUPS cap applies after it and need not keep it.
+struct Items {
+    int count, max_groups, group = 1, max_per_cu = 0;
+};
+template <class F, class... Args>
+inline hipError_t launch_items(F kernel, int threads, Items it, hipStream_t s, const Args&... args) {
+    int per_cu = resident_per_cu((const void*)kernel, threads);
+    if (it.max_per_cu > 0 && per_cu > it.max_per_cu) per_cu = it.max_per_cu;
+    int g = device_cus() * per_cu;
+    if (it.count < g) g = it.count;
+    g -= g % it.group;
+    launch(kernel, dim3(capped_grid(g, it.max_groups)), dim3(threads), 0, s, args...);
+    return hipGetLastError();
+}
 
 hipError_t launch_init_spectrum(const DevView& v, const SpectrumParams& p, hipStream_t s);
 hipError_t launch_conjugate(const DevView& v, hipStream_t s);
@@ -180,18 +199,15 @@ hipError_t launch_surface_bounds(const DevView& v, int tile, float* partial, flo
 hipError_t launch_raycast(const DevView& v, int tile, int iterations, int steps, int refine, const float* bounds,
                           const float* rays, int count, float* out, hipStream_t s);
 
-// fft4k.hip (N = 2048, 4096): four-step column passes C1 (in place on the
+// fft4k.hip (N = 2048, 4096: pass_c4_supported): four-step column passes C1 (in place on the
 // 16-wide tile-major intermediate) + C2 (with the pass-B epilogue); replace pass B.
-bool pass_c4_supported(int n);
 hipError_t launch_pass_c4(const DevView& v, hipStream_t s);
 // Mirror-pair row pass (N = 512 / 1024, 4 planes): one item = rows y and N - y; the
-// texels k and -k share wave data and the phase factor and read h0 once (h0k).
-bool pass_a4_supported(int n, int planes);
+// texels k and -k share wave data and the phase factor and read h0 once (h0k).  Sizes: frame_plan.h pass_a4_supported.
 hipError_t launch_pass_a_v4(const DevView& v, float t, hipStream_t s);
 // fftq.hip: the fused frame through a three-plane intermediate (full outputs): pass AQ
 // (mirror-pair rows, N = 512 / 1024) or A3Q (one row per item, N = 2048 / 4096), then pass BQ
-// (column tiles, four transforms, N <= 1024) or the four-step column passes with Q planes.
-bool pass_q_supported(int n, int planes);
+// (column tiles, four transforms, N <= 1024) or the four-step column passes with Q planes.  Sizes: pass_q_supported.
 // Band-limited cascades (N = 512 / 1024, full column band): the live rows of a view's units, device
 // pointers.  tab = the view's `items` live items of pass AQ, each (context unit << 16 | y1) with the
 // view's unit 0 being context unit ubase (prune_items.h); ext = the live extent m_u of each unit of the

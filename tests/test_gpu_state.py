@@ -106,6 +106,29 @@ def test_kernel_timing_events_bounded():
     ctx.close()
 
 
+FLAT = dict(O.SCENE_CASCADES[0], cutoff_low=1e6)  # no texel inside the band: zero amplitude, every extent -1
+
+
+@pytest.mark.parametrize("env,n,cas,kw,rows,cols", [
+    # three-plane frame, 6 MiB per unit: chunks of two units, three of them
+    pytest.param({"OCEAN_CHUNK_MIB": "12"}, 512, O.SCENE_CASCADES[:2], dict(tiles=3), 3, 3, id="512-chunks"),
+    # the same on a flat sea: a chunk with no live item launches no row pass
+    pytest.param({"OCEAN_CHUNK_MIB": "12"}, 512, [FLAT, FLAT], dict(tiles=3), 0, 3, id="512-chunks-flat"),
+    pytest.param({}, 512, O.SCENE_CASCADES[:1], dict(flags=oh.F_DISPLACEMENT_ONLY), 1, 1, id="512-displacement"),
+    # 128 MiB per unit: one unit per chunk, each a row launch and the column passes once per band
+    pytest.param({"OCEAN_C4_BANDS": "2"}, 2048, O.SCENE_CASCADES[:1], dict(tiles=2), 2, 4, id="2048-bands"),
+])
+def test_frame_launch_counts_follow_the_plan(env, n, cas, kw, rows, cols):
+    """One frame makes one timed call per step of its plan (csrc/frame_plan.h; the same shapes are derived in
+    tests/frame_plan_test.cpp): kind 0 counts the row launches, kind 1 the column launches."""
+    from test_gpu_parity import _ctx_with_env
+    ctx, _ = _ctx_with_env(env, n, cas, **kw)
+    ctx.set_kernel_timing(True)
+    ctx.step(0.5)
+    assert (ctx.kernel_stats(0)[1], ctx.kernel_stats(1)[1]) == (rows, cols)
+    ctx.close()
+
+
 def _hip_runtime():
     """The process's HIP runtime (the copy torch loaded, which liboceanhip.so binds to), for
     hipGetDevice / hipSetDevice."""
