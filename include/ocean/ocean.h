@@ -73,7 +73,9 @@ extern "C" {
  *      Added later within version 4 in the same way: ocean_surface_bounds, ocean_surface_bounds_device,
  *      ocean_raycast, ocean_raycast_device, ocean_raycast_async.
  *      Added later within version 4 in the same way: OCEAN_DRAG_LINEAR, OCEAN_DRAG_QUADRATIC, ocean_body_dynamics,
- *      ocean_body_dynamics_device, ocean_body_dynamics_async. */
+ *      ocean_body_dynamics_device, ocean_body_dynamics_async.
+ *      Added later within version 4 in the same way: OCEAN_WHITECAP_MAX_RECORDS, ocean_whitecaps,
+ *      ocean_whitecaps_device, ocean_whitecaps_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -715,10 +717,64 @@ int ocean_raycast_device(ocean_ctx *ctx, int tile, int iterations, int steps, in
 int ocean_raycast_async(ocean_ctx *ctx, int tile, int iterations, int steps, int refine, const float *rays,
                         int count, float *dst, ocean_readback **req);
 
+/* Whitecap emitters: where the sea is breaking.  Every entry above answers "what is the water doing here?" for a
+ * place the host already knows; a spray, foam-particle or audio system asks where to spawn, every frame.  The
+ * reference has the foam only as a shading term (Water.shader:343 sums 1 - saturate(TURB.x) over the cascades); a
+ * host that wants emitters would read the TURB slices back, or a dense OCEAN_GRID_VERTICES grid at 32 B per node,
+ * to threshold a few hundred nodes out of them.  Here the threshold and the compaction run on the device and
+ * (capacity + 1) x 32 B come back.
+ *
+ * The grid is ocean_surface_grid's six numbers with the same node arithmetic: node (i, j), i < nx, j < ny, lies at
+ *       q.x = x0 + (float)i * dx,   q.z = z0 + (float)j * dz     (one fp32 multiply and one fp32 add each)
+ * and has the index k = j * nx + i.  Zero and negative spacings are valid.  With S(q) what ocean_sample_world
+ * returns for the point (q.x, q.z, lod) of tile `tile` (TURB at `lod` exactly as there: trilinear on OCEAN_F_MIPS
+ * contexts, level 0 otherwise):
+ *       foam(k) = S(q)[3]
+ *       node k is selected iff foam(k) >= threshold      (an fp32 compare: a NaN foam is never selected)
+ *       T = the number of selected nodes,   rank(k) = the number of selected nodes k' < k
+ *
+ * `out` holds capacity + 1 records of 32 B; `bytes` must equal (capacity + 1) * 32.  Record 0 is a header of eight
+ * uint32: T, W = min(T, capacity), nx * ny, capacity, 0, 0, 0, 0.  Every selected node with rank(k) < capacity
+ * writes record 1 + rank(k), eight floats:
+ *       [0..3] = q.x + S(q)[0], S(q)[1], q.z + S(q)[2], foam(k)    (bit for bit the first four floats of the
+ *                                                                   OCEAN_GRID_VERTICES record of that node at that lod)
+ *       [4..6] = Vs(q).xyz, exactly out[0..2] of ocean_query_velocity for q with iterations = 0, on an
+ *                OCEAN_F_VELOCITY context; +0, +0, +0 on any other
+ *       [7]    = (float)k                                          (exact: k < 2^22)
+ * The records come out in ascending k.  On overflow (T > capacity) the first `capacity` selected nodes in k order
+ * are kept and T still counts every selected node, so a host sees how much it missed.  Records W + 1 .. capacity
+ * are not written; their contents are unspecified.  The result does not depend on the launch grid or on
+ * scheduling: three launches (count, scan, emit; kind 2 of ocean_kernel_stats / ocean_kernel_name) with no atomics
+ * and no workgroup that waits for another.  Their scratch (at most 576 KiB) belongs to the context: allocated by
+ * the first call of any form, reused by every later one, freed by ocean_destroy.
+ *
+ * ocean_whitecaps: `out` is a host buffer; blocks, as ocean_surface_grid.
+ * ocean_whitecaps_device: `out` is a device pointer, 16-B aligned (else OCEAN_E_INVALID_ARG); async on the ctx
+ * stream, ordered after the queued steps: a particle system on the device reads the list with no host copy.
+ * ocean_whitecaps_async: `out` is a host destination (pinned, ocean_host_alloc, for a truly asynchronous copy).  The
+ * list is built in a readback slot on the ctx stream, after the steps queued so far and before later ones, and all
+ * (capacity + 1) * 32 bytes (at most 2 MiB: every list fits a slot) are copied on the copy stream like an
+ * ocean_read_async slice, with the same ocean_readback_status / _wait / _release / _copy_ms.  *req is NULL after
+ * every failure.
+ * All three: OCEAN_E_INVALID_ARG, checked before any device call, for a null ctx, `out` or `req`, a tile out of
+ * range, a lod that is not finite or negative, a non-finite threshold, x0, z0, dx or dz, nx < 1 or ny < 1,
+ * nx * ny > OCEAN_GRID_MAX_NODES (in 64 bits), capacity outside [1, OCEAN_WHITECAP_MAX_RECORDS], a wrong `bytes` or
+ * a misaligned device `out`; then, in this order, OCEAN_E_UNSUPPORTED on a DISPLACEMENT_ONLY context (it has no
+ * TURB), OCEAN_E_STATE before ocean_init_spectrum and OCEAN_E_UNSUPPORTED on a column-parity context (as the
+ * queries). */
+#define OCEAN_WHITECAP_MAX_RECORDS 65535
+int ocean_whitecaps(ocean_ctx *ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz,
+                    int nx, int ny, int capacity, float *out, size_t bytes);
+int ocean_whitecaps_device(ocean_ctx *ctx, int tile, float lod, float threshold, float x0, float z0, float dx,
+                           float dz, int nx, int ny, int capacity, float *out, size_t bytes);
+int ocean_whitecaps_async(ocean_ctx *ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz,
+                          int nx, int ny, int capacity, float *out, size_t bytes, ocean_readback **req);
+
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
  * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async /
- * ocean_body_buoyancy_async / ocean_query_velocity_async / ocean_raycast_async / ocean_body_dynamics_async request records HIP timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it
- * is off record only untimed events. */
+ * ocean_body_buoyancy_async / ocean_query_velocity_async / ocean_raycast_async / ocean_body_dynamics_async /
+ * ocean_whitecaps_async request records HIP timing events around its device-to-host copy, for
+ * ocean_readback_copy_ms.  Requests made while it is off record only untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 
 /* Duration of a completed request's device-to-host copy in ms (HIP events on the copy stream around

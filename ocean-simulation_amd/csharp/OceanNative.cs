@@ -171,6 +171,17 @@ namespace OceanHip
         public static extern OceanStatus ocean_raycast_device(IntPtr ctx, int tile, int iterations, int steps, int refine, IntPtr rays, int count, IntPtr output);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_raycast_async(IntPtr ctx, int tile, int iterations, int steps, int refine, [In] float[] rays, int count, IntPtr dst, out IntPtr request);
+        // Whitecap emitters (added within ABI 4 in the same way).  The nodes (i, j) at (x0 + i dx, z0 + j dz) whose foam at
+        // `lod` is >= threshold, compacted in ascending k = j * nx + i: capacity + 1 records of 32 B, bytes = (capacity + 1) * 32.
+        // Record 0 = eight uint (T selected, W = min(T, capacity) written, nx * ny, capacity, 0, 0, 0, 0); then 8 floats per
+        // node: displaced x, y, z, foam, the water's velocity x, y, z (OceanFlags.Velocity contexts, else 0), (float)k.
+        public const int WhitecapMaxRecords = 65535;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_whitecaps(IntPtr ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz, int nx, int ny, int capacity, [Out] float[] output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_whitecaps_device(IntPtr ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz, int nx, int ny, int capacity, IntPtr output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_whitecaps_async(IntPtr ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz, int nx, int ny, int capacity, IntPtr dst, UIntPtr bytes, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_read_async(IntPtr ctx, OceanTexture tex, int tile, int cascade, IntPtr dst, UIntPtr bytes, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

@@ -255,6 +255,26 @@ namespace OceanHip
             return (int)hit[3] != OceanNative.RayMiss;
         }
 
+        // Where the sea is breaking (ocean.h ocean_whitecaps): the nodes (i, j) at (x0 + i dx, z0 + j dz) whose foam
+        // reaches `threshold`, in ascending j * nx + i.  Returns T, the number of selected nodes; records = 8 floats
+        // for each of the first min(T, capacity): displaced x, y, z, foam, the water's velocity x, y, z (`velocity`
+        // set before Awake, else 0), (float)(j * nx + i).  Spawn points for spray and foam particles; the reference
+        // has the foam only as a shading term (Water.shader:343).
+        public int Whitecaps(float threshold, float x0, float z0, float dx, float dz, int nx, int ny, int capacity,
+                             out float[] records, float lod = 0f)
+        {
+            // (a capacity outside the limits is refused by the library; no managed buffer of that size first)
+            bool valid = capacity >= 1 && capacity <= OceanNative.WhitecapMaxRecords;
+            var output = new float[((valid ? capacity : 0) + 1) * 8];
+            OceanNative.Check(OceanNative.ocean_whitecaps(ctx, 0, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, output,
+                                                          (UIntPtr)(ulong)(output.Length * 4)), "ocean_whitecaps");
+            int total = BitConverter.ToInt32(BitConverter.GetBytes(output[0]), 0);
+            int written = BitConverter.ToInt32(BitConverter.GetBytes(output[1]), 0);
+            records = new float[written * 8];
+            Array.Copy(output, 8, records, 0, records.Length);
+            return total;
+        }
+
         // The per-cascade bounds of the displacement (ocean.h ocean_surface_bounds): 8 floats per cascade, (min x, y,
         // z, w, max x, y, z, w); their cascade sums bound the displaced mesh (culling, tessellation range).
         public float[] SurfaceBounds()

@@ -262,6 +262,9 @@ struct ocean_ctx {
     float* bounds_dev = nullptr;
     std::vector<bool> bounds_valid;
     bool disp_exposed = false;
+    // whitecap emitters (whitecaps.hip): the ballot masks and per-chunk counts of the largest grid, allocated by the
+    // first ocean_whitecaps* call and reused by every later one
+    void* whitecap_dev = nullptr;
     float4* deriv_mips = nullptr;  // OCEAN_F_MIPS chains (levels 1..log2 N per slice)
     float4* turb_mips = nullptr;
     size_t mip_chain = 0;
@@ -473,7 +476,7 @@ int slice_ptr(ocean_ctx* ctx, int tex, int tile, int cascade, size_t bytes, char
 void free_all(ocean_ctx* c) {
     void* ptrs[] = {c->noise, c->h0, c->h0k, c->waves, c->plane[0], c->disp, c->deriv,
                     c->turb,  c->normal, c->tw,    c->casc,     c->tplane, c->foam, c->deriv_mips, c->turb_mips,
-                    c->qside, c->vel, c->vplane, c->prune_dev, c->bounds_dev};
+                    c->qside, c->vel, c->vplane, c->prune_dev, c->bounds_dev, c->whitecap_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (auto& t : c->pending) {
@@ -1780,6 +1783,95 @@ int ocean_raycast_async(ocean_ctx* ctx, int tile, int iterations, int steps, int
         ctx, {{rays, (size_t)count * 8 * 4}}, dst, (size_t)count * 8 * 4,
         [&](const float* d_rays, float* d_out) {
             return launch_ray(ctx, tile, iterations, steps, refine, d_rays, count, d_out);
+        },
+        req);
+}
+
+// Whitecap emitters (ocean.h).
+
+// Argument checks of the whitecap emitters, before any device call (ocean.h).  What does not need the context
+// comes first, so that a host learns of a bad argument whatever its context is; device_out: the _device form's
+// output pointer, 16-byte aligned.
+static int check_whitecaps(ocean_ctx* ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz,
+                           int nx, int ny, int capacity, const float* out, size_t bytes, bool device_out) {
+    if (!out) return fail(OCEAN_E_INVALID_ARG, "null output");
+    if (!std::isfinite(lod) || lod < 0.0f) return fail(OCEAN_E_INVALID_ARG, "lod must be finite and >= 0");
+    if (!std::isfinite(threshold)) return fail(OCEAN_E_INVALID_ARG, "threshold must be finite");
+    if (!std::isfinite(x0) || !std::isfinite(z0) || !std::isfinite(dx) || !std::isfinite(dz))
+        return fail(OCEAN_E_INVALID_ARG, "grid origin and spacing must be finite");
+    if (nx < 1 || ny < 1) return fail(OCEAN_E_INVALID_ARG, "nx and ny must be at least 1");
+    const uint64_t nodes = (uint64_t)nx * (uint64_t)ny;
+    if (nodes > (uint64_t)OCEAN_GRID_MAX_NODES)
+        return fail(OCEAN_E_INVALID_ARG, "nx * ny = " + std::to_string(nodes) + " > OCEAN_GRID_MAX_NODES");
+    if (capacity < 1 || capacity > OCEAN_WHITECAP_MAX_RECORDS)
+        return fail(OCEAN_E_INVALID_ARG, "capacity = " + std::to_string(capacity) + " outside [1, OCEAN_WHITECAP_MAX_RECORDS]");
+    const size_t want = ((size_t)capacity + 1) * 32;
+    if (bytes != want)
+        return fail(OCEAN_E_INVALID_ARG, "byte count " + std::to_string(bytes) + " != (capacity + 1) * 32 = " +
+                                             std::to_string(want));
+    if (device_out)
+        if (int r = check_aligned("ocean_whitecaps_device", nullptr, {}, out)) return r;
+    if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+    if (tile < 0 || tile >= ctx->T) return fail(OCEAN_E_INVALID_ARG, "tile out of range");
+    return OCEAN_OK;
+}
+
+// ... and of the context's flags and state.
+static int check_whitecaps_state(const ocean_ctx* ctx) {
+    if (ctx->flags & OCEAN_F_DISPLACEMENT_ONLY)
+        return fail(OCEAN_E_UNSUPPORTED, "ocean_whitecaps needs the TURB texture (not OCEAN_F_DISPLACEMENT_ONLY)");
+    if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, "ocean_init_spectrum must precede ocean_whitecaps");
+    if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, "whitecaps of a column-parity shard (half the columns)");
+    return OCEAN_OK;
+}
+
+// The three whitecap kernels on the ctx stream (device pointer; kind 2 of ocean_kernel_stats), over the
+// context's scratch, which the first call allocates.  (the caller has entered: OCEAN_ENTER)
+static int launch_whitecap_kernels(ocean_ctx* ctx, int tile, float lod, float threshold, float x0, float z0, float dx,
+                                   float dz, int nx, int ny, int capacity, float* d_out) {
+    if (!ctx->whitecap_dev) OCEAN_HIP(hipMalloc(&ctx->whitecap_dev, ocean::whitecap_scratch_bytes()));
+    const ocean::DevView v = ctx->view();
+    return timed(ctx, 2,
+                 [&] {
+                     return ocean::launch_whitecaps(v, ctx->vel, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity,
+                                                    ctx->whitecap_dev, d_out, ctx->stream);
+                 },
+                 "whitecaps");
+}
+
+// The largest list, header included, fits the smallest readback slot.
+static_assert(((size_t)OCEAN_WHITECAP_MAX_RECORDS + 1) * 32 <= kQuerySlotBytes, "a readback slot holds every whitecap list");
+
+int ocean_whitecaps_device(ocean_ctx* ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz,
+                           int nx, int ny, int capacity, float* out, size_t bytes) {
+    if (int r = check_whitecaps(ctx, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, out, bytes, true)) return r;
+    if (int r = check_whitecaps_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    return launch_whitecap_kernels(ctx, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, out);
+}
+
+int ocean_whitecaps(ocean_ctx* ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz, int nx,
+                    int ny, int capacity, float* out, size_t bytes) {
+    if (int r = check_whitecaps(ctx, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, out, bytes, false)) return r;
+    if (int r = check_whitecaps_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    // no inputs: the nodes follow from the six numbers
+    return run_staged(ctx, "ocean_whitecaps", {}, out, bytes, [&](const float*, float* d_out) {
+        return launch_whitecap_kernels(ctx, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, d_out);
+    });
+}
+
+int ocean_whitecaps_async(ocean_ctx* ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz,
+                          int nx, int ny, int capacity, float* out, size_t bytes, ocean_readback** req) {
+    if (!req) return fail(OCEAN_E_INVALID_ARG, "req is null");
+    *req = nullptr;
+    if (int r = check_whitecaps(ctx, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, out, bytes, false)) return r;
+    if (int r = check_whitecaps_state(ctx)) return r;
+    OCEAN_ENTER(ctx);
+    return start_staged_readback(
+        ctx, {}, out, bytes,
+        [&](const float*, float* d_out) {
+            return launch_whitecap_kernels(ctx, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, d_out);
         },
         req);
 }

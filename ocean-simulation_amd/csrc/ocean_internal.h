@@ -199,6 +199,14 @@ hipError_t launch_surface_bounds(const DevView& v, int tile, float* partial, flo
 hipError_t launch_raycast(const DevView& v, int tile, int iterations, int steps, int refine, const float* bounds,
                           const float* rays, int count, float* out, hipStream_t s);
 
+// whitecaps.hip: whitecap emitters (ocean_whitecaps*), device pointers: out = (capacity + 1) records of 32 B, the
+// header then the selected nodes of the grid in ascending node order, 16-B aligned; vel = the context's VEL or null
+// (records carry a zero velocity); scratch: whitecap_scratch_bytes() bytes, 8-B aligned, the ballot masks of the
+// largest grid then its per-chunk counts.  Three launches: count, scan, emit.
+size_t whitecap_scratch_bytes();
+hipError_t launch_whitecaps(const DevView& v, const float4* vel, int tile, float lod, float threshold, float x0, float z0,
+                            float dx, float dz, int nx, int ny, int capacity, void* scratch, float* out, hipStream_t s);
+
 // fft4k.hip (N = 2048, 4096: pass_c4_supported): four-step column passes C1 (in place on the
 // 16-wide tile-major intermediate) + C2 (with the pass-B epilogue); replace pass B.
 hipError_t launch_pass_c4(const DevView& v, hipStream_t s);

@@ -114,6 +114,39 @@ __device__ __forceinline__ float4 sample_disp(const DevView& v, int tile, float 
     return disp;
 }
 
+// The .x channel of tap / tri alone: the same texels, weights and operations on that channel, 4 B per texel.
+__device__ __forceinline__ float tap_x(const float4* __restrict__ t, int m, const Bil& b) {
+    const float t00 = t[(size_t)b.y0 * m + b.x0].x, t10 = t[(size_t)b.y0 * m + b.x1].x;
+    const float t01 = t[(size_t)b.y1 * m + b.x0].x, t11 = t[(size_t)b.y1 * m + b.x1].x;
+    const float a = t00 + b.fx * (t10 - t00), c = t01 + b.fx * (t11 - t01);
+    return a + b.fy * (c - a);
+}
+
+__device__ __forceinline__ float tri_x(const float4* tex0, const float4* chain, size_t chain_len, int slice, int n,
+                                       int logn, float u, float v, float lod) {
+    if (!chain || !(lod > 0.0f)) return tap_x(tex0 + (size_t)slice * n * n, n, bil(u, v, n));
+    const float lc = fminf(lod, (float)logn);
+    const int l0 = (int)floorf(lc), l1 = min(l0 + 1, logn);
+    const float f = lc - (float)l0;
+    const int m0 = n >> l0, m1 = n >> l1;
+    const float a = tap_x(level_ptr(tex0, chain, chain_len, slice, n, l0), m0, bil(u, v, m0));
+    const float b = tap_x(level_ptr(tex0, chain, chain_len, slice, n, l1), m1, bil(u, v, m1));
+    return a + f * (b - a);
+}
+
+// The TURB taps of sample_cascades alone (a context with TURB: not DISPLACEMENT_ONLY): the same operations on
+// the same texels, so the result is bit-identical to sample_cascades(...).turb, with mip chains and lod > 0 too.
+__device__ __forceinline__ float sample_foam(const DevView& v, int tile, float x, float z, float lod) {
+    float turb = 0.0f;
+    for (int c = 0; c < v.C; ++c) {
+        const float L = v.casc[c * 5];
+        const float u = x / L, w = z / L;
+        const float tb = tri_x(v.turb, v.turb_mips, v.mip_chain, tile * v.C + c, v.n, v.logn, u, w, lod);
+        turb = turb + (1.0f - fminf(fmaxf(tb, 0.0f), 1.0f));
+    }
+    return turb;
+}
+
 // The surface above a world point q (OCEAN_QUERY_SURFACE, query.hip has the derivation): `iterations` steps
 // of the fixed point p <- q - D_xz(p) from p = q.  Returns p = (px, pz).
 __device__ __forceinline__ float2 surface_fixed_point(const DevView& v, int tile, float qx, float qz, int iterations) {

@@ -4,8 +4,12 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps]
 //
+// With whitecaps the host reads nothing back per frame: it runs F steps on a velocity context, then one
+// WaterBody::Whitecaps over a 101 x 101 grid (threshold 0.1, capacity 4096, lod 0) and writes whitecaps.bin (float32
+// [4097][8]: the header, the W records, zeros); the summary line carries the header's T and W and the W records
+// ("records", %.9g: exact for fp32); tests/test_gpu_whitecaps_host.py checks them.
 // With rays the host reads nothing back per frame: it runs F steps, then one WaterBody::Raycast for six rays (4
 // fixed-point steps, 32 march steps, 8 bisections) and one WaterBody::SurfaceBounds, and writes rays.bin (float32
 // [6][8]), raycast.bin (float32 [6][8]) and bounds.bin (float32 [cascades][8]); the summary line carries both
@@ -52,13 +56,13 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
     if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity" &&
-        mode != "rays" && mode != "dynamics") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays or dynamics\n");
+        mode != "rays" && mode != "dynamics" && mode != "whitecaps") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics or whitecaps\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -132,6 +136,25 @@ int main(int argc, char** argv) {
             std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"points\": %zu, \"records\": [", F, n,
                         (int)wb.cascades.size(), points.size() / 2);
             for (size_t i = 0; i < rec.size(); ++i) std::printf("%s%.9g", i ? ", " : "", rec[i]);
+            std::printf("]}\n");
+            wb.OnDisable();
+            return 0;
+        }
+        if (mode == "whitecaps") {
+            // MeshGenerator's default plane as the region: 101 x 101 nodes 10 m apart around the origin
+            const float threshold = 0.1f, x0 = -500.0f, z0 = -500.0f, dx = 10.0f, dz = 10.0f;
+            const int nx = 101, ny = 101, capacity = 4096;
+            wb.velocity = true;
+            wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
+            wb.Awake();
+            for (int f = 0; f < F; ++f) wb.Update((float)f / 60.0f);
+            const std::vector<float> list = wb.Whitecaps(threshold, x0, z0, dx, dz, nx, ny, capacity);
+            uint32_t head[8];
+            ocean_host::WaterBody::WhitecapHeader(list, head);
+            write_bin(out + "/whitecaps.bin", list.data(), list.size());
+            std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"nodes\": %u, \"capacity\": %u, \"selected\": %u, "
+                        "\"written\": %u, \"records\": [", F, n, (int)wb.cascades.size(), head[2], head[3], head[0], head[1]);
+            for (size_t i = 0; i < (size_t)head[1] * 8; ++i) std::printf("%s%.9g", i ? ", " : "", list[8 + i]);
             std::printf("]}\n");
             wb.OnDisable();
             return 0;

@@ -232,6 +232,29 @@ public:
         return out;
     }
 
+    // Where the sea is breaking (ocean.h ocean_whitecaps): the nodes (i, j) at (x0 + i dx, z0 + j dz) whose foam
+    // reaches `threshold`, in ascending j * nx + i.  Returns the list as the library writes it, capacity + 1 records
+    // of 8 floats: the header (eight uint32: T selected, W = min(T, capacity) written, nx * ny, capacity, 0, 0, 0, 0;
+    // WhitecapHeader reads it), then W records: displaced x, y, z, foam, the water's velocity x, y, z (`velocity` set
+    // before Awake, else 0), (float)(j * nx + i); the records past W are zero.  Spawn points for spray and foam
+    // particles; the reference has the foam only as a shading term (Water.shader:343).
+    std::vector<float> Whitecaps(float threshold, float x0, float z0, float dx, float dz, int nx, int ny, int capacity,
+                                 float lod = 0.0f) const {
+        std::vector<float> out(((size_t)std::max(capacity, 0) + 1) * 8);
+        check(ocean_whitecaps(ctx_, 0, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, out.data(),
+                              out.size() * sizeof(float)),
+              "ocean_whitecaps");
+        uint32_t head[8];
+        WhitecapHeader(out, head);
+        std::fill(out.begin() + 8 * ((size_t)head[1] + 1), out.end(), 0.0f);  // unspecified in the library's output
+        return out;
+    }
+
+    // The eight uint32 of a whitecap list's header (its floats hold their bits).
+    static void WhitecapHeader(const std::vector<float>& list, uint32_t head[8]) {
+        std::memcpy(head, list.data(), 8 * sizeof(uint32_t));
+    }
+
     // The per-cascade bounds of the displacement (ocean.h ocean_surface_bounds): 8 floats per cascade, (min x, y,
     // z, w, max x, y, z, w); their cascade sums bound the displaced mesh.
     std::vector<float> SurfaceBounds() const {

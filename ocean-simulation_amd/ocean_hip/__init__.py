@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "ocean_surface_bounds", "ocean_surface_bounds_device",
     "ocean_raycast", "ocean_raycast_device", "ocean_raycast_async",
     "ocean_body_dynamics", "ocean_body_dynamics_device", "ocean_body_dynamics_async",
+    "ocean_whitecaps", "ocean_whitecaps_device", "ocean_whitecaps_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -91,6 +92,8 @@ RAY_MISS, RAY_HIT, RAY_SUBMERGED = 0, 1, 2
 RAY_MAX_RAYS = 16384
 RAY_MAX_STEPS = 1024
 RAY_MAX_SAMPLES = 1 << 24
+# ocean_whitecaps* limit (ocean.h): records of a list, the header not counted
+WHITECAP_MAX_RECORDS = 65535
 
 
 class OceanError(RuntimeError):
@@ -182,6 +185,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_body_dynamics": ([P, i, i, i, i, P, i, P, P, i, P], i),
         "ocean_body_dynamics_device": ([P, i, i, i, i, P, i, P, P, i, P], i),
         "ocean_body_dynamics_async": ([P, i, i, i, i, P, i, P, P, i, P, ctypes.POINTER(P)], i),
+        "ocean_whitecaps": ([P, i, f, f, f, f, f, f, i, i, i, P, sz], i),
+        "ocean_whitecaps_device": ([P, i, f, f, f, f, f, f, i, i, i, P, sz], i),
+        "ocean_whitecaps_async": ([P, i, f, f, f, f, f, f, i, i, i, P, sz, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -466,6 +472,44 @@ class OceanContext:
                                                                            dz, nx, ny, dst, nbytes, req), buf)
 
     @staticmethod
+    def parse_whitecaps(buf: np.ndarray):
+        """(T, records float32[W][8]) of a whitecap list float32[capacity + 1][8] as ocean_whitecaps writes it: the
+        header's eight uint32 (T, W, nodes, capacity, 0, 0, 0, 0), then W records in ascending node order."""
+        buf = np.ascontiguousarray(buf, np.float32).reshape(-1, 8)
+        head = buf[0].view(np.uint32)
+        return int(head[0]), buf[1:1 + int(head[1])].copy()
+
+    def whitecaps(self, threshold: float, x0: float, z0: float, dx: float, dz: float, nx: int, ny: int,
+                  capacity: int = 4096, lod: float = 0.0, tile: int = 0):
+        """Whitecap emitters (ocean.h ocean_whitecaps), blocking: the nodes (i, j) at (x0 + i dx, z0 + j dz) whose
+        foam, sample_world's [0][3] at `lod`, is >= threshold, in ascending k = j nx + i -> (T, float32[W][8]): T the
+        number of selected nodes, W = min(T, capacity) records (displaced x, y, z, foam, the water's velocity x, y,
+        z on an F_VELOCITY context else zeros, float(k))."""
+        capacity = int(capacity)
+        # (a capacity outside the limits is refused by the library; no host buffer of that size first)
+        buf = np.empty((capacity + 1 if 1 <= capacity <= WHITECAP_MAX_RECORDS else 1, 8), np.float32)
+        _check(self.lib.ocean_whitecaps(self._h, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, buf.ctypes.data,
+                                        buf.nbytes), "ocean_whitecaps")
+        return self.parse_whitecaps(buf)
+
+    def whitecaps_async(self, threshold: float, x0: float, z0: float, dx: float, dz: float, nx: int, ny: int,
+                        capacity: int = 4096, lod: float = 0.0, tile: int = 0, buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_whitecaps_async): the list is built behind the queued steps and its
+        float32[capacity + 1][8] lands in pinned host memory like a read_async slice.  Poll .done() / .wait(), then
+        .whitecaps() -> (T, records[W][8]); `buf`: a caller-owned pinned slot of at least (capacity + 1) x 32 B."""
+        nbytes = (int(capacity) + 1) * 32
+        return Readback(self, (int(capacity) + 1, 8), nbytes, "ocean_whitecaps_async",
+                        lambda dst, req: self.lib.ocean_whitecaps_async(self._h, tile, lod, threshold, x0, z0, dx, dz, nx,
+                                                                        ny, capacity, dst, nbytes, req), buf)
+
+    def whitecaps_device(self, out_ptr: int, threshold: float, x0: float, z0: float, dx: float, dz: float, nx: int,
+                         ny: int, capacity: int, lod: float = 0.0, tile: int = 0) -> None:
+        """The device-pointer form (ocean_whitecaps_device): out float[capacity + 1][8] on this context's device,
+        16-B aligned; async on the context's stream, after the queued steps.  parse_whitecaps reads a copy of it."""
+        _check(self.lib.ocean_whitecaps_device(self._h, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity,
+                                               ctypes.c_void_p(out_ptr), (int(capacity) + 1) * 32), "ocean_whitecaps_device")
+
+    @staticmethod
     def _body_args(hull, bodies):
         h = np.ascontiguousarray(hull, np.float32)
         b = np.ascontiguousarray(bodies, np.float32)
@@ -731,6 +775,10 @@ class Readback:
         v = np.frombuffer(raw, np.float32).reshape(self.shape)
         v.flags.writeable = False
         return v
+
+    def whitecaps(self):
+        """A completed whitecaps_async request parsed: (T, records float32[W][8]) (waits if still pending)."""
+        return OceanContext.parse_whitecaps(self.view())
 
     def release(self) -> None:
         if self._h:
@@ -1041,6 +1089,13 @@ class WaterBody:
             return None
         point = ray[0, :3] + rec[0] * ray[0, 3:6]  # fp32: pos(t*) of ocean.h
         return WaterHit(float(rec[0]), point, rec[4:7].copy(), float(rec[7]), int(rec[3]) == RAY_SUBMERGED)
+
+    def Whitecaps(self, threshold: float, x0: float, z0: float, dx: float, dz: float, nx: int, ny: int,
+                  capacity: int = 4096, lod: float = 0.0, tile: int = 0):
+        """Where the sea is breaking (OceanContext.whitecaps): the nodes of the grid whose foam reaches `threshold`,
+        as (T, float32[W][8]): spawn points for spray and foam particles with the water's velocity beside them
+        (`velocity=True`).  The reference has the foam only as a shading term (Water.shader:343).  Blocking."""
+        return self.ctx.whitecaps(threshold, x0, z0, dx, dz, nx, ny, capacity, lod, tile)
 
     def SurfaceBounds(self, tile: int = 0) -> np.ndarray:
         """(min xyz, max xyz) float32[2][3] of the cascade-summed displacement, from the per-cascade records
