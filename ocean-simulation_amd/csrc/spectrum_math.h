@@ -42,9 +42,10 @@ __device__ __forceinline__ float4 wave_data(int x, int y, int n, WaveBand b, flo
 // sin and cos of an fp32 argument, |x| < 2^17 on the fast path: Cody-Waite
 // reduction by pi/2 with a three-part FMA split (exact products), then
 // minimax polynomials on [-pi/4, pi/4] (Cephes sinf/cosf coefficients);
-// max error ~1-2 ulp against correctly rounded sin/cos.  Larger |x| falls back
-// to the library sincosf.  ~25 VALU instead of the library's ~45 plus its
-// Payne-Hanek branch.
+// max error ~1-2 ulp against correctly rounded sin/cos (tests/test_phase_math.py
+// holds a numpy restatement to 2 ulp, tests/test_gpu_phase.py the device to that
+// restatement bit for bit).  Larger |x| falls back to the library sincosf.  ~25
+// VALU instead of the library's ~45 plus its Payne-Hanek branch.
 __device__ __forceinline__ void sincos_fast(float x, float* s, float* c) {
     if (!(fabsf(x) < 131072.0f)) {
         sincosf(x, s, c);
