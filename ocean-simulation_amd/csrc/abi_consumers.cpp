@@ -1,0 +1,572 @@
+// C-ABI layer of liboceanhip.so, the point consumers (ocean.h): surface and velocity queries, surface grids,
+// buoyant bodies, body dynamics, ray casts and whitecap emitters, each in a _device, a blocking host and an
+// _async form; and world sampling and the surface bounds, which keep bodies of their own.
+//
+// A consumer is stated once, as a struct built from its entry's arguments (a "family"), and its three entries
+// are the three forms of that struct: device_form, host_form, async_form.  A family has
+//   ctx, out          the context and the caller's output pointer;
+//   check(form)       its argument checks, before any device call.  They take the form because the staged forms
+//                     (host and async) have a limit on what they stage, and a family may place its alignment
+//                     or slot-size test among its own;
+//   state()           what it needs of the context (StateRule);
+//   inputs()          the caller's arrays its kernel reads (StagedInputs), in the order launch takes them;
+//   out_bytes()       the size of its results;
+//   lacks()           null, or the noun of what an empty call has none of ("points"): the blocking forms then
+//                     return OCEAN_OK without a launch, and the async form refuses, since there is no request;
+//   launch(in, out)   its kernel on the ctx stream over device pointers (kind 2 of ocean_kernel_stats), the
+//                     caller having entered the device scope.
+// The order of the tests of each form is the form's, below, and the same for every family.
+#include <cmath>
+
+#include "abi_internal.h"
+
+namespace {
+
+enum class Form { Device, Host, Async };
+
+// What a family needs of its context: the flag it was created with or without, the spectrum (the cascade
+// wavelengths exist only after init), and all the columns (a column-parity shard holds half of them).
+enum class Needs { Nothing, Velocity, Turb };
+struct StateRule {
+    const char* entry;  // the family's name in messages, and the stem of its entries' names
+    const char* shard;  // "surface query of": ... a column-parity shard
+    Needs needs = Needs::Nothing;
+};
+int check_state(const ocean_ctx* ctx, const StateRule& s) {
+    if (s.needs == Needs::Velocity && !(ctx->flags & OCEAN_F_VELOCITY))
+        return fail(OCEAN_E_UNSUPPORTED, std::string(s.entry) + " needs a context created with OCEAN_F_VELOCITY");
+    if (s.needs == Needs::Turb && (ctx->flags & OCEAN_F_DISPLACEMENT_ONLY))
+        return fail(OCEAN_E_UNSUPPORTED, std::string(s.entry) + " needs the TURB texture (not OCEAN_F_DISPLACEMENT_ONLY)");
+    if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, std::string("ocean_init_spectrum must precede ") + s.entry);
+    if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, std::string(s.shard) + " a column-parity shard (half the columns)");
+    return OCEAN_OK;
+}
+
+// The _device forms: the kernels read floats and write float4 rows (ocean.h).
+int check_aligned(const char* entry, const StagedInputs& in, const void* out) {
+    bool ok = ((uintptr_t)out & 15) == 0;
+    for (int k = 0; k < in.n; ++k) ok = ok && ((uintptr_t)in.v[k].ptr & 3) == 0;
+    if (ok) return OCEAN_OK;
+    return fail(OCEAN_E_INVALID_ARG, std::string(entry) + "_device: " +
+                                         (in.names ? std::string(in.names) + " must be 4-byte and out" : "out must be") +
+                                         " 16-byte aligned");
+}
+
+int check_tile(const ocean_ctx* ctx, int tile) {
+    if (tile < 0 || tile >= ctx->T) return fail(OCEAN_E_INVALID_ARG, "tile out of range");
+    return OCEAN_OK;
+}
+
+int check_iterations(int iterations) {
+    if (iterations < 0 || iterations > 16) return fail(OCEAN_E_INVALID_ARG, "iterations must be in [0, 16]");
+    return OCEAN_OK;
+}
+
+// A mode of the `what` ("query", "grid") modes, and its iterations: none in the mode `direct`, which takes no
+// fixed-point steps.
+int check_mode(bool known, const char* what, int iterations, bool is_direct, const char* direct) {
+    if (!known) return fail(OCEAN_E_INVALID_ARG, std::string("unknown ") + what + " mode");
+    if (int r = check_iterations(iterations)) return r;
+    if (is_direct && iterations != 0) return fail(OCEAN_E_INVALID_ARG, std::string(direct) + " takes iterations = 0");
+    return OCEAN_OK;
+}
+int check_query_mode(int mode, int iterations) {
+    return check_mode(mode == OCEAN_QUERY_REFERENCE || mode == OCEAN_QUERY_SURFACE, "query", iterations,
+                      mode == OCEAN_QUERY_REFERENCE, "OCEAN_QUERY_REFERENCE");
+}
+
+// The region of a grid: nx x ny nodes from (x0, z0), (dx, dz) apart.
+int check_region(float x0, float z0, float dx, float dz, int nx, int ny) {
+    if (!std::isfinite(x0) || !std::isfinite(z0) || !std::isfinite(dx) || !std::isfinite(dz))
+        return fail(OCEAN_E_INVALID_ARG, "grid origin and spacing must be finite");
+    if (nx < 1 || ny < 1) return fail(OCEAN_E_INVALID_ARG, "nx and ny must be at least 1");
+    const uint64_t nodes = (uint64_t)nx * (uint64_t)ny;
+    if (nodes > (uint64_t)OCEAN_GRID_MAX_NODES)
+        return fail(OCEAN_E_INVALID_ARG, "nx * ny = " + std::to_string(nodes) + " > OCEAN_GRID_MAX_NODES");
+    return OCEAN_OK;
+}
+
+// The _device form: the caller's own device pointers go to the launch; nothing is staged, so no limit.
+template <class Family>
+int device_form(const Family& f) {
+    if (int r = f.check(Form::Device)) return r;
+    const StagedInputs in = f.inputs();
+    if (int r = check_aligned(f.state().entry, in, f.out)) return r;
+    if (int r = check_state(f.ctx, f.state())) return r;
+    if (f.lacks()) return OCEAN_OK;
+    OCEAN_ENTER(f.ctx);
+    const float* d_in[kMaxInputs] = {};
+    for (int k = 0; k < in.n; ++k) d_in[k] = static_cast<const float*>(in.v[k].ptr);
+    return f.launch(d_in, f.out);
+}
+
+// The blocking host form: inputs and results through one stream-ordered block (run_staged).
+template <class Family>
+int host_form(const Family& f) {
+    if (int r = f.check(Form::Host)) return r;
+    if (int r = check_state(f.ctx, f.state())) return r;
+    if (f.lacks()) return OCEAN_OK;
+    OCEAN_ENTER(f.ctx);
+    return run_staged(f.ctx, f.state().entry, f.inputs(), f.out, f.out_bytes(),
+                      [&](const float* const* d_in, float* d_out) { return f.launch(d_in, d_out); });
+}
+
+// The async form: a readback request over a slot (start_staged_readback).  req_name: the parameter's name in
+// ocean.h.
+template <class Family>
+int async_form(const Family& f, ocean_readback** req, const char* req_name = "req") {
+    if (!req) return fail(OCEAN_E_INVALID_ARG, std::string(req_name) + " is null");
+    *req = nullptr;
+    if (int r = f.check(Form::Async)) return r;
+    if (const char* noun = f.lacks())
+        return fail(OCEAN_E_INVALID_ARG, std::string(f.state().entry) + "_async: no " + noun + ", so no request");
+    if (int r = check_state(f.ctx, f.state())) return r;
+    OCEAN_ENTER(f.ctx);
+    return start_staged_readback(f.ctx, f.inputs(), f.out, f.out_bytes(),
+                                 [&](const float* const* d_in, float* d_out) { return f.launch(d_in, d_out); }, req);
+}
+
+// Surface queries: points float[count][2] -> records float[count][8]; the staged forms take at most
+// OCEAN_QUERY_MAX_POINTS.
+struct SurfaceQuery {
+    ocean_ctx* ctx;
+    int tile, mode, iterations;
+    const float* points;
+    int count;
+    float* out;
+
+    int check(Form form) const {
+        if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+        if (!points || !out) return fail(OCEAN_E_INVALID_ARG, "null points or output");
+        if (count < 0) return fail(OCEAN_E_INVALID_ARG, "negative point count");
+        if (form != Form::Device && count > OCEAN_QUERY_MAX_POINTS)
+            return fail(OCEAN_E_INVALID_ARG, "point count " + std::to_string(count) + " > OCEAN_QUERY_MAX_POINTS");
+        if (int r = check_query_mode(mode, iterations)) return r;
+        return check_tile(ctx, tile);
+    }
+    StateRule state() const { return {"ocean_query_surface", "surface query of"}; }
+    StagedInputs inputs() const { return {"points", 1, {{points, (size_t)count * 2 * 4}}}; }
+    size_t out_bytes() const { return (size_t)count * 8 * 4; }
+    const char* lacks() const { return count == 0 ? "points" : nullptr; }
+    int launch(const float* const* in, float* d_out) const {
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] { return ocean::launch_query_surface(v, tile, mode, iterations, in[0], count, d_out, ctx->stream); },
+                     "query_surface");
+    }
+};
+
+// Surface-velocity queries: the surface query in surface mode, over the VELOCITY texture.
+struct VelocityQuery : SurfaceQuery {
+    StateRule state() const { return {"ocean_query_velocity", "velocity query of", Needs::Velocity}; }
+    int launch(const float* const* in, float* d_out) const {
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] { return ocean::launch_query_velocity(v, ctx->vel, tile, iterations, in[0], count, d_out, ctx->stream); },
+                     "query_velocity");
+    }
+};
+
+// Workgroup tile of the grid kernel (grid.hip), nodes along x: the fastest of the shapes measured
+// (docs/MEASUREMENTS.md section 10) unless OCEAN_GRID_TILE names another (A/B).
+constexpr int kGridTileDefault = 32;
+
+// Surface grids: no inputs, the nodes follow from the six numbers; float[ny][nx][8], or float[ny][nx] in
+// heightfield mode.  One alignment rule for all modes, though heightfield mode writes one float per node.
+struct SurfaceGrid {
+    ocean_ctx* ctx;
+    int tile, mode, iterations;
+    float lod, x0, z0, dx, dz;
+    int nx, ny;
+    float* out;
+    size_t bytes;
+
+    int check(Form form) const {
+        if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+        if (!out) return fail(OCEAN_E_INVALID_ARG, "null output");
+        if (int r = check_tile(ctx, tile)) return r;
+        if (int r = check_mode(mode == OCEAN_GRID_VERTICES || mode == OCEAN_GRID_SURFACE || mode == OCEAN_GRID_HEIGHTFIELD,
+                               "grid", iterations, mode == OCEAN_GRID_VERTICES, "OCEAN_GRID_VERTICES"))
+            return r;
+        if (!std::isfinite(lod) || lod < 0.0f) return fail(OCEAN_E_INVALID_ARG, "lod must be finite and >= 0");
+        if (mode != OCEAN_GRID_VERTICES && lod != 0.0f)
+            return fail(OCEAN_E_INVALID_ARG, "OCEAN_GRID_SURFACE and OCEAN_GRID_HEIGHTFIELD take lod = 0");
+        if (int r = check_region(x0, z0, dx, dz, nx, ny)) return r;
+        const size_t want = (size_t)nx * (size_t)ny * (mode == OCEAN_GRID_HEIGHTFIELD ? 4 : 32);
+        if (bytes != want)
+            return fail(OCEAN_E_INVALID_ARG, "byte count " + std::to_string(bytes) + " != nx * ny * " +
+                                                 (mode == OCEAN_GRID_HEIGHTFIELD ? "4 = " : "32 = ") + std::to_string(want));
+        // the async form's result is written into a readback slot
+        if (form == Form::Async && bytes > stage_slot_bytes(ctx))
+            return fail(OCEAN_E_INVALID_ARG, "ocean_surface_grid_async: " + std::to_string(bytes) +
+                                                 " B exceed a readback slot of " + std::to_string(stage_slot_bytes(ctx)) + " B");
+        return OCEAN_OK;
+    }
+    StateRule state() const { return {"ocean_surface_grid", "surface grid of"}; }
+    StagedInputs inputs() const { return {nullptr, 0, {}}; }
+    size_t out_bytes() const { return bytes; }
+    const char* lacks() const { return nullptr; }
+    int launch(const float* const*, float* d_out) const {
+        const ocean::DevView v = ctx->view();
+        const int tw = ocean::grid_tile_supported(ctx->opt.grid_tile) ? ctx->opt.grid_tile : kGridTileDefault;
+        return timed(ctx, 2,
+                     [&] {
+                         return ocean::launch_surface_grid(v, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, tw, d_out,
+                                                           ctx->stream);
+                     },
+                     "surface_grid");
+    }
+};
+
+// Buoyant bodies: bodies float[count][10] and the hull float[probes][5] -> records float[count][8]; the staged
+// forms take at most OCEAN_BODY_MAX_BODIES.
+struct BodyBuoyancy {
+    ocean_ctx* ctx;
+    int tile, mode, iterations;
+    const float* hull;
+    int probes;
+    const float* bodies;
+    int count;
+    float* out;
+
+    int check(Form form) const {
+        if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+        if (!hull || !bodies || !out) return fail(OCEAN_E_INVALID_ARG, "null hull, bodies or output");
+        if (int r = check_tile(ctx, tile)) return r;
+        if (int r = check_query_mode(mode, iterations)) return r;
+        if (probes < 1 || probes > OCEAN_BODY_MAX_PROBES)
+            return fail(OCEAN_E_INVALID_ARG, "probes = " + std::to_string(probes) + " outside [1, OCEAN_BODY_MAX_PROBES]");
+        if (count < 0) return fail(OCEAN_E_INVALID_ARG, "negative body count");
+        if (form != Form::Device && count > OCEAN_BODY_MAX_BODIES)
+            return fail(OCEAN_E_INVALID_ARG, "body count " + std::to_string(count) + " > OCEAN_BODY_MAX_BODIES");
+        const uint64_t samples = (uint64_t)count * (uint64_t)probes;
+        if (samples > (uint64_t)OCEAN_BODY_MAX_SAMPLES)
+            return fail(OCEAN_E_INVALID_ARG, "count * probes = " + std::to_string(samples) + " > OCEAN_BODY_MAX_SAMPLES");
+        return OCEAN_OK;
+    }
+    StateRule state() const { return {"ocean_body_buoyancy", "buoyancy on"}; }
+    StagedInputs inputs() const {
+        return {"hull and bodies", 2, {{bodies, (size_t)count * 10 * 4}, {hull, (size_t)probes * 5 * 4}}};
+    }
+    size_t out_bytes() const { return (size_t)count * 8 * 4; }
+    const char* lacks() const { return count == 0 ? "bodies" : nullptr; }
+    int launch(const float* const* in, float* d_out) const {
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] {
+                         return ocean::launch_body_buoyancy(v, tile, mode, iterations, in[1], probes, in[0], count, d_out,
+                                                            ctx->stream);
+                     },
+                     "body_buoyancy");
+    }
+};
+
+// Body dynamics: the buoyant bodies with their motion float[count][6] and a drag law -> records float[count][16].
+// Its inputs outgrow the point queries' place in a slot (StageSlot), so they start behind its own records.
+struct BodyDynamics : BodyBuoyancy {
+    int law;
+    const float* motion;
+
+    int check(Form form) const {
+        if (int r = BodyBuoyancy::check(form)) return r;
+        if (!motion) return fail(OCEAN_E_INVALID_ARG, "null motion");
+        if (law != OCEAN_DRAG_LINEAR && law != OCEAN_DRAG_QUADRATIC) return fail(OCEAN_E_INVALID_ARG, "unknown drag law");
+        return OCEAN_OK;
+    }
+    StateRule state() const { return {"ocean_body_dynamics", "body dynamics on", Needs::Velocity}; }
+    StagedInputs inputs() const {
+        return {"hull, bodies and motion",
+                3,
+                {{bodies, (size_t)count * 10 * 4}, {motion, (size_t)count * 6 * 4}, {hull, (size_t)probes * 5 * 4}},
+                kDynamicsInputOffset};
+    }
+    size_t out_bytes() const { return (size_t)count * 16 * 4; }
+    int launch(const float* const* in, float* d_out) const {
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] {
+                         return ocean::launch_body_dynamics(v, ctx->vel, tile, mode, iterations, law, in[2], probes, in[0],
+                                                            in[1], count, d_out, ctx->stream);
+                     },
+                     "body_dynamics");
+    }
+};
+
+// Tile `tile`'s bounds records on the device, float[C][8], current on the ctx stream once this returns: the
+// two bounds launches (kind 2 of ocean_kernel_stats) are enqueued unless the cached records still match DISP.
+// (the caller has entered: OCEAN_ENTER)
+int ensure_bounds(ocean_ctx* ctx, int tile, const float** records) {
+    const size_t rec_floats = ctx->units() * 8;
+    if (!ctx->bounds_dev)
+        OCEAN_HIP(hipMalloc((void**)&ctx->bounds_dev, (rec_floats + ocean::bounds_partial_floats(ctx->C)) * sizeof(float)));
+    float* rec = ctx->bounds_dev + (size_t)tile * ctx->C * 8;
+    *records = rec;
+    if (ctx->bounds_valid[tile] && !ctx->disp_exposed) return OCEAN_OK;
+    const ocean::DevView v = ctx->view();
+    if (int r = timed(ctx, 2,
+                      [&] { return ocean::launch_surface_bounds(v, tile, ctx->bounds_dev + rec_floats, rec, ctx->stream); },
+                      "surface_bounds"))
+        return r;
+    ctx->bounds_valid[tile] = !ctx->disp_exposed;
+    return OCEAN_OK;
+}
+
+// Ray casts: rays float[count][8] -> records float[count][8]; the staged forms take at most OCEAN_RAY_MAX_RAYS.
+// The kernel runs behind the bounds launches where the air skip is on and the tile's bounds are stale.
+struct RayCast {
+    ocean_ctx* ctx;
+    int tile, iterations, steps, refine;
+    const float* rays;
+    int count;
+    float* out;
+
+    int check(Form form) const {
+        if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+        if (!rays || !out) return fail(OCEAN_E_INVALID_ARG, "null rays or output");
+        if (count < 0) return fail(OCEAN_E_INVALID_ARG, "negative ray count");
+        if (form != Form::Device && count > OCEAN_RAY_MAX_RAYS)
+            return fail(OCEAN_E_INVALID_ARG, "ray count " + std::to_string(count) + " > OCEAN_RAY_MAX_RAYS");
+        if (steps < 1 || steps > OCEAN_RAY_MAX_STEPS)
+            return fail(OCEAN_E_INVALID_ARG, "steps = " + std::to_string(steps) + " outside [1, OCEAN_RAY_MAX_STEPS]");
+        const uint64_t samples = (uint64_t)count * (uint64_t)steps;
+        if (samples > (uint64_t)OCEAN_RAY_MAX_SAMPLES)
+            return fail(OCEAN_E_INVALID_ARG, "count * steps = " + std::to_string(samples) + " > OCEAN_RAY_MAX_SAMPLES");
+        if (int r = check_iterations(iterations)) return r;
+        if (refine < 0 || refine > 32) return fail(OCEAN_E_INVALID_ARG, "refine must be in [0, 32]");
+        return check_tile(ctx, tile);
+    }
+    StateRule state() const { return {"ocean_raycast", "ray cast on"}; }
+    StagedInputs inputs() const { return {"rays", 1, {{rays, (size_t)count * 8 * 4}}}; }
+    size_t out_bytes() const { return (size_t)count * 8 * 4; }
+    const char* lacks() const { return count == 0 ? "rays" : nullptr; }
+    int launch(const float* const* in, float* d_out) const {
+        const float* bounds = nullptr;
+        if (ctx->opt.ray_bounds)
+            if (int r = ensure_bounds(ctx, tile, &bounds)) return r;
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] {
+                         return ocean::launch_raycast(v, tile, iterations, steps, refine, bounds, in[0], count, d_out,
+                                                      ctx->stream);
+                     },
+                     "raycast");
+    }
+};
+
+// Whitecap emitters: no inputs; (capacity + 1) records of 32 B.  What does not need the context is checked
+// first, the _device form's alignment with it, so that a host learns of a bad argument whatever its context
+// is.  The three kernels run over the context's scratch, which the first call allocates.
+struct Whitecaps {
+    ocean_ctx* ctx;
+    int tile;
+    float lod, threshold, x0, z0, dx, dz;
+    int nx, ny, capacity;
+    float* out;
+    size_t bytes;
+
+    int check(Form form) const {
+        if (!out) return fail(OCEAN_E_INVALID_ARG, "null output");
+        if (!std::isfinite(lod) || lod < 0.0f) return fail(OCEAN_E_INVALID_ARG, "lod must be finite and >= 0");
+        if (!std::isfinite(threshold)) return fail(OCEAN_E_INVALID_ARG, "threshold must be finite");
+        if (int r = check_region(x0, z0, dx, dz, nx, ny)) return r;
+        if (capacity < 1 || capacity > OCEAN_WHITECAP_MAX_RECORDS)
+            return fail(OCEAN_E_INVALID_ARG, "capacity = " + std::to_string(capacity) + " outside [1, OCEAN_WHITECAP_MAX_RECORDS]");
+        const size_t want = ((size_t)capacity + 1) * 32;
+        if (bytes != want)
+            return fail(OCEAN_E_INVALID_ARG, "byte count " + std::to_string(bytes) + " != (capacity + 1) * 32 = " +
+                                                 std::to_string(want));
+        if (form == Form::Device)
+            if (int r = check_aligned(state().entry, inputs(), out)) return r;
+        if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+        return check_tile(ctx, tile);
+    }
+    StateRule state() const { return {"ocean_whitecaps", "whitecaps of", Needs::Turb}; }
+    StagedInputs inputs() const { return {nullptr, 0, {}}; }
+    size_t out_bytes() const { return bytes; }
+    const char* lacks() const { return nullptr; }
+    int launch(const float* const*, float* d_out) const {
+        if (!ctx->whitecap_dev) OCEAN_HIP(hipMalloc(&ctx->whitecap_dev, ocean::whitecap_scratch_bytes()));
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] {
+                         return ocean::launch_whitecaps(v, ctx->vel, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity,
+                                                        ctx->whitecap_dev, d_out, ctx->stream);
+                     },
+                     "whitecaps");
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int ocean_query_surface_device(ocean_ctx* ctx, int tile, int mode, int iterations, const float* points, int count,
+                               float* out) {
+    return device_form(SurfaceQuery{ctx, tile, mode, iterations, points, count, out});
+}
+
+int ocean_query_surface(ocean_ctx* ctx, int tile, int mode, int iterations, const float* points, int count,
+                        float* out) {
+    return host_form(SurfaceQuery{ctx, tile, mode, iterations, points, count, out});
+}
+
+int ocean_query_surface_async(ocean_ctx* ctx, int tile, int mode, int iterations, const float* points, int count,
+                              float* dst, ocean_readback** out) {
+    return async_form(SurfaceQuery{ctx, tile, mode, iterations, points, count, dst}, out, "out");
+}
+
+int ocean_query_velocity_device(ocean_ctx* ctx, int tile, int iterations, const float* points, int count, float* out) {
+    return device_form(VelocityQuery{{ctx, tile, OCEAN_QUERY_SURFACE, iterations, points, count, out}});
+}
+
+int ocean_query_velocity(ocean_ctx* ctx, int tile, int iterations, const float* points, int count, float* out) {
+    return host_form(VelocityQuery{{ctx, tile, OCEAN_QUERY_SURFACE, iterations, points, count, out}});
+}
+
+int ocean_query_velocity_async(ocean_ctx* ctx, int tile, int iterations, const float* points, int count, float* dst,
+                               ocean_readback** req) {
+    return async_form(VelocityQuery{{ctx, tile, OCEAN_QUERY_SURFACE, iterations, points, count, dst}}, req);
+}
+
+int ocean_surface_grid_device(ocean_ctx* ctx, int tile, int mode, int iterations, float lod, float x0, float z0,
+                              float dx, float dz, int nx, int ny, float* out, size_t bytes) {
+    return device_form(SurfaceGrid{ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out, bytes});
+}
+
+int ocean_surface_grid(ocean_ctx* ctx, int tile, int mode, int iterations, float lod, float x0, float z0, float dx,
+                       float dz, int nx, int ny, float* out, size_t bytes) {
+    return host_form(SurfaceGrid{ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out, bytes});
+}
+
+int ocean_surface_grid_async(ocean_ctx* ctx, int tile, int mode, int iterations, float lod, float x0, float z0,
+                             float dx, float dz, int nx, int ny, float* out, size_t bytes, ocean_readback** req) {
+    return async_form(SurfaceGrid{ctx, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out, bytes}, req);
+}
+
+int ocean_body_buoyancy_device(ocean_ctx* ctx, int tile, int mode, int iterations, const float* hull, int probes,
+                               const float* bodies, int count, float* out) {
+    return device_form(BodyBuoyancy{ctx, tile, mode, iterations, hull, probes, bodies, count, out});
+}
+
+int ocean_body_buoyancy(ocean_ctx* ctx, int tile, int mode, int iterations, const float* hull, int probes,
+                        const float* bodies, int count, float* out) {
+    return host_form(BodyBuoyancy{ctx, tile, mode, iterations, hull, probes, bodies, count, out});
+}
+
+int ocean_body_buoyancy_async(ocean_ctx* ctx, int tile, int mode, int iterations, const float* hull, int probes,
+                              const float* bodies, int count, float* out, ocean_readback** req) {
+    return async_form(BodyBuoyancy{ctx, tile, mode, iterations, hull, probes, bodies, count, out}, req);
+}
+
+int ocean_body_dynamics_device(ocean_ctx* ctx, int tile, int mode, int iterations, int law, const float* hull, int probes,
+                               const float* bodies, const float* motion, int count, float* out) {
+    return device_form(BodyDynamics{{ctx, tile, mode, iterations, hull, probes, bodies, count, out}, law, motion});
+}
+
+int ocean_body_dynamics(ocean_ctx* ctx, int tile, int mode, int iterations, int law, const float* hull, int probes,
+                        const float* bodies, const float* motion, int count, float* out) {
+    return host_form(BodyDynamics{{ctx, tile, mode, iterations, hull, probes, bodies, count, out}, law, motion});
+}
+
+int ocean_body_dynamics_async(ocean_ctx* ctx, int tile, int mode, int iterations, int law, const float* hull, int probes,
+                              const float* bodies, const float* motion, int count, float* out, ocean_readback** req) {
+    return async_form(BodyDynamics{{ctx, tile, mode, iterations, hull, probes, bodies, count, out}, law, motion}, req);
+}
+
+int ocean_raycast_device(ocean_ctx* ctx, int tile, int iterations, int steps, int refine, const float* rays, int count,
+                         float* out) {
+    return device_form(RayCast{ctx, tile, iterations, steps, refine, rays, count, out});
+}
+
+int ocean_raycast(ocean_ctx* ctx, int tile, int iterations, int steps, int refine, const float* rays, int count,
+                  float* out) {
+    return host_form(RayCast{ctx, tile, iterations, steps, refine, rays, count, out});
+}
+
+int ocean_raycast_async(ocean_ctx* ctx, int tile, int iterations, int steps, int refine, const float* rays, int count,
+                        float* dst, ocean_readback** req) {
+    return async_form(RayCast{ctx, tile, iterations, steps, refine, rays, count, dst}, req);
+}
+
+int ocean_whitecaps_device(ocean_ctx* ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz,
+                           int nx, int ny, int capacity, float* out, size_t bytes) {
+    return device_form(Whitecaps{ctx, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, out, bytes});
+}
+
+int ocean_whitecaps(ocean_ctx* ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz, int nx,
+                    int ny, int capacity, float* out, size_t bytes) {
+    return host_form(Whitecaps{ctx, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, out, bytes});
+}
+
+int ocean_whitecaps_async(ocean_ctx* ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz,
+                          int nx, int ny, int capacity, float* out, size_t bytes, ocean_readback** req) {
+    return async_form(Whitecaps{ctx, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, out, bytes}, req);
+}
+
+// World sampling has no async form and enters the device scope before its checks.
+// (the caller has entered: OCEAN_ENTER)
+static int check_sample(ocean_ctx* ctx, int tile, const float* pts, int count, float* out) {
+    if (int r = check_tile(ctx, tile)) return r;
+    if (count < 0) return fail(OCEAN_E_INVALID_ARG, "negative point count");
+    if (count > 0 && (!pts || !out)) return fail(OCEAN_E_INVALID_ARG, "null points or output");
+    // the cascade constants (wavelengths) the sampler divides by exist only after init
+    if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, "ocean_init_spectrum must precede ocean_sample_world");
+    return OCEAN_OK;
+}
+
+int ocean_sample_world_device(ocean_ctx* ctx, int tile, const float* points, int count, float* out) {
+    OCEAN_ENTER(ctx);
+    if (int r = check_sample(ctx, tile, points, count, out)) return r;
+    if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, "world sampling of a column-parity shard (half the columns)");
+    if (int r = check_aligned("ocean_sample_world", {"points", 1, {{points, 0}}}, out)) return r;
+    const ocean::DevView v = ctx->view();
+    return timed(ctx, 2, [&] { return ocean::launch_sample_world(v, tile, points, count, out, ctx->stream); },
+                 "sample_world");
+}
+
+int ocean_sample_world(ocean_ctx* ctx, int tile, const float* points, int count, float* out) {
+    OCEAN_ENTER(ctx);
+    if (int r = check_sample(ctx, tile, points, count, out)) return r;
+    if (count == 0) return OCEAN_OK;
+    return run_staged(ctx, "ocean_sample_world", {"points", 1, {{points, (size_t)count * 3 * 4}}}, out,
+                      (size_t)count * 12 * 4, [&](const float* const* d_in, float* d_out) {
+                          return ocean_sample_world_device(ctx, tile, d_in[0], count, d_out);
+                      });
+}
+
+// The surface bounds stage nothing: the records are copied out of the context's own.
+static int check_bounds(ocean_ctx* ctx, int tile, const float* out, size_t bytes) {
+    if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+    if (!out) return fail(OCEAN_E_INVALID_ARG, "null output");
+    if (int r = check_tile(ctx, tile)) return r;
+    if (bytes != (size_t)ctx->C * 32)
+        return fail(OCEAN_E_INVALID_ARG, "byte count " + std::to_string(bytes) + " != cascades * 32 = " +
+                                             std::to_string((size_t)ctx->C * 32));
+    return OCEAN_OK;
+}
+
+static const StateRule kBoundsState{"ocean_surface_bounds", "surface bounds of"};
+
+int ocean_surface_bounds_device(ocean_ctx* ctx, int tile, float* out, size_t bytes) {
+    if (int r = check_bounds(ctx, tile, out, bytes)) return r;
+    if (int r = check_aligned(kBoundsState.entry, {nullptr, 0, {}}, out)) return r;
+    if (int r = check_state(ctx, kBoundsState)) return r;
+    OCEAN_ENTER(ctx);
+    const float* rec = nullptr;
+    if (int r = ensure_bounds(ctx, tile, &rec)) return r;
+    OCEAN_HIP(hipMemcpyAsync(out, rec, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return OCEAN_OK;
+}
+
+int ocean_surface_bounds(ocean_ctx* ctx, int tile, float* out, size_t bytes) {
+    if (int r = check_bounds(ctx, tile, out, bytes)) return r;
+    if (int r = check_state(ctx, kBoundsState)) return r;
+    OCEAN_ENTER(ctx);
+    const float* rec = nullptr;
+    if (int r = ensure_bounds(ctx, tile, &rec)) return r;
+    OCEAN_HIP(hipMemcpyAsync(out, rec, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    OCEAN_HIP(hipStreamSynchronize(ctx->stream));
+    return OCEAN_OK;
+}
+
+}  // extern "C"

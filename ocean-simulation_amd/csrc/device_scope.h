@@ -2,7 +2,7 @@
 // for its own span and gives the calling thread its own current device back on return, so a host that
 // drives several contexts from one thread, or runs torch in the same process, never sees its current
 // device move.  The runtime's get / set pair is a template parameter: the library instantiates it with
-// hipGetDevice / hipSetDevice (ocean_abi.cpp), and tests/test_device_scope.py with a two-device stub on
+// hipGetDevice / hipSetDevice (abi_internal.h), and tests/test_device_scope.py with a two-device stub on
 // the CPU, so the restore branch is exercised without a second GPU.
 //   Api::get(int* device) -> 0 on success;  Api::set(int device) -> 0 on success, else the error code.
 #pragma once

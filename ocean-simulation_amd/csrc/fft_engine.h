@@ -78,7 +78,7 @@ __device__ __forceinline__ void store4_nt(float4* p, float4 x) {
 // k < Ns, r < R (r-major: lanes with consecutive k read consecutive entries,
 // bank-conflict free; a butterfly's R-1 twiddles sit at compile-time strides);
 // stages concatenated.  Built on the host in double precision
-// at tw + N + 128 (ocean_abi.cpp).
+// at tw + N + 128 (abi_context.cpp).
 template <int N, int R0 = 16>
 struct StageTw {
     static constexpr int S = n_stages(N, R0);

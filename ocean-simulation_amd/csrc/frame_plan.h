@@ -2,7 +2,7 @@
 // choice below can be read off a printed plan (tests/frame_plan_test.cpp builds it alone).
 //
 // A frame is a list of timed launches.  plan_frame() walks it in launch order and hands each step to the
-// caller; ocean_abi.cpp step_fused turns a step into a view of the context and one launch_* call.  What is
+// caller; abi_frame.cpp step_fused turns a step into a view of the context and one launch_* call.  What is
 // decided here, from the shape, the knobs and a few flags of the context:
 //   - three-plane or four-plane frame (use_q, q_planes) and the row pass of the four-plane one;
 //   - unit chunks (chunk_units) and where a chunk's intermediate sits (inter_at_base);
@@ -18,7 +18,7 @@
 // and a pruned pass BQ reads no row its pass AQ did not write, so neither depends on what the other left there.
 // ocean_create sizes the intermediate, h0k, the side arrays and the prune tables with the same functions, so
 // the sizing and the schedule cannot drift apart.  Nothing here reads the environment: the knobs arrive as
-// values (ocean_abi.cpp ocean_options::from_env).
+// values (abi_internal.h ocean_options::from_env).
 #pragma once
 
 #include <algorithm>

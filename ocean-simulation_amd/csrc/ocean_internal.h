@@ -1,4 +1,4 @@
-// Internal declarations shared by the C-ABI layer (ocean_abi.cpp) and the HIP kernel translation
+// Internal declarations shared by the C-ABI layer (abi_*.cpp) and the HIP kernel translation
 // units (every csrc/*.hip): the launch wrapper, the device view of a context and one launch_*
 // function per kernel family.  Not part of the ABI.
 #pragma once
@@ -21,9 +21,9 @@ struct LaunchEvents {
     hipEvent_t start, stop;
     bool launched;
 };
-LaunchEvents*& launch_events();  // thread-local slot, ocean_abi.cpp
+LaunchEvents*& launch_events();  // thread-local slot, launch.cpp
 // Host pointer of the kernel this thread launched last (ocean_kernel_name reports its symbol).
-const void*& last_kernel();  // thread-local slot, ocean_abi.cpp
+const void*& last_kernel();  // thread-local slot, launch.cpp
 
 template <class F, class... Args>
 inline void launch(F kernel, dim3 grid, dim3 block, uint32_t shmem, hipStream_t s, Args... args) {
@@ -94,7 +94,7 @@ struct SpectrumParams {
     float wind_speed, wind_dir_x, wind_dir_y, gravity, fetch, depth;
 };
 
-// spectrum.hip
+// launch.cpp
 // Resident workgroups per CU of `kernel` at `threads` lanes (hipOccupancyMaxActiveBlocksPerMultiprocessor,
 // at least 1) and the device's CU count, cached per device (and kernel): the queries cost microseconds
 // of host time, paid once instead of per launch (small jobs issue a launch every few microseconds).

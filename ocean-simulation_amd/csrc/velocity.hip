@@ -2,7 +2,7 @@
 // say where it is.  The velocity is the same inverse transform applied to dh/dt, so nothing is differenced
 // in time: k_evolve_velocity forms dh/dt = i omega (A - B) from the resident H0 and WAVES with the frame's
 // own phase factor and packs it as the reference packs h into DxDz and DyDxz (spectrum_math.h planes_of),
-// the two planes go through the operator IFFT (fft2.hip, launched by ocean_abi.cpp), and k_pack_velocity
+// the two planes go through the operator IFFT (fft2.hip, launched by abi_frame.cpp), and k_pack_velocity
 // interleaves them into the VEL texture.  With the reference's packing VEL.xyz is the exact time derivative
 // of DISP.xyz as this library computes it (include/ocean/ocean.h states every operation).
 //

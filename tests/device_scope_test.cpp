@@ -1,8 +1,8 @@
 // CPU test of the C ABI's device rule (ocean-simulation_amd/csrc/device_scope.h) over a two-device stub
 // runtime: the WaterBody lifecycle's entry points -- create, set_params, init, step, read_async,
-// readback release, destroy -- each run inside the scope exactly as ocean_abi.cpp wraps them, with the
-// caller's thread on device 0 or 1 and the context on device 0 or 1.  Inside every call the context's
-// device must be current; after every call the caller's own device must be current again, also when
+// readback release, destroy -- each run inside the scope exactly as the C-ABI layer wraps them (abi_internal.h
+// OCEAN_ENTER), with the caller's thread on device 0 or 1 and the context on device 0 or 1.  Inside every call
+// the context's device must be current; after every call the caller's own device must be current again, also when
 // the runtime refuses to switch.  Built and run by tests/test_device_scope.py (g++, no HIP).
 //   device_scope_test            exit 0 when every check holds, 1 (with the failed check) otherwise
 #include <cstdio>
@@ -51,7 +51,7 @@ struct Readback {
     int device;
 };
 
-// An entry point as ocean_abi.cpp writes one: the scope first, the work inside it.  `work` checks that
+// An entry point as the C-ABI layer writes one: the scope first, the work inside it.  `work` checks that
 // the context's device is current for the call's whole span; the return value is the call's status.
 template <class Work>
 int entry(int device, Work&& work) {

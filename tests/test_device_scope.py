@@ -6,8 +6,10 @@ caller's device).  Here the rule's implementation (ocean-simulation_amd/csrc/dev
 the library instantiates over hipGetDevice / hipSetDevice) runs over a two-device stub runtime through
 the WaterBody lifecycle's entry points (tests/device_scope_test.cpp): caller on 1 with the context on 0,
 the reverse, the same device, a refused switch and nested calls.  The test also checks that it would
-catch a broken scope (mutants of the header must fail it), and that every entry point of ocean_abi.cpp
-that touches the device enters through the scope."""
+catch a broken scope (mutants of the header must fail it), and that every entry point of the C-ABI layer
+(csrc/*.cpp) that touches the device enters through the scope, in its own body or in the form of a point
+consumer it returns (abi_consumers.cpp: device_form, host_form, async_form)."""
+import glob
 import os
 import re
 import shutil
@@ -58,34 +60,47 @@ def test_stub_test_catches_broken_scope(tmp_path, mutant):
     assert r.returncode != 0 and "FAIL" in r.stdout, f"mutant {mutant} survived:\n{r.stdout}"
 
 
+def _sources():
+    return "\n".join(open(p).read() for p in sorted(glob.glob(os.path.join(CSRC, "*.cpp"))))
+
+
+def _body(src, name):
+    m = re.search(r"^[a-z][\w\s\*]*\b" + name + r"\([^;{]*\)\s*\{", src, flags=re.M)
+    assert m, f"{name} is not defined in csrc/*.cpp"
+    i, depth = m.end(), 1
+    while depth:
+        depth += {"{": 1, "}": -1}.get(src[i], 0)
+        i += 1
+    return src[m.end():i]
+
+
 def _entry_bodies():
-    src = open(os.path.join(CSRC, "ocean_abi.cpp")).read()
+    src = _sources()
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ocean", "ocean.h")).read(), flags=re.S)
     names = sorted(set(re.findall(r"\b(ocean_[a-z0-9_]+)\s*\(", hdr)))
-    bodies = {}
-    for name in names:
-        m = re.search(r"^[a-z][\w\s\*]*\b" + name + r"\([^;{]*\)\s*\{", src, flags=re.M)
-        assert m, f"{name} declared in ocean.h but not defined in ocean_abi.cpp"
-        i, depth = m.end(), 1
-        while depth:
-            depth += {"{": 1, "}": -1}.get(src[i], 0)
-            i += 1
-        bodies[name] = src[m.end():i]
-    return bodies
+    return {name: _body(src, name) for name in names}
+
+
+# The three forms of a point consumer: an entry that returns one does its device work there.
+FORMS = ("device_form", "host_form", "async_form")
 
 
 # What puts work on, or allocates on, a device: any HIP call except the event queries (events carry their
 # device) and pinned host memory (no device), a kernel launch, or the library's step / timing helpers.
 DEVICE_WORK = re.compile(r"\bhip(?!Event(?:Query|Synchronize|ElapsedTime)\b|Host(?:Malloc|Free)\b)[A-Z]\w*\(|\blaunch|\bstep_\w+\(|"
-                         r"\bfold_pending\(|\bread_impl\(|\bwrite_impl\(")
+                         r"\bfold_pending\(|\bread_impl\(|\bwrite_impl\(|\b(?:device|host|async)_form\(")
 
 
 def test_every_device_entry_enters_through_the_scope():
     bodies = _entry_bodies()
     assert len(bodies) >= 38
+    src = _sources()
+    form_in_scope = {form: "OCEAN_ENTER(" in _body(src, form) for form in FORMS}
+    assert all(form_in_scope.values()), form_in_scope
     scoped = 0
     for name, body in bodies.items():
-        in_scope = "OCEAN_ENTER(" in body or "DeviceScope " in body
+        in_scope = ("OCEAN_ENTER(" in body or "DeviceScope " in body
+                    or any(form_in_scope[form] and re.search(r"\b" + form + r"\(", body) for form in FORMS))
         if DEVICE_WORK.search(body) or in_scope:
             assert in_scope, f"{name} touches the device outside the scope"
             scoped += 1

@@ -6,7 +6,7 @@ The host launches min(items, CUs x resident workgroups per CU) workgroups and ea
 stay at or near that grid, so a workgroup handles one item, at most two, and the code that carries state from one
 item to the next hardly runs there: the register rings two steps ahead, the h0k pair and table key read one item
 ahead, d0 staged through LDS, the foam prefetch, the XCD regrouping, the live extent of the next item's unit.
-OCEAN_MAX_GROUPS=k caps every such grid at k workgroups (a schedule knob: ocean_abi.cpp ocean_options), and then
+OCEAN_MAX_GROUPS=k caps every such grid at k workgroups (a schedule knob: abi_internal.h ocean_options), and then
 those loops iterate at the smallest shapes:
 
   k = 1  one workgroup crosses every unit boundary in order;
