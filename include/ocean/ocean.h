@@ -75,7 +75,9 @@ extern "C" {
  *      Added later within version 4 in the same way: OCEAN_DRAG_LINEAR, OCEAN_DRAG_QUADRATIC, ocean_body_dynamics,
  *      ocean_body_dynamics_device, ocean_body_dynamics_async.
  *      Added later within version 4 in the same way: OCEAN_WHITECAP_MAX_RECORDS, ocean_whitecaps,
- *      ocean_whitecaps_device, ocean_whitecaps_async. */
+ *      ocean_whitecaps_device, ocean_whitecaps_async.
+ *      Added later within version 4 in the same way: OCEAN_CAMERA_HITS, OCEAN_CAMERA_RANGE, OCEAN_CAMERA_COLOR,
+ *      ocean_camera, ocean_camera_device, ocean_camera_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -770,10 +772,134 @@ int ocean_whitecaps_device(ocean_ctx *ctx, int tile, float lod, float threshold,
 int ocean_whitecaps_async(ocean_ctx *ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz,
                           int nx, int ny, int capacity, float *out, size_t bytes, ocean_readback **req);
 
+/* Camera views: an image of the sea.  The fragment stage of Water.shader (:336-374) is what the reference's
+ * textures exist for, and a host on a device without a display pipeline has no picture of them: with ocean_raycast
+ * it would build width x height rays on the CPU, upload and read back 32 B per pixel, sample DERIV and TURB again
+ * at a distance-dependent lod and shade on the CPU.  Maritime camera and lidar sensors, regression pictures,
+ * previews and training data need the image itself.  Here the rays follow from a camera of fourteen numbers, as a
+ * grid follows from six; the march, the sample and the shading are one kernel, and 4, 16 or 32 B per pixel come
+ * back.
+ *
+ * `camera` is float[OCEAN_CAMERA_FLOATS] = (o.x, o.y, o.z, d00.x, d00.y, d00.z, du.x, du.y, du.z, dv.x, dv.y, dv.z,
+ * t0, t1): the eye, the unnormalised direction through pixel (0, 0), its change per pixel along a row and along a
+ * column, and the parameter interval every ray searches.  Pixel (i, j), i < width and j < height, is element
+ * k = j * width + i of `out`.  All arithmetic is fp32, one rounding per operation in the order written (no fused
+ * multiply-add); sqrtf and / are correctly rounded.
+ *       raw = (d00 + (float)i * du) + (float)j * dv                     (componentwise)
+ *       len = sqrtf((raw.x * raw.x + raw.y * raw.y) + raw.z * raw.z)
+ *       d   = (raw.x / len, raw.y / len, raw.z / len)
+ * The pixel's ray is (o, d, t0, t1), and R_k is the 8-float record of ocean_raycast for that ray with the same
+ * `tile`, `iterations` (K), `steps` (S) and `refine` (B), bit for bit.  The air skip, the bounds launches on a
+ * context whose bounds are stale and OCEAN_RAY_BOUNDS=0 are exactly ocean_raycast's.  The library does not inspect
+ * what the camera spans: len = 0 gives unspecified numbers (never an access outside the textures).
+ *
+ *   OCEAN_CAMERA_HITS:  out[8k + 0..7] = R_k: the G-buffer, 32 B per pixel.
+ *   OCEAN_CAMERA_RANGE: out[k] = R_k[0] after a hit or a submerged start, +INFINITY after a miss: a range or lidar
+ *                       image, 4 B per pixel.
+ *   OCEAN_CAMERA_COLOR: out[4k + 0..3] = (r, g, b, (float)status): the shaded picture, 16 B per pixel.
+ * `bytes` must equal width * height * 32, 4 or 16.  `material` is read in colour mode only and may be NULL in the
+ * other two.
+ *
+ * `material` is float[OCEAN_CAMERA_MATERIAL_FLOATS]; the names in brackets are Water.shader's properties:
+ *       [0..2]   C      the water colour (_Color)
+ *       [3]      R0     the reflectance at normal incidence (the shader's R0: ((1 - 1.333) / (1 + 1.333))^2)
+ *       [4]      FE     the Fresnel exponent 5 exp(-2.69 roughness)                 (:353)
+ *       [5]      FD     the Fresnel divisor 1 + 22.7 roughness^1.5                  (:353)
+ *       [6]      rho    the roughness (_Roughness)
+ *       [7]      lod_slope: levels of detail per unit of distance along the ray (the role of _MaxLODLevel /
+ *                _MaxTesselationDistance, :319-320)
+ *       [8], [9] EX, EY (_EX, _EY)
+ *       [10]     ke     the environment reflection strength (_EnvironmentReflectionStrength)
+ *       [11]     ks     the sun reflection strength (_SunReflectionStrength)
+ *       [12..14] SS     the subsurface colour times the subsurface intensity (_SubsurfaceScatteringColor.rgb *
+ *                       _SubsurfaceScatteringIntensity): the bindings take the two apart and multiply once
+ *       [15]     FT     the foam threshold (_FoamThreshold)
+ *       [16..18] FC     the foam colour (_FoamColor)
+ *       [19]     FB     the foam blending (_FoamBlending)
+ *       [20..22] L      the direction towards the light, unit (the caller keeps it so)
+ *       [23..25] LC     the light's colour (_MainLightColor)
+ *       [26..28] HZ     the sky's colour at and below the horizon
+ *       [29..31] ZN     the sky's colour at the zenith
+ * FE and FD are the material's only transcendentals: whoever builds the material computes them once, and the
+ * kernel evaluates none per material.
+ *
+ * The colour is the fragment stage restated in fp32 in the order written, with these definitions of the library's
+ * own where the shader reads what a headless host does not have:
+ *   - view and lod: V = -d, and the pixel's lod = R_k[0] * lod_slope (the distance along the ray in place of
+ *     :319-320's distance to the camera);
+ *   - the surface sample is taken at the point the fixed point ended on: with q = o + R_k[0] * d and p_K the
+ *     fixed point of OCEAN_QUERY_SURFACE for (q.x, q.z) after K steps, S = ocean_sample_world's result for
+ *     (p_K.x, p_K.z, lod): n = S[8..10], foam = S[3], eta = S[1].  DERIV and TURB use `lod` exactly as
+ *     ocean_sample_world does (trilinear on OCEAN_F_MIPS contexts, level 0 otherwise, a lod <= 0 is level 0);
+ *   - no shadow map: the shadow factor is 1, so the sun's lobes are not attenuated and the shadow lerp of :370
+ *     (whose weight is then 0) is left out, _ShadowsColor and _ShadowsIntensity with it;
+ *   - no opaque or depth texture: UnderwaterView is its fog limit, the water colour;
+ *   - no cubemap: sky(r) = HZ + saturate(r.y) * (ZN - HZ), per channel.
+ * With sat(x) = fminf(fmaxf(x, 0), 1), dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z, pi = (float)3.14159265358979
+ * and tiny = 1.175494351e-38f, a HIT pixel is
+ *       hr  = V + L;   h = hr / sqrtf(dot(hr, hr))                                  (the halfway vector, three divisions)
+ *       ndv = dot(n, V);  ndl = dot(n, L);  hdv = dot(h, V);  hdn = dot(h, n)
+ *       F   = R0 + ((1 - R0) * powf(1 - sat(ndv), FE)) / FD                         (:353)
+ *       x   = 1 - sat(hdv);   FH = R0 + (1 - R0) * (((x * x) * (x * x)) * x)        (:354)
+ *       s   = fmaxf(0, dot(L, d));   g = fmaxf(0, eta) * ((s * s) * (s * s))        (subsurface: dot(L, -V), :176)
+ *       refraction_c = C_c + (g * SS_c) * LC_c
+ *       ry  = (2 * ndv) * n.y - V.y                                                 (-reflect(V, n), its y)
+ *       env_c = (sky(ry)_c * pi) * ke                                               (:187)
+ *     if L.y > 0 (else cook_c = 0 and ash_c = 0, :215 and :225):
+ *       den = fmaxf(1 - h.z * h.z, tiny);  c2 = fmaxf((h.x * h.x) / den, 0);  s2 = fmaxf((h.y * h.y) / den, 0)
+ *       nu  = (EX * 10) * (1 - rho);   nv = (EY * 10) * (1 - rho)
+ *       D   = sqrtf((nu + 1) * (nv + 1)) * powf(fmaxf(hdn, 0), nu * c2 + nv * s2)
+ *       A   = fmaxf((D * FH) / fmaxf(((8 * pi) * hdv) * fmaxf(ndv, ndl), tiny), 0);   ash_c = LC_c * A     (:226-230)
+ *       a2  = (rho * rho) * (rho * rho);   q = (sat(hdn) * sat(hdn)) * (a2 - 1) + 1
+ *       N   = fmaxf(a2 / fmaxf(pi * (q * q), tiny), 0);   k = rho / 2                                      (:192-196)
+ *       G   = fmaxf((sat(ndv) / fmaxf(sat(ndv) * (1 - k) + k, tiny)) * (sat(ndl) / fmaxf(sat(ndl) * (1 - k) + k, tiny)), 0)
+ *       cook_c = ((LC_c * N) * G) / fmaxf((8 * sat(ndv)) * sat(ndl), tiny)                                 (:219)
+ *     then
+ *       reflections_c = env_c + (cook_c + ash_c * sat(ndv)) * ks                    (:368)
+ *       e_c = refraction_c + F * (reflections_c - refraction_c)                     (:370)
+ *       if foam >= FT:  e_c = e_c + FB * (FC_c - e_c)                               (:371)
+ *       (r, g, b) = e
+ * The shader's quirks are kept: the Ashikhmin-Shirley angles are taken in the world's x and y, FH feeds only that
+ * lobe, and the lobes are clamped, not the sum.  Integer powers are the multiplications written; the two powf are
+ * the only operations whose last bits depend on the device's math library.  A MISS pixel is sky(d.y) and a
+ * SUBMERGED pixel is C, both with their status in the fourth channel.  A DISPLACEMENT_ONLY context shades with
+ * n = (0, 1, 0) and never foams, as the queries report it.
+ *
+ * ocean_camera: `out` is a host buffer; blocks, as ocean_surface_grid.
+ * ocean_camera_device: `out` is a device pointer, 16-B aligned in every mode (else OCEAN_E_INVALID_ARG); async on
+ * the ctx stream, ordered after the queued steps.
+ * ocean_camera_async: `out` is a host destination (pinned, ocean_host_alloc, for a truly asynchronous copy).  The
+ * image is computed into a readback slot on the ctx stream, after the steps queued so far and before later ones,
+ * and copied on the copy stream like an ocean_read_async slice, with the same ocean_readback_status / _wait /
+ * _release / _copy_ms.  The result must fit a slot: bytes <= max(N * N * 16, OCEAN_QUERY_MAX_POINTS * 40), else
+ * OCEAN_E_INVALID_ARG.  *req is NULL after every failure.
+ * In all three `camera` and `material` are host arrays, consumed before the call returns and passed to the kernel
+ * by value: nothing is staged.
+ * All three: OCEAN_E_INVALID_ARG, checked before any device call, for a null ctx, `camera`, `out` or `req`, a null
+ * `material` in colour mode, a tile out of range, an unknown mode, iterations outside [0, 16], steps outside
+ * [1, OCEAN_RAY_MAX_STEPS], refine outside [0, 32], a non-finite camera value or a non-finite value of a `material` that is passed (in any mode),
+ * width < 1 or height < 1, width * height > OCEAN_CAMERA_MAX_PIXELS, width * height * steps >
+ * OCEAN_CAMERA_MAX_SAMPLES (both in 64 bits), a wrong `bytes`, a misaligned device `out` or an async result larger
+ * than a slot; then OCEAN_E_STATE before ocean_init_spectrum and OCEAN_E_UNSUPPORTED on a column-parity context (as
+ * the queries).  The launch counts as kind 2 of ocean_kernel_stats / ocean_kernel_name. */
+#define OCEAN_CAMERA_HITS 0
+#define OCEAN_CAMERA_RANGE 1
+#define OCEAN_CAMERA_COLOR 2
+#define OCEAN_CAMERA_FLOATS 14
+#define OCEAN_CAMERA_MATERIAL_FLOATS 32
+#define OCEAN_CAMERA_MAX_PIXELS (1 << 22)
+#define OCEAN_CAMERA_MAX_SAMPLES (1 << 28)
+int ocean_camera(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine, const float *camera,
+                 const float *material, int width, int height, float *out, size_t bytes);
+int ocean_camera_device(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine, const float *camera,
+                        const float *material, int width, int height, float *out, size_t bytes);
+int ocean_camera_async(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine, const float *camera,
+                       const float *material, int width, int height, float *out, size_t bytes, ocean_readback **req);
+
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
  * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async /
  * ocean_body_buoyancy_async / ocean_query_velocity_async / ocean_raycast_async / ocean_body_dynamics_async /
- * ocean_whitecaps_async request records HIP timing events around its device-to-host copy, for
+ * ocean_whitecaps_async / ocean_camera_async request records HIP timing events around its device-to-host copy, for
  * ocean_readback_copy_ms.  Requests made while it is off record only untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 

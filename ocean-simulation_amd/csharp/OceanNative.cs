@@ -182,6 +182,20 @@ namespace OceanHip
         public static extern OceanStatus ocean_whitecaps_device(IntPtr ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz, int nx, int ny, int capacity, IntPtr output, UIntPtr bytes);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_whitecaps_async(IntPtr ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz, int nx, int ny, int capacity, IntPtr dst, UIntPtr bytes, out IntPtr request);
+        // Camera views (added within ABI 4 in the same way).  camera = 14 floats (eye, the direction through pixel (0, 0),
+        // its change per column and per row, t0, t1); pixel (i, j) is element j * width + i.  CameraHits: ocean_raycast's 8
+        // floats per pixel; CameraRange: the distance along the ray, +infinity after a miss, 1 float; CameraColor: r, g, b,
+        // status, 4 floats, shaded with the 32 floats of `material` (ocean.h names them; null in the other two modes).
+        // bytes = width * height * 32, 4 or 16.
+        public const int CameraHits = 0, CameraRange = 1, CameraColor = 2;
+        public const int CameraFloats = 14, CameraMaterialFloats = 32;
+        public const int CameraMaxPixels = 1 << 22, CameraMaxSamples = 1 << 28;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_camera(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, [Out] float[] output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_camera_device(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, IntPtr output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_camera_async(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, IntPtr dst, UIntPtr bytes, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_read_async(IntPtr ctx, OceanTexture tex, int tile, int cascade, IntPtr dst, UIntPtr bytes, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

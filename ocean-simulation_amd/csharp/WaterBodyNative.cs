@@ -275,6 +275,23 @@ namespace OceanHip
             return total;
         }
 
+        // What a camera sees of the water (ocean.h ocean_camera): `camera` = 14 floats (eye, the direction through pixel
+        // (0, 0), its change per column and per row, t0, t1).  OceanNative.CameraColor shades the fragment stage of
+        // Water.shader with the 32 floats of `material` and returns r, g, b, status per pixel; CameraRange returns
+        // the distance along each ray (+infinity where it misses), CameraHits Raycast's 8 floats per pixel; both take
+        // a null material.  The headless stand-in for the reference's renderer.
+        public float[] Camera(float[] camera, int width, int height, int mode = OceanNative.CameraColor,
+                              float[] material = null, int iterations = 4, int steps = 64, int refine = 8)
+        {
+            int per = mode == OceanNative.CameraHits ? 8 : mode == OceanNative.CameraRange ? 1 : 4;
+            // (a size outside the limits is refused by the library; no managed buffer of that size first)
+            bool valid = width >= 1 && height >= 1 && (long)width * height <= OceanNative.CameraMaxPixels;
+            var output = new float[valid ? width * height * per : 0];
+            OceanNative.Check(OceanNative.ocean_camera(ctx, 0, mode, iterations, steps, refine, camera, material, width, height,
+                                                       output, (UIntPtr)(ulong)(output.Length * 4)), "ocean_camera");
+            return output;
+        }
+
         // The per-cascade bounds of the displacement (ocean.h ocean_surface_bounds): 8 floats per cascade, (min x, y,
         // z, w, max x, y, z, w); their cascade sums bound the displaced mesh (culling, tessellation range).
         public float[] SurfaceBounds()

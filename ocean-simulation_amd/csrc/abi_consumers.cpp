@@ -1,6 +1,6 @@
 // C-ABI layer of liboceanhip.so, the point consumers (ocean.h): surface and velocity queries, surface grids,
-// buoyant bodies, body dynamics, ray casts and whitecap emitters, each in a _device, a blocking host and an
-// _async form; and world sampling and the surface bounds, which keep bodies of their own.
+// buoyant bodies, body dynamics, ray casts, whitecap emitters and camera views, each in a _device, a blocking host
+// and an _async form; and world sampling and the surface bounds, which keep bodies of their own.
 //
 // A consumer is stated once, as a struct built from its entry's arguments (a "family"), and its three entries
 // are the three forms of that struct: device_form, host_form, async_form.  A family has
@@ -16,6 +16,7 @@
 //   launch(in, out)   its kernel on the ctx stream over device pointers (kind 2 of ocean_kernel_stats), the
 //                     caller having entered the device scope.
 // The order of the tests of each form is the form's, below, and the same for every family.
+#include <algorithm>
 #include <cmath>
 
 #include "abi_internal.h"
@@ -396,6 +397,76 @@ struct Whitecaps {
     }
 };
 
+// Camera views: no staged inputs, the rays follow from the camera's fourteen numbers, which travel to the kernel by
+// value with the material; float[height][width][8], [height][width] or [height][width][4] by mode.  As for the
+// whitecaps, what does not need the context is checked first, the _device form's alignment with it.  The kernel
+// runs behind the bounds launches exactly as the ray casts' does.
+struct Camera {
+    ocean_ctx* ctx;
+    int tile, mode, iterations, steps, refine;
+    const float* camera;
+    const float* material;
+    int width, height;
+    float* out;
+    size_t bytes;
+
+    static size_t pixel_bytes(int mode) { return mode == OCEAN_CAMERA_HITS ? 32 : mode == OCEAN_CAMERA_RANGE ? 4 : 16; }
+    int check(Form form) const {
+        if (!camera || !out) return fail(OCEAN_E_INVALID_ARG, "null camera or output");
+        if (mode != OCEAN_CAMERA_HITS && mode != OCEAN_CAMERA_RANGE && mode != OCEAN_CAMERA_COLOR)
+            return fail(OCEAN_E_INVALID_ARG, "unknown camera mode");
+        if (mode == OCEAN_CAMERA_COLOR && !material) return fail(OCEAN_E_INVALID_ARG, "OCEAN_CAMERA_COLOR needs a material");
+        if (int r = check_iterations(iterations)) return r;
+        if (steps < 1 || steps > OCEAN_RAY_MAX_STEPS)
+            return fail(OCEAN_E_INVALID_ARG, "steps = " + std::to_string(steps) + " outside [1, OCEAN_RAY_MAX_STEPS]");
+        if (refine < 0 || refine > 32) return fail(OCEAN_E_INVALID_ARG, "refine must be in [0, 32]");
+        for (int k = 0; k < OCEAN_CAMERA_FLOATS; ++k)
+            if (!std::isfinite(camera[k])) return fail(OCEAN_E_INVALID_ARG, "camera[" + std::to_string(k) + "] is not finite");
+        for (int k = 0; material && k < OCEAN_CAMERA_MATERIAL_FLOATS; ++k)
+            if (!std::isfinite(material[k])) return fail(OCEAN_E_INVALID_ARG, "material[" + std::to_string(k) + "] is not finite");
+        if (width < 1 || height < 1) return fail(OCEAN_E_INVALID_ARG, "width and height must be at least 1");
+        const uint64_t pixels = (uint64_t)width * (uint64_t)height;
+        if (pixels > (uint64_t)OCEAN_CAMERA_MAX_PIXELS)
+            return fail(OCEAN_E_INVALID_ARG, "width * height = " + std::to_string(pixels) + " > OCEAN_CAMERA_MAX_PIXELS");
+        if (pixels * (uint64_t)steps > (uint64_t)OCEAN_CAMERA_MAX_SAMPLES)
+            return fail(OCEAN_E_INVALID_ARG, "width * height * steps = " + std::to_string(pixels * (uint64_t)steps) +
+                                                 " > OCEAN_CAMERA_MAX_SAMPLES");
+        const size_t want = (size_t)pixels * pixel_bytes(mode);
+        if (bytes != want)
+            return fail(OCEAN_E_INVALID_ARG, "byte count " + std::to_string(bytes) + " != width * height * " +
+                                                 std::to_string(pixel_bytes(mode)) + " = " + std::to_string(want));
+        if (form == Form::Device)
+            if (int r = check_aligned(state().entry, inputs(), out)) return r;
+        if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+        if (int r = check_tile(ctx, tile)) return r;
+        // the async form's result is written into a readback slot
+        if (form == Form::Async && bytes > stage_slot_bytes(ctx))
+            return fail(OCEAN_E_INVALID_ARG, "ocean_camera_async: " + std::to_string(bytes) + " B exceed a readback slot of " +
+                                                 std::to_string(stage_slot_bytes(ctx)) + " B");
+        return OCEAN_OK;
+    }
+    StateRule state() const { return {"ocean_camera", "camera view of"}; }
+    StagedInputs inputs() const { return {nullptr, 0, {}}; }
+    size_t out_bytes() const { return bytes; }
+    const char* lacks() const { return nullptr; }
+    int launch(const float* const*, float* d_out) const {
+        const float* bounds = nullptr;
+        if (ctx->opt.ray_bounds)
+            if (int r = ensure_bounds(ctx, tile, &bounds)) return r;
+        ocean::CameraRays cam;
+        ocean::CameraMaterial mat = {};
+        std::copy(camera, camera + OCEAN_CAMERA_FLOATS, cam.c);
+        if (material) std::copy(material, material + OCEAN_CAMERA_MATERIAL_FLOATS, mat.m);
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] {
+                         return ocean::launch_camera(v, tile, mode, iterations, steps, refine, bounds, cam, mat, width, height,
+                                                     ctx->opt.camera_tile != 0, d_out, ctx->stream);
+                     },
+                     "camera");
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -501,6 +572,21 @@ int ocean_whitecaps(ocean_ctx* ctx, int tile, float lod, float threshold, float 
 int ocean_whitecaps_async(ocean_ctx* ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz,
                           int nx, int ny, int capacity, float* out, size_t bytes, ocean_readback** req) {
     return async_form(Whitecaps{ctx, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity, out, bytes}, req);
+}
+
+int ocean_camera_device(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, int refine, const float* camera,
+                        const float* material, int width, int height, float* out, size_t bytes) {
+    return device_form(Camera{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes});
+}
+
+int ocean_camera(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, int refine, const float* camera,
+                 const float* material, int width, int height, float* out, size_t bytes) {
+    return host_form(Camera{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes});
+}
+
+int ocean_camera_async(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, int refine, const float* camera,
+                       const float* material, int width, int height, float* out, size_t bytes, ocean_readback** req) {
+    return async_form(Camera{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes}, req);
 }
 
 // World sampling has no async form and enters the device scope before its checks.

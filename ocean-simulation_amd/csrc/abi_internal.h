@@ -104,6 +104,7 @@ struct ocean_options {
     int vel_nt = 0;         // OCEAN_VEL_NT=1: the velocity pack kernel writes VEL with nontemporal stores
     int prune = 1;          // OCEAN_PRUNE=0: passes AQ / BQ run every row of a band-limited cascade (dense schedule)
     int ray_bounds = 1;     // OCEAN_RAY_BOUNDS=0: the ray kernel samples every node (no air skip, no bounds launches)
+    int camera_tile = 1;    // OCEAN_CAMERA_TILE=0: the camera kernel maps pixels to lanes row-linearly, not in 8 x 8 tiles (A/B)
     int max_groups = 0;     // OCEAN_MAX_GROUPS: at most this many workgroups per persistent launch (the transform passes
                             // of fftq / fft3 / fft4k / fft2.hip), so that their item loops iterate at small shapes; 0: no cap
 
@@ -120,6 +121,7 @@ struct ocean_options {
         if (const char* e = std::getenv("OCEAN_VEL_NT")) o.vel_nt = std::atoi(e) != 0;
         if (const char* e = std::getenv("OCEAN_PRUNE")) o.prune = std::atoi(e);
         if (const char* e = std::getenv("OCEAN_RAY_BOUNDS")) o.ray_bounds = std::atoi(e);
+        if (const char* e = std::getenv("OCEAN_CAMERA_TILE")) o.camera_tile = std::atoi(e);
         if (const char* e = std::getenv("OCEAN_MAX_GROUPS")) o.max_groups = std::max(0, std::atoi(e));
         return o;
     }

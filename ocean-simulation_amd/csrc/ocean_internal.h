@@ -199,6 +199,20 @@ hipError_t launch_surface_bounds(const DevView& v, int tile, float* partial, flo
 hipError_t launch_raycast(const DevView& v, int tile, int iterations, int steps, int refine, const float* bounds,
                           const float* rays, int count, float* out, hipStream_t s);
 
+// view.hip: camera views (ocean_camera*), device pointer: out float[height][width][8] (OCEAN_CAMERA_HITS), float
+// [height][width] (_RANGE) or float[height][width][4] (_COLOR), 16-B aligned.  The camera's 14 and the material's 32
+// floats of ocean.h travel as kernel arguments (the material is not read in the first two modes); bounds as
+// launch_raycast takes them; tiled: a wave covers 8 x 8 pixels, else 64 consecutive pixels of the row-major image.
+struct CameraRays {
+    float c[OCEAN_CAMERA_FLOATS];
+};
+struct CameraMaterial {
+    float m[OCEAN_CAMERA_MATERIAL_FLOATS];
+};
+hipError_t launch_camera(const DevView& v, int tile, int mode, int iterations, int steps, int refine, const float* bounds,
+                         const CameraRays& cam, const CameraMaterial& mt, int width, int height, bool tiled, float* out,
+                         hipStream_t s);
+
 // whitecaps.hip: whitecap emitters (ocean_whitecaps*), device pointers: out = (capacity + 1) records of 32 B, the
 // header then the selected nodes of the grid in ascending node order, 16-B aligned; vel = the context's VEL or null
 // (records carry a zero velocity); scratch: whitecap_scratch_bytes() bytes, 8-B aligned, the ballot masks of the

@@ -4,8 +4,12 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera]
 //
+// With camera the host reads nothing back per frame: it runs F steps, then one WaterBody::Camera for a fixed camera of
+// 45 x 37 pixels (2 fixed-point steps, 32 march steps, 6 bisections): the shaded picture under a fixed material; it
+// writes camera.bin (float32 [14]), material.bin (float32 [32]) and color.bin (float32 [37][45][4]); the summary line
+// carries the number of pixels of each status; tests/test_gpu_camera_host.py checks them.
 // With whitecaps the host reads nothing back per frame: it runs F steps on a velocity context, then one
 // WaterBody::Whitecaps over a 101 x 101 grid (threshold 0.1, capacity 4096, lod 0) and writes whitecaps.bin (float32
 // [4097][8]: the header, the W records, zeros); the summary line carries the header's T and W and the W records
@@ -56,13 +60,13 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
     if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity" &&
-        mode != "rays" && mode != "dynamics" && mode != "whitecaps") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics or whitecaps\n");
+        mode != "rays" && mode != "dynamics" && mode != "whitecaps" && mode != "camera") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps or camera\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -156,6 +160,34 @@ int main(int argc, char** argv) {
                         "\"written\": %u, \"records\": [", F, n, (int)wb.cascades.size(), head[2], head[3], head[0], head[1]);
             for (size_t i = 0; i < (size_t)head[1] * 8; ++i) std::printf("%s%.9g", i ? ", " : "", list[8 + i]);
             std::printf("]}\n");
+            wb.OnDisable();
+            return 0;
+        }
+        if (mode == "camera") {
+            // an eye 30 m up that looks ahead and slightly down, so that the horizon crosses the image: the eye, the
+            // direction through pixel (0, 0), its change per column and per row, t0, t1
+            const int width = 45, height = 37;
+            const std::vector<float> camera = {3.0f, 30.0f, -4.0f, -0.45f, 0.21f, 0.85f, 0.02f, 0.0f, 0.01f,
+                                               0.0f,  -0.02f, 0.0f,  0.0f,   600.0f};
+            // water colour, R0; Fresnel exponent and divisor of roughness 0.3, roughness, lod slope; EX, EY, environment
+            // and sun strength; subsurface colour x intensity, foam threshold; foam colour, blending; light direction
+            // (unit), light colour, horizon colour, zenith colour (ocean.h)
+            const std::vector<float> material = {0.02f,  0.1f,  0.16f,  0.0203731f, 2.2308f, 4.72995f, 0.3f, 0.004f,
+                                                 0.25f,  0.25f, 1.0f,   1.0f,       0.0f,    0.3f,     0.25f, 0.25f,
+                                                 1.0f,   1.0f,  1.0f,   0.5f,       0.36f,   0.48f,    0.8f,  1.0f,
+                                                 0.96f,  0.9f,  0.75f,  0.82f,      0.9f,    0.2f,     0.4f,  0.8f};
+            wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
+            wb.Awake();
+            for (int f = 0; f < F; ++f) wb.Update((float)f / 60.0f);
+            const std::vector<float> color = wb.Camera(camera, width, height, OCEAN_CAMERA_COLOR, material, 2, 32, 6);
+            write_bin(out + "/camera.bin", camera.data(), camera.size());
+            write_bin(out + "/material.bin", material.data(), material.size());
+            write_bin(out + "/color.bin", color.data(), color.size());
+            int status[3] = {0, 0, 0};
+            for (int k = 0; k < width * height; ++k) ++status[(int)color[4 * k + 3]];
+            std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"width\": %d, \"height\": %d, \"miss\": %d, "
+                        "\"hit\": %d, \"submerged\": %d}\n", F, n, (int)wb.cascades.size(), width, height, status[0], status[1],
+                        status[2]);
             wb.OnDisable();
             return 0;
         }

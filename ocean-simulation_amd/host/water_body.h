@@ -232,6 +232,26 @@ public:
         return out;
     }
 
+    // What a camera sees of the water (ocean.h ocean_camera): camera = 14 floats (eye, the direction through pixel
+    // (0, 0), its change per column and per row, t0, t1); pixel (i, j) is element j * width + i of the result.
+    // OCEAN_CAMERA_COLOR shades the fragment stage of Water.shader with the 32 floats of `material`: r, g, b, status
+    // per pixel; OCEAN_CAMERA_RANGE: the distance along each ray, +infinity where it misses; OCEAN_CAMERA_HITS:
+    // Raycast's 8 floats per pixel (both with an empty material).  The headless stand-in for the reference's renderer.
+    std::vector<float> Camera(const std::vector<float>& camera, int width, int height, int mode = OCEAN_CAMERA_COLOR,
+                              const std::vector<float>& material = {}, int iterations = 4, int steps = 64,
+                              int refine = 8) const {
+        if (camera.size() != OCEAN_CAMERA_FLOATS || (!material.empty() && material.size() != OCEAN_CAMERA_MATERIAL_FLOATS))
+            throw std::runtime_error("Camera: camera is 14 floats, material 32 or none");
+        const size_t per = mode == OCEAN_CAMERA_HITS ? 8 : mode == OCEAN_CAMERA_RANGE ? 1 : 4;
+        // (a size outside the limits is refused by the library; no buffer of that size first)
+        const bool valid = width >= 1 && height >= 1 && (long long)width * height <= OCEAN_CAMERA_MAX_PIXELS;
+        std::vector<float> out(valid ? (size_t)width * height * per : 0);
+        check(ocean_camera(ctx_, 0, mode, iterations, steps, refine, camera.data(), material.empty() ? nullptr : material.data(),
+                           width, height, out.data(), out.size() * sizeof(float)),
+              "ocean_camera");
+        return out;
+    }
+
     // Where the sea is breaking (ocean.h ocean_whitecaps): the nodes (i, j) at (x0 + i dx, z0 + j dz) whose foam
     // reaches `threshold`, in ascending j * nx + i.  Returns the list as the library writes it, capacity + 1 records
     // of 8 floats: the header (eight uint32: T selected, W = min(T, capacity) written, nx * ny, capacity, 0, 0, 0, 0;

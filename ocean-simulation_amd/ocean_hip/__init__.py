@@ -73,6 +73,7 @@ EXPORTED_SYMBOLS = (
     "ocean_raycast", "ocean_raycast_device", "ocean_raycast_async",
     "ocean_body_dynamics", "ocean_body_dynamics_device", "ocean_body_dynamics_async",
     "ocean_whitecaps", "ocean_whitecaps_device", "ocean_whitecaps_async",
+    "ocean_camera", "ocean_camera_device", "ocean_camera_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -94,6 +95,12 @@ RAY_MAX_STEPS = 1024
 RAY_MAX_SAMPLES = 1 << 24
 # ocean_whitecaps* limit (ocean.h): records of a list, the header not counted
 WHITECAP_MAX_RECORDS = 65535
+# ocean_camera* modes, array sizes and limits (ocean.h)
+CAMERA_HITS, CAMERA_RANGE, CAMERA_COLOR = 0, 1, 2
+CAMERA_FLOATS = 14
+CAMERA_MATERIAL_FLOATS = 32
+CAMERA_MAX_PIXELS = 1 << 22
+CAMERA_MAX_SAMPLES = 1 << 28
 
 
 class OceanError(RuntimeError):
@@ -188,6 +195,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_whitecaps": ([P, i, f, f, f, f, f, f, i, i, i, P, sz], i),
         "ocean_whitecaps_device": ([P, i, f, f, f, f, f, f, i, i, i, P, sz], i),
         "ocean_whitecaps_async": ([P, i, f, f, f, f, f, f, i, i, i, P, sz, ctypes.POINTER(P)], i),
+        "ocean_camera": ([P, i, i, i, i, i, P, P, i, i, P, sz], i),
+        "ocean_camera_device": ([P, i, i, i, i, i, P, P, i, i, P, sz], i),
+        "ocean_camera_async": ([P, i, i, i, i, i, P, P, i, i, P, sz, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -201,6 +211,55 @@ def _check(rc: int, where: str) -> None:
     if rc != OK:
         msg = load_library().ocean_last_error().decode(errors="replace")
         raise OceanError(rc, where, msg)
+
+
+def look_at_camera(eye, target, up, fov_y: float, width: int, height: int, t0: float, t1: float) -> np.ndarray:
+    """The float32[14] camera of ocean_camera (ocean.h) for a pinhole at `eye` looking at `target`: pixel (i, j) looks
+    through the centre of its cell of an image plane one unit ahead, `fov_y` radians tall, row 0 at the top, column
+    0 at the left (right = forward x up).  Every ray searches [t0, t1].  Computed in float64 and rounded once."""
+    e, t, u = (np.asarray(a, np.float64) for a in (eye, target, up))
+    fwd = t - e
+    fwd = fwd / np.sqrt((fwd * fwd).sum())
+    right = np.cross(fwd, u)
+    right = right / np.sqrt((right * right).sum())
+    top = np.cross(right, fwd)
+    step = 2.0 * np.tan(0.5 * float(fov_y)) / int(height)  # a pixel's side on the image plane: square pixels
+    du, dv = right * step, -top * step
+    d00 = fwd + du * (0.5 - 0.5 * int(width)) + dv * (0.5 - 0.5 * int(height))
+    return np.concatenate([e, d00, du, dv, [float(t0), float(t1)]]).astype(np.float32)
+
+
+def material(color=(0.02, 0.1, 0.16), roughness: float = 0.3, ex: float = 0.25, ey: float = 0.25,
+             environment_strength: float = 1.0, sun_strength: float = 1.0, subsurface_intensity: float = 0.5,
+             subsurface_color=(0.0, 0.6, 0.5), foam_color=(1.0, 1.0, 1.0), foam_threshold: float = 0.5,
+             foam_blending: float = 0.5, light_direction=(0.3, 0.5, 0.4), light_color=(1.0, 0.96, 0.9),
+             horizon_color=(0.75, 0.82, 0.9), zenith_color=(0.2, 0.4, 0.8), lod_slope: float = 0.0) -> np.ndarray:
+    """The float32[32] material of ocean_camera's colour mode (ocean.h names the fields; the arguments are
+    Water.shader's properties, a light and a two-colour sky).  Computed in float64 and rounded once: R0 of air over
+    water, the Fresnel exponent 5 exp(-2.69 roughness) and divisor 1 + 22.7 roughness^1.5, the subsurface colour
+    times its intensity, and the direction towards the light normalised."""
+    light = np.asarray(light_direction, np.float64)
+    light = light / np.sqrt((light * light).sum())
+    r = float(roughness)
+    m = np.zeros(CAMERA_MATERIAL_FLOATS, np.float64)
+    m[0:3] = color
+    m[3] = ((1.0 - 1.333) / (1.0 + 1.333)) ** 2
+    m[4] = 5.0 * np.exp(-2.69 * r)
+    m[5] = 1.0 + 22.7 * r ** 1.5
+    m[6], m[7], m[8], m[9] = r, lod_slope, ex, ey
+    m[10], m[11] = environment_strength, sun_strength
+    m[12:15] = np.asarray(subsurface_color, np.float64) * float(subsurface_intensity)
+    m[15] = foam_threshold
+    m[16:19] = foam_color
+    m[19] = foam_blending
+    m[20:23] = light
+    m[23:26] = light_color
+    m[26:29] = horizon_color
+    m[29:32] = zenith_color
+    return m.astype(np.float32)
+
+
+_material = material  # (WaterBody.Camera has a parameter of that name)
 
 
 class OceanContext:
@@ -422,6 +481,58 @@ class OceanContext:
         vp = ctypes.c_void_p
         _check(self.lib.ocean_raycast_device(self._h, tile, iterations, steps, refine, vp(rays_ptr), count,
                                              vp(out_ptr)), "ocean_raycast_device")
+
+    @staticmethod
+    def _camera_args(camera, material, mode: int, width: int, height: int):
+        """(camera float32[14], material float32[32] or None, result shape, bytes)."""
+        cam = np.ascontiguousarray(camera, np.float32).reshape(-1)
+        if cam.shape[0] != CAMERA_FLOATS:
+            raise ValueError(f"camera must be float32[{CAMERA_FLOATS}] (look_at_camera), got {cam.shape}")
+        mat = None
+        if material is not None:
+            mat = np.ascontiguousarray(material, np.float32).reshape(-1)
+            if mat.shape[0] != CAMERA_MATERIAL_FLOATS:
+                raise ValueError(f"material must be float32[{CAMERA_MATERIAL_FLOATS}] (material()), got {mat.shape}")
+        w, h = max(int(width), 0), max(int(height), 0)
+        if w * h > CAMERA_MAX_PIXELS:  # refused by the library as well; no host buffer of that size first
+            w = h = 0
+        shape = {CAMERA_HITS: (h, w, 8), CAMERA_RANGE: (h, w), CAMERA_COLOR: (h, w, 4)}.get(mode, (0,))
+        return cam, mat, shape, int(np.prod(shape, dtype=np.int64)) * 4
+
+    def camera(self, camera, width: int, height: int, mode: int = CAMERA_COLOR, material=None, tile: int = 0,
+               iterations: int = 4, steps: int = 64, refine: int = 8) -> np.ndarray:
+        """An image of the sea (ocean.h ocean_camera), blocking: pixel (i, j)'s ray follows from `camera`
+        (look_at_camera) and meets the water where raycast says that ray does.  CAMERA_HITS: raycast's records,
+        float32[height][width][8]; CAMERA_RANGE: the distance along the ray, inf after a miss,
+        float32[height][width]; CAMERA_COLOR: Water.shader's fragment stage at the point met under `material`
+        (material()), float32[height][width][4] = (r, g, b, status)."""
+        cam, mat, shape, nbytes = self._camera_args(camera, material, mode, width, height)
+        out = np.empty(shape, np.float32)
+        _check(self.lib.ocean_camera(self._h, tile, mode, iterations, steps, refine, cam.ctypes.data,
+                                     mat.ctypes.data if mat is not None else None, width, height, out.ctypes.data,
+                                     nbytes), "ocean_camera")
+        return out
+
+    def camera_async(self, camera, width: int, height: int, mode: int = CAMERA_COLOR, material=None, tile: int = 0,
+                     iterations: int = 4, steps: int = 64, refine: int = 8, buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_camera_async), as surface_grid_async: the image is computed behind the queued
+        steps and lands in pinned host memory; it must fit a readback slot."""
+        cam, mat, shape, nbytes = self._camera_args(camera, material, mode, width, height)
+        return Readback(self, shape, nbytes, "ocean_camera_async",
+                        lambda dst, req: self.lib.ocean_camera_async(self._h, tile, mode, iterations, steps, refine,
+                                                                     cam.ctypes.data,
+                                                                     mat.ctypes.data if mat is not None else None,
+                                                                     width, height, dst, nbytes, req), buf)
+
+    def camera_device(self, out_ptr: int, camera, width: int, height: int, mode: int = CAMERA_COLOR, material=None,
+                      tile: int = 0, iterations: int = 4, steps: int = 64, refine: int = 8) -> None:
+        """The device-pointer form (ocean_camera_device): the image is written to `out_ptr` on this context's device,
+        16-B aligned; async on the context's stream, after the queued steps.  `camera` and `material` are host
+        arrays, consumed by the call."""
+        cam, mat, _, nbytes = self._camera_args(camera, material, mode, width, height)
+        _check(self.lib.ocean_camera_device(self._h, tile, mode, iterations, steps, refine, cam.ctypes.data,
+                                            mat.ctypes.data if mat is not None else None, width, height,
+                                            ctypes.c_void_p(out_ptr), nbytes), "ocean_camera_device")
 
     @staticmethod
     def grid_points(x0: float, z0: float, dx: float, dz: float, nx: int, ny: int) -> np.ndarray:
@@ -1089,6 +1200,17 @@ class WaterBody:
             return None
         point = ray[0, :3] + rec[0] * ray[0, 3:6]  # fp32: pos(t*) of ocean.h
         return WaterHit(float(rec[0]), point, rec[4:7].copy(), float(rec[7]), int(rec[3]) == RAY_SUBMERGED)
+
+    def Camera(self, eye, target, width: int, height: int, fov_y: float = 1.0, max_distance: float = 2000.0,
+               mode: int = CAMERA_COLOR, material=None, up=(0.0, 1.0, 0.0), iterations: int = 4, steps: int = 64,
+               refine: int = 8, tile: int = 0) -> np.ndarray:
+        """What a camera at `eye` looking at `target` sees of the water (OceanContext.camera over look_at_camera;
+        colour mode shades with `material`, material()'s defaults when None): the headless stand-in for the
+        reference's renderer, whose fragment stage (Water.shader:336-374) this evaluates.  Blocking."""
+        if mode == CAMERA_COLOR and material is None:
+            material = _material()
+        cam = look_at_camera(eye, target, up, fov_y, width, height, 0.0, max_distance)
+        return self.ctx.camera(cam, width, height, mode, material, tile, iterations, steps, refine)
 
     def Whitecaps(self, threshold: float, x0: float, z0: float, dx: float, dz: float, nx: int, ny: int,
                   capacity: int = 4096, lod: float = 0.0, tile: int = 0):
