@@ -204,6 +204,23 @@ namespace OceanHip
             return output;
         }
 
+        // The surface over a regular grid (ocean.h ocean_surface_grid): node (i, j) at (x0 + i dx, z0 + j dz) is element
+        // j * nx + i of the result.  GridVertices (iterations 0, `lod` as SampleWorld): 8 floats per node, the displaced
+        // vertex x, y, z, the foam, the normal, 0: MeshGenerator's plane through the domain stage of Water.shader;
+        // GridSurface: ocean_query_surface's record at every node; GridHeightfield: its height alone, 1 float per node.
+        public float[] SurfaceGrid(float x0, float z0, float dx, float dz, int nx, int ny, int mode = OceanNative.GridSurface,
+                                   int iterations = 4, float lod = 0f)
+        {
+            int per = mode == OceanNative.GridHeightfield ? 1 : 8;
+            // (a size outside the limits is refused by the library; no managed buffer of that size first)
+            bool valid = nx >= 1 && ny >= 1 && (long)nx * ny <= OceanNative.GridMaxNodes;
+            var output = new float[valid ? nx * ny * per : 0];
+            OceanNative.Check(OceanNative.ocean_surface_grid(ctx, 0, mode, mode == OceanNative.GridVertices ? 0 : iterations, lod,
+                                                             x0, z0, dx, dz, nx, ny, output,
+                                                             (UIntPtr)(ulong)(output.Length * 4)), "ocean_surface_grid");
+            return output;
+        }
+
         // BuoyantObject.FixedUpdate's lookup for M bodies of P probes each (ocean.h ocean_body_buoyancy): hull is
         // [P][5] = (cell centre in the body frame, vertical extent, volume), bodies [M][10] = (origin, body -> world
         // quaternion xyzw, per-axis scale); per body 8 floats: submerged volume V, V * centroid relative to the

@@ -101,7 +101,7 @@ int device_form(const Family& f) {
     return f.launch(d_in, f.out);
 }
 
-// The blocking host form: inputs and results through one stream-ordered block (run_staged).
+// The blocking host form: inputs and results through the context's staging block (run_staged).
 template <class Family>
 int host_form(const Family& f) {
     if (int r = f.check(Form::Host)) return r;

@@ -173,6 +173,9 @@ struct ocean_ctx {
     // whitecap emitters (whitecaps.hip): the ballot masks and per-chunk counts of the largest grid, allocated by the
     // first ocean_whitecaps* call and reused by every later one
     void* whitecap_dev = nullptr;
+    // the staging block of the blocking host forms (run_staged_impl): inputs, then the output; grown on demand
+    void* stage_block = nullptr;
+    size_t stage_block_bytes = 0;
     float4* deriv_mips = nullptr;  // OCEAN_F_MIPS chains (levels 1..log2 N per slice)
     float4* turb_mips = nullptr;
     size_t mip_chain = 0;
@@ -347,6 +350,9 @@ struct StagedInputs {
 // points and results (N <= 256).
 size_t stage_slot_bytes(const ocean_ctx* ctx);
 
+// The context's staging block (ocean_ctx::stage_block) grows in multiples of this.
+constexpr size_t kStageBlockGrain = (size_t)1 << 16;
+
 // A staged launch: (device addresses of the inputs, device address of the output) -> an OCEAN_* code.  Passed
 // as a plain function and its argument: these calls are latency-bound, nothing here allocates.
 using StagedLaunch = int (*)(const void* arg, const float* const* d_in, float* d_out);
@@ -358,7 +364,7 @@ template <class F>
 int call_staged(const void* f, const float* const* d_in, float* d_out) {
     return (*static_cast<const F*>(f))(d_in, d_out);
 }
-// The blocking host form: upload, launch, download, synchronize.
+// The blocking host form: upload, launch, download, synchronize, through the context's staging block.
 template <class F>
 int run_staged(ocean_ctx* ctx, const char* entry, const StagedInputs& in, void* out, size_t out_bytes, const F& launch) {
     return run_staged_impl(ctx, entry, in, out, out_bytes, &call_staged<F>, &launch);

@@ -110,17 +110,32 @@ int start_readback(ocean_ctx* ctx, void* dst, size_t bytes, Snapshot&& snapshot,
 
 size_t stage_slot_bytes(const ocean_ctx* ctx) { return std::max(ctx->texels() * 16, kQuerySlotBytes); }
 
-// The blocking host form: one stream-ordered block holds the inputs from its base and the output at the next
-// 256-byte boundary (float4 output rows stay 16-B aligned); upload, launch, download, free, synchronize.  The
-// launch's own code comes first, then the copies', the free's and the synchronize's.
+// The blocking host form: one block of device memory that the context owns (stage_block: hipMalloc, grown on
+// demand, freed by ocean_destroy) holds the inputs from its base and the output at the next 256-byte boundary
+// (float4 output rows stay 16-B aligned); upload, launch, download, synchronize.  The call ends with the stream
+// idle, so the block is free again when the next blocking call starts, and growing it frees nothing in use.
+// It was a stream-ordered block per call (hipMallocAsync before the upload, hipFreeAsync behind the download) until
+// tests/test_gpu_host_sequences.py played sequences of blocking calls in one process on the system's HIP runtime
+// (/opt/rocm 7.2.0): the results of ocean_camera, ocean_whitecaps and ocean_surface_grid came back all zero or
+// partly written, and those of ocean_query_surface and ocean_sample_world with wrong numbers, each with OCEAN_OK
+// and from a compiled host and a torch-less Python alike, while the same calls on the runtime torch bundles were
+// right (docs/MEASUREMENTS.md section 24).  What in the runtime differs was not looked for.
+// The launch's own code comes first, then the copies' and the synchronize's.
 int run_staged_impl(ocean_ctx* ctx, const char* entry, const StagedInputs& in, void* out, size_t out_bytes,
                     StagedLaunch launch, const void* arg) {
     size_t in_bytes = 0;
     for (int k = 0; k < in.n; ++k) in_bytes += in.v[k].bytes;
     const size_t out_off = (in_bytes + 255) & ~(size_t)255;
-    void* d = nullptr;
-    OCEAN_HIP(hipMallocAsync(&d, out_off + out_bytes, ctx->stream));
-    char* base = static_cast<char*>(d);
+    const size_t need = out_off + out_bytes;
+    if (need > ctx->stage_block_bytes) {
+        if (ctx->stage_block) OCEAN_HIP(hipFree(ctx->stage_block));
+        ctx->stage_block = nullptr;
+        ctx->stage_block_bytes = 0;
+        const size_t bytes = (need + kStageBlockGrain - 1) / kStageBlockGrain * kStageBlockGrain;
+        OCEAN_HIP(hipMalloc(&ctx->stage_block, bytes));
+        ctx->stage_block_bytes = bytes;
+    }
+    char* base = static_cast<char*>(ctx->stage_block);
     float* d_out = reinterpret_cast<float*>(base + out_off);
     const float* d_in[kMaxInputs] = {};
     hipError_t e = hipSuccess;
@@ -133,11 +148,9 @@ int run_staged_impl(ocean_ctx* ctx, const char* entry, const StagedInputs& in, v
     int r = OCEAN_OK;
     if (e == hipSuccess) r = launch(arg, d_in, d_out);
     if (e == hipSuccess && r == OCEAN_OK) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t ef = hipFreeAsync(d, ctx->stream);
     const hipError_t es = hipStreamSynchronize(ctx->stream);
     if (r != OCEAN_OK) return r;
     if (e != hipSuccess) return hip_fail(e, (std::string(entry) + " copy").c_str());
-    if (ef != hipSuccess) return hip_fail(ef, "hipFreeAsync");
     if (es != hipSuccess) return hip_fail(es, "hipStreamSynchronize");
     return OCEAN_OK;
 }

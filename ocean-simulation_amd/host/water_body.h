@@ -182,6 +182,23 @@ public:
         return out;
     }
 
+    // The surface over a regular grid (ocean.h ocean_surface_grid): node (i, j) at (x0 + i dx, z0 + j dz) is element
+    // j * nx + i of the result.  OCEAN_GRID_VERTICES (iterations 0, `lod` as SampleWorld): 8 floats per node, the
+    // displaced vertex x, y, z, the foam, the normal, 0: MeshGenerator's plane through the domain stage of
+    // Water.shader; OCEAN_GRID_SURFACE: ocean_query_surface's record at every node; OCEAN_GRID_HEIGHTFIELD: its
+    // height alone, 1 float per node.  The per-frame call of a renderer or a heightfield collider.
+    std::vector<float> SurfaceGrid(float x0, float z0, float dx, float dz, int nx, int ny, int mode = OCEAN_GRID_SURFACE,
+                                   int iterations = 4, float lod = 0.0f) const {
+        const size_t per = mode == OCEAN_GRID_HEIGHTFIELD ? 1 : 8;
+        // (a size outside the limits is refused by the library; no buffer of that size first)
+        const bool valid = nx >= 1 && ny >= 1 && (long long)nx * ny <= OCEAN_GRID_MAX_NODES;
+        std::vector<float> out(valid ? (size_t)nx * ny * per : 0);
+        check(ocean_surface_grid(ctx_, 0, mode, mode == OCEAN_GRID_VERTICES ? 0 : iterations, lod, x0, z0, dx, dz, nx, ny,
+                                 out.data(), out.size() * sizeof(float)),
+              "ocean_surface_grid");
+        return out;
+    }
+
     // BuoyantObject.FixedUpdate's lookup for M bodies of P probes each (ocean.h ocean_body_buoyancy): hull is
     // [P][5] = (cell centre in the body frame, vertical extent, volume), bodies [M][10] = (origin, body -> world
     // quaternion xyzw, per-axis scale) -> 8 floats per body: submerged volume V, V * centroid relative to the
@@ -315,6 +332,9 @@ public:
         if (!held_ || readback == Readback::Probes) buoy_.clear();
         return buoy_;
     }
+    // The context itself, for a host that also calls entries this facade does not wrap (null outside Awake ..
+    // OnDisable; the facade keeps owning it).
+    ocean_ctx* Context() const { return ctx_; }
     long requested() const { return requested_; }
     long completed() const { return completed_; }
 

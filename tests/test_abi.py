@@ -108,6 +108,24 @@ def test_cpp_host_builds_and_checks_arguments():
     assert r.returncode == 2 and "usage" in r.stderr
 
 
+def test_sequence_host_builds_and_checks_arguments(tmp_path):
+    """The compiled host that plays a sequence of calls (host/abi_sequence; tests/test_gpu_host_sequences.py runs
+    it): with no arguments, with an op it does not know, with an op of the wrong length or with flags that
+    water_body.h cannot make, it exits 2 with a usage line before any device call (which, without a GPU, would
+    fail with exit 1)."""
+    import subprocess
+    host = os.path.join(ROOT, "ocean-simulation_amd", "host", "abi_sequence")
+    assert os.path.exists(host), "build it: make -C ocean-simulation_amd"
+    r = subprocess.run([host], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "usage" in r.stderr and r.stdout == ""
+    for ops, flags, why in (("step 0\nsplash 1 2\n", "8", "unknown op splash"), ("step 0\ngrid 1 4 0\n", "8", "grid takes 9"),
+                            ("step 0\n", "12", "flags"), ("ctx 1 64 2 7 2\n", "8", "flags")):
+        with open(tmp_path / "ops.txt", "w") as f:
+            f.write(ops)
+        r = subprocess.run([host, str(tmp_path), "64", "2", flags], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 2 and "usage" in r.stderr and why in r.stderr and r.stdout == "", (ops, r.stderr)
+
+
 def test_env_knobs_match_integration_table():
     """Every environment variable the library reads (getenv in csrc/) is one of INTEGRATION.md's
     knob table, and every row of that table is read: no hidden schedule switches, and no knob that
