@@ -2,7 +2,13 @@
 sincos_fast (csrc/spectrum_math.h), its argument sets, the ulp measure, and the per-wavenumber analysis of a
 frame against a float64 frame whose phase is formed the way the reference forms it (the fp32 product omega * t).
 
-Nothing here is collected by pytest (no test_ prefix) and nothing here needs a GPU."""
+The frame analysis has two backends that state the same formulas: float64 numpy (the module's functions), and
+complex128 torch.fft on a device (TorchRef), for the sizes at which the numpy transforms cost more than the
+frames they judge.  tests/test_gpu_phase.py holds the two to 1e-12 of each other.
+
+Nothing here is collected by pytest (no test_ prefix) and nothing but TorchRef needs a GPU."""
+import sys
+
 import numpy as np
 
 import oracle as O
@@ -193,37 +199,49 @@ def col_rms(d):
     return np.sqrt(pw / n), float(np.sqrt(pw.sum() / (n * n)))
 
 
-def worst_ratio(got, oracle, ref, rms=row_rms):
+def spec_rows(p):
+    """rms of a spectrum plane per mirror-row pair y = 0 .. N/2 (|P|^2 summed over the pair)."""
+    n = p.shape[0]
+    pw = (np.abs(p) ** 2).sum(axis=1)
+    return np.sqrt((pw + pw[(n - np.arange(n)) % n])[: n // 2 + 1] / (2 * n))
+
+
+def worst_ratio(got, oracle, ref, rms=row_rms, where=False):
     """max over rows (or columns) of rms(got - ref) / max(rms(oracle - ref), floor), floor = the oracle's rms
     over the whole plane.  A plane on which the oracle is exact everywhere has no yardstick: the ratio is then
-    0 if `got` is exact too, else inf."""
+    0 if `got` is exact too, else inf.  where: also the index of the row pair (or column) of the maximum."""
     mine, _ = rms(got - ref)
     own, floor = rms(oracle - ref)
     den = np.maximum(own, floor)
     if floor == 0.0:
-        return 0.0 if not mine.any() else float("inf")
-    return float((mine / den).max())
+        worst, at = (0.0 if not mine.any() else float("inf")), int(np.argmax(mine))
+    else:
+        worst, at = float((mine / den).max()), int(np.argmax(mine / den))
+    return (worst, at) if where else worst
 
 
-def frame_ratios(got, oracle, ref):
+def frame_ratios(got, oracle, ref, be=None, where=False):
     """got / oracle / ref: lists of fields of one unit of one frame.  (worst row ratio, worst column ratio)
-    over the planes."""
-    rows = max(worst_ratio(g, o, r, row_rms) for g, o, r in zip(got, oracle, ref))
-    cols = max(worst_ratio(g, o, r, col_rms) for g, o, r in zip(got, oracle, ref))
-    return rows, cols
+    over the planes.  be: the backend whose row_rms / col_rms take the fields (None: numpy, this module).
+    where: each as (ratio, index of the row pair or column, plane)."""
+    be = be or sys.modules[__name__]
+    out = []
+    for rms in (be.row_rms, be.col_rms):
+        per = [worst_ratio(g, o, r, rms, True) + (p,) for p, (g, o, r) in enumerate(zip(got, oracle, ref))]
+        out.append(max(per))
+    return tuple(out) if where else (out[0][0], out[1][0])
 
 
-def blind_share(spec, oracle, ref):
+def blind_share(spec, oracle, ref, be=None):
     """The share of mirror-row pairs whose own spectrum rms (of the float64 planes `spec`, each |P| summed over
     the pair) is below the floor of its plane, worst plane: such rows are checked against the floor only.  The
     first two fields come from plane 0 and plane 1 (Dy + i Dxz); a real field sees the Hermitian part of its
     plane, which is no smaller in rms than half of it, so the plane's own rms is the measure for all four."""
+    be = be or sys.modules[__name__]
     worst = 0.0
     for p, (o, r) in enumerate(zip(oracle, ref)):
-        n = spec[p].shape[0]
-        pw = (np.abs(spec[p]) ** 2).sum(axis=1)
-        rows = np.sqrt((pw + pw[(n - np.arange(n)) % n])[: n // 2 + 1] / (2 * n))
-        _, floor = row_rms(o - r)
+        rows = be.spec_rows(spec[p])
+        _, floor = be.row_rms(o - r)
         worst = max(worst, float((rows < floor).mean()))
     return worst
 
@@ -234,3 +252,78 @@ def crossing_time(waves, h0, share=1.0 / 3.0):
     om = waves[..., 3]
     live = om[(om > 0) & (h0[..., :2] != 0).any(axis=-1)]
     return float(f32(HANDOVER / np.quantile(live.astype(f64), 1.0 - share)))
+
+
+# ------------------------------------------------------------------ the same analysis in complex128 torch.fft
+class TorchRef:
+    """ref_fields, out_fields, row_rms, col_rms and spec_rows as above, formula for formula, in float64 /
+    complex128 torch on `device`: the float64 numpy transforms of a 4096^2 frame cost more than the frame and its
+    oracle together.  The phase is evolve64's: the fp32 product omega * t formed in numpy, then float64 sin / cos
+    of that fp32 number (on the device).  Fields stay on the device; the per-row and per-column rms come back as
+    numpy arrays, so worst_ratio, frame_ratios and blind_share (be=this object) are the functions above."""
+
+    def __init__(self, device="cuda"):
+        import torch
+        self.torch, self.device = torch, torch.device(device)
+        self._s = {}
+
+    def _dev(self, a, dtype):
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.device).to(dtype)
+
+    def _checker(self, n):
+        if n not in self._s:
+            t = self.torch
+            i = t.arange(n, device=self.device)
+            self._s[n] = 1.0 - 2.0 * ((i[None, :] + i[:, None]) % 2).to(t.float64)
+        return self._s[n]
+
+    def evolve64(self, h0, waves, t):
+        T = self.torch
+        phase = self._dev(waves[..., 3].astype(f32) * f32(t), T.float64)  # the fp32 product, as evolve64 forms it
+        h0, waves = self._dev(h0, T.float64), self._dev(waves, T.float64)
+        e = T.complex(T.cos(phase), T.sin(phase))
+        h = T.complex(h0[..., 0], h0[..., 1]) * e + T.complex(h0[..., 2], h0[..., 3]) * T.conj(e)
+        ih = 1j * h
+        kx, ik, kz = waves[..., 0], waves[..., 1], waves[..., 2]
+        aux = -h * ik
+        return [ih * kx * ik + 1j * (ih * kz * ik), h + 1j * (aux * kx * kz), ih * kx + 1j * (ih * kz),
+                aux * kx * kx + 1j * (aux * kz * kz)]
+
+    def ref_fields(self, h0, waves, t, full):
+        T = self.torch
+        n = h0.shape[0]
+        spec = self.evolve64(h0, waves, t)[:4 if full else 2]
+        P = [T.fft.ifft2(q) * (n * n) * self._checker(n) for q in spec]  # oracle.ref64.ifft2d
+        out = [P[0], P[1].real.clone()]
+        if full:
+            out += [P[2], P[3]]
+        return out, spec
+
+    def out_fields(self, disp, deriv):
+        T = self.torch
+        d = self._dev(disp, T.float64)
+        out = [T.complex(d[..., 0], d[..., 2]), d[..., 1].clone()]
+        if deriv is not None:
+            g = self._dev(deriv, T.float64)
+            out += [T.complex(g[..., 0], g[..., 1]), T.complex(g[..., 2], g[..., 3])]
+        return out
+
+    def spec_rows(self, p):
+        T = self.torch
+        n = p.shape[0]
+        pw = (p.abs() ** 2).sum(dim=1)
+        pair = pw + pw[(n - T.arange(n, device=self.device)) % n]
+        return T.sqrt(pair[: n // 2 + 1] / (2 * n)).cpu().numpy()
+
+    def row_rms(self, d):
+        T = self.torch
+        n = d.shape[0]
+        pw = ((T.fft.fft2(self._checker(n) * d) / (n * n)).abs() ** 2).sum(dim=1)
+        pair = pw + pw[(n - T.arange(n, device=self.device)) % n]
+        return T.sqrt(pair[: n // 2 + 1] / (2 * n)).cpu().numpy(), float(T.sqrt(pw.sum() / (n * n)))
+
+    def col_rms(self, d):
+        T = self.torch
+        n = d.shape[0]
+        pw = ((T.fft.fft(self._checker(n) * d, dim=0) / n).abs() ** 2).sum(dim=0)
+        return T.sqrt(pw / n).cpu().numpy(), float(T.sqrt(pw.sum() / (n * n)))

@@ -12,7 +12,14 @@ mirror-row pair (a pass-A item) and each spatial column (a pass-B item) is held 
 larger.  The norm-relative 1e-5 of the other parity tests cannot see one row's fault under a spectrum that falls
 by five decades (tests/test_phase_math.py shows one: 41 times the bound here, 1.6e-6 there).
 
-N = 4096 (k_pass_a3q, k_pass_a3pp) is left out: the oracle frame alone takes tens of seconds there.
+Part 3: the same bound at N = 2048 and 4096, where the column passes are the four-step k_col4s1 / k_col4s2
+(csrc/fft4k.hip) and the row pass at 4096 is k_pass_a3q, or k_pass_a3pp under a column parity (csrc/fftq.hip).
+The oracle runs threaded there (a second per 4096^2 frame), and the float64 analysis runs in complex128
+torch.fft on the device (phase_ref.TorchRef), which test_reference_backends_agree holds to the numpy one: the
+numpy transforms of one 4096^2 frame take longer than the frame, its oracle and its readback together.
+tests/test_phase_math.py shows what the bound resolves in a four-step transform: one inter-step twiddle 1e-5 rad
+off is 5.1 times sqrt(2) x 1.1 there and 2.1e-6 norm-relative.
+
 k_evolve's launch grid is not under OCEAN_MAX_GROUPS (spectrum.hip grid_for: one lane per texel up to 4 M
 texels), so the one call made under that knob runs the same grid; it is kept because the issue asks for it."""
 import re
@@ -23,7 +30,7 @@ import pytest
 import ocean_hip as oh
 import oracle as O
 import phase_ref as R
-from test_gpu_parity import TOL, _ctx_with_env, assert_channels
+from test_gpu_parity import TOL, _ctx_with_env, assert_channels, oracle_threads
 from test_gpu_prune import FLAT, SPARSE
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("require_gpu")]
@@ -237,3 +244,170 @@ def test_rows_per_wavenumber(case):
         assert blind <= 0.5, "more than half of the rows are checked against the floor only"
     assert worst_rows <= c_row, f"row ratio {worst_rows:.3f} > {c_row}"
     assert worst_cols <= c_col, f"column ratio {worst_cols:.3f} > {c_col}"
+
+
+# ------------------------------------------------------------------ part 3: N = 2048 and 4096, four-step columns
+def _worst_dev(a, b):
+    """max |a - b| / max |a| of a numpy field and a device field."""
+    b = b.cpu().numpy()
+    return float(np.abs(a - b).max() / np.abs(a).max())
+
+
+def test_reference_backends_agree():
+    """phase_ref.TorchRef (complex128 torch.fft on the device) against the numpy functions it restates, N = 256,
+    the full-band frame at t = 100, the library's frame and the oracle's as the fp32 fields.  Each function on the
+    same input, to 1e-12 relative: ref_fields and its spectrum planes (of each field's maximum); every mirror-row
+    pair's rms, every column's rms and both floors of row_rms / col_rms on the numpy error fields d = got - ref
+    and d = oracle - ref, uploaded as they are; spec_rows.
+    The chain end to end cannot meet 1e-12 in float64 and is held to 1e-6: each backend subtracts its own ref,
+    two float64 transforms 2^-53 log2(N^2) ~ 2e-15 of the field apart, from fp32 data 2^-24 ~ 6e-8 of the field
+    away from either, so the error fields agree to 3e-8 of their own size and a single row's ratio to some tens
+    of that."""
+    n, t = 256, 100.0
+    cas = [R.full_band_cascade(n)]
+    ctx, (noise,) = _ctx_with_env({}, n, cas)
+    oc = O.OracleOcean(n, O.scene_params(), cas, noise)
+    ctx.step(t)
+    disp, deriv, _ = oc.step(t)
+    g_disp, g_deriv = ctx.read_all(oh.TEX_DISP), ctx.read_all(oh.TEX_DERIV)
+    ctx.close()
+    be = R.TorchRef()
+    ref, spec = R.ref_fields(oc.h0[0], oc.waves[0], t, True)
+    tref, tspec = be.ref_fields(oc.h0[0], oc.waves[0], t, True)
+    worst = {"ref_fields": max(_worst_dev(a, b) for a, b in zip(ref, tref)),
+             "spectrum": max(_worst_dev(a, b) for a, b in zip(spec, tspec)),
+             "spec_rows": max(float(np.abs(be.spec_rows(b) / R.spec_rows(a) - 1).max()) for a, b in zip(spec, tspec))}
+    got, own = R.out_fields(g_disp[0], g_deriv[0]), R.out_fields(disp[0], deriv[0])
+    tgot, town = be.out_fields(g_disp[0], g_deriv[0]), be.out_fields(disp[0], deriv[0])
+    assert all(_worst_dev(a, b) == 0.0 for a, b in zip(got + own, tgot + town))  # fp32 to float64: exact
+    for name, mine, theirs in (("row_rms", R.row_rms, be.row_rms), ("col_rms", R.col_rms, be.col_rms)):
+        per = floor = 0.0
+        for f, r in zip(got + own, ref + ref):
+            d = f - r
+            (a, fa), (b, fb) = mine(d), theirs(be.torch.from_numpy(d).to(be.device))
+            assert a.shape == b.shape == ((n // 2 + 1,) if name == "row_rms" else (n,)) and a.min() > 0
+            per, floor = max(per, float(np.abs(b / a - 1).max())), max(floor, abs(fb / fa - 1))
+        worst[name], worst[name + " floor"] = per, floor
+    a = R.frame_ratios(got, own, ref) + (R.blind_share(spec, own, ref),)
+    b = R.frame_ratios(tgot, town, tref, be=be) + (R.blind_share(tspec, town, tref, be=be),)
+    chain = max(abs(y / x - 1) for x, y in zip(a[:2], b[:2]))
+    print("backends, worst relative difference:", {k: f"{v:.2e}" for k, v in worst.items()},
+          f"; end to end: numpy {a}, torch {b}, {chain:.2e} apart")
+    for k, v in worst.items():
+        assert v <= 1e-12, f"{k}: {v:.2e}"
+    assert chain <= 1e-6 and a[2] == b[2]
+
+
+# id -> (N, cascades (None: the full-band scene), flags, knobs, uploaded H0, column parity, column bands, frames,
+#        pattern of kernel_name(0), pattern of kernel_name(1), (c rows, c columns))
+# c: by the rule above CASES.  Column bands: OCEAN_C4_BANDS, else the plan's own (frame_plan.h c4_bands: two where
+# four planes of 4096^2 exceed 256 MiB, one under a parity or with two planes).  One unit each: the kernels are templates on N, so these are the smallest shapes.
+# N = 4096 runs two frames, t = 100 and t_x (both paths of sincos_fast in one frame, and the larger phases):
+# a third adds the readback and the transforms of another 4 x 4096^2 frame to each case and runs no other code.
+# kernel_name(1) is the last kernel of the column call: k_col4s2<N, P, Q>.  k_col4s1<N, Q> is launched before
+# it inside the same call (fft4k.hip launch_pass_c4 / launch_pass_c4q: go_c1<N, Q> then go_c2<N, P, Q>), so the
+# k_col4s2 instantiation names its k_col4s1; no index of kernel_name reports it on its own.
+# What the plan (csrc/frame_plan.h) picks, against the table of the issue that asked for these cases:
+#   - N = 2048 has no three-plane frame and no mirror-pair row pass, so an uploaded H0 (h0k not valid) changes no
+#     kernel there: c4-2048-uploaded-h0 runs the kernels of c4-2048-four-planes.  It is kept for its input, a white
+#     spectrum in which every row and every inter-step twiddle weighs the same.
+#   - at N = 4096 with full outputs the plan picks k_pass_a3q with no knob; k_pass_a3pp is the row pass of a
+#     column parity (ocean_set_column_parity).  q-4096-a3pp runs two contexts, one per parity, and interleaves
+#     their compact columns into one frame: every mirror-row pair is then one k_pass_a3pp item of each.
+#   - q-4096-dense-scene runs the kernels of q-4096-a3q on scene cascade 0, whose band ends inside the grid.
+LARGE = {
+    "c4-2048-four-planes": (2048, None, 0, {}, False, False, 1, 3,
+                            r"k_pass_a3<2048, 4,", r"k_col4s2<2048, 4, false>", (1.18, 1.22)),
+    "c4-2048-bands-4": (2048, None, 0, {"OCEAN_C4_BANDS": "4"}, False, False, 4, 3,
+                        r"k_pass_a3<2048, 4,", r"k_col4s2<2048, 4, false>", (1.18, 1.22)),
+    "c4-2048-two-planes": (2048, None, D, {}, False, False, 1, 3,
+                           r"k_pass_a3<2048, 2,", r"k_col4s2<2048, 2, false>", (1.15, 1.07)),
+    "c4-2048-uploaded-h0": (2048, None, 0, {}, True, False, 1, 3,
+                            r"k_pass_a3<2048, 4,", r"k_col4s2<2048, 4, false>", (0.53, 0.58)),
+    "q-4096-a3pp": (4096, None, 0, {}, False, True, 1, 2,
+                    r"k_pass_a3pp<4096, (true|false)>", r"k_col4s2<4096, 4, true>", (1.38, 1.13)),
+    "q-4096-a3q": (4096, None, 0, {}, False, False, 2, 2,
+                   r"k_pass_a3q<4096, false>", r"k_col4s2<4096, 4, true>", (1.36, 1.14)),
+    "q-4096-dense-scene": (4096, [O.SCENE_CASCADES[0]], 0, {}, False, False, 2, 2,
+                           r"k_pass_a3q<4096, false>", r"k_col4s2<4096, 4, true>", (1.35, 1.12)),
+    "c4-4096-two-planes": (4096, None, D, {}, False, False, 1, 2,
+                           r"k_pass_a3<4096, 2,", r"k_col4s2<4096, 2, false>", (1.10, 1.15)),
+}
+
+
+def _read_whole(ctxs, tex, n):
+    """One unit's texture [1][N][N][4]: the context's own, or the compact halves of the two parity contexts
+    (column m of parity b holds x = 2 m + b) interleaved."""
+    if len(ctxs) == 1:
+        return ctxs[0].read_all(tex)
+    out = np.empty((1, n, n, 4), f32)
+    for b, ctx in enumerate(ctxs):
+        out[:, :, b::2] = ctx.read_all(tex)[:, :, : n // 2]
+    return out
+
+
+@pytest.mark.parametrize("case", list(LARGE))
+def test_rows_per_wavenumber_large(case):
+    """test_rows_per_wavenumber's assertions at N = 2048 (three frames) and 4096 (two: see LARGE), the float64
+    frame and the transforms of the error in complex128 torch.fft on the device (phase_ref.TorchRef), the oracle
+    threaded.  Also asserted: kernel_name(1), and one column call per band and frame (kernel_stats).
+    The oracle alone on the full-band scene, measured on the CPU before any device run: no row below the floor
+    at N = 2048 (t = 100, -37.5, t_x = 49 892) nor at N = 4096 (t = 100, t_x = 49 892), four planes or two
+    (blind_share 0.000 in all five frames), so the peak at a quarter of Nyquist still fills the rows."""
+    n, cas, flags, env, upload, parity, bands, frames, pat_rows, pat_cols, (c_row, c_col) = LARGE[case]
+    full_band = cas is None
+    cas = cas or [R.full_band_cascade(n)]
+    full = not flags & D
+    be = R.TorchRef()
+    ctxs = []
+    O.set_threads(oracle_threads())
+    try:
+        for b in range(2 if parity else 1):
+            ctx, (noise,) = _ctx_with_env(env, n, cas, flags=flags)
+            if parity:
+                ctx.set_column_parity(b)
+            ctx.set_kernel_timing(True)
+            ctxs.append(ctx)
+        oc = O.OracleOcean(n, O.scene_params(), cas, noise, nplanes=4 if full else 2)
+        if upload:
+            oc.h0[0] = _white_h0(n)
+            ctxs[0].write(oh.TEX_H0, oc.h0[0])
+        h0, waves = ctxs[0].read_all(oh.TEX_H0), ctxs[0].read_all(oh.TEX_WAVES)
+        assert np.array_equal(h0, oc.h0) and np.array_equal(waves, oc.waves)  # the library's own, bit-exact
+        times = (100.0, -37.5, R.crossing_time(waves[0], h0[0]))
+        times = times if frames == 3 else (times[0], times[2])
+        worst_rows = worst_cols = (0.0, 0, 0)
+        blind = 0.0
+        for t in times:
+            for ctx in ctxs:
+                ctx.step(t)
+            disp, deriv, turb = oc.step(t)
+            g_disp = _read_whole(ctxs, oh.TEX_DISP, n)
+            g_deriv = _read_whole(ctxs, oh.TEX_DERIV, n) if full else None
+            if full:
+                assert_channels(_read_whole(ctxs, oh.TEX_TURB, n), turb, tol=TOL, what=f"{case} t={t:g} turb")
+            ref, spec = be.ref_fields(h0[0], waves[0], t, full)
+            got = be.out_fields(g_disp[0], g_deriv[0] if full else None)
+            own = be.out_fields(disp[0], deriv[0] if full else None)
+            rows, cols = R.frame_ratios(got, own, ref, be=be, where=True)
+            worst_rows, worst_cols = max(worst_rows, rows), max(worst_cols, cols)
+            blind = max(blind, R.blind_share(spec, own, ref, be=be))
+            del ref, spec, got, own, disp, deriv, turb, g_disp, g_deriv
+        names = [(ctx.kernel_name(0), ctx.kernel_name(1)) for ctx in ctxs]
+        calls = [(ctx.kernel_stats(0)[1], ctx.kernel_stats(1)[1]) for ctx in ctxs]
+    finally:
+        O.set_threads(1)
+        for ctx in ctxs:
+            ctx.close()
+        be.torch.cuda.empty_cache()
+    print(f"{case}: t_x = {times[-1]:.6g}, worst row ratio {worst_rows[0]:.3f} (row pair {worst_rows[1]}, plane "
+          f"{worst_rows[2]}), worst column ratio {worst_cols[0]:.3f} (column {worst_cols[1]}, plane {worst_cols[2]}), "
+          f"rows below the floor {blind:.3f}, kernels {names}, calls {calls}")
+    for (rows_name, cols_name), call in zip(names, calls):
+        assert re.search(pat_rows, rows_name), rows_name
+        assert re.search(pat_cols, cols_name), cols_name
+        assert call == (len(times), bands * len(times))
+    if full_band:
+        assert blind <= 0.5, "more than half of the rows are checked against the floor only"
+    assert worst_rows[0] <= c_row, f"row ratio {worst_rows[0]:.3f} > {c_row}"
+    assert worst_cols[0] <= c_col, f"column ratio {worst_cols[0]:.3f} > {c_col}"

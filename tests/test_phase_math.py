@@ -1,7 +1,8 @@
 """The phase factor exp(i omega t) on the CPU: sincos_fast (csrc/spectrum_math.h) restated in numpy
 (tests/phase_ref.py), held to the header's "1-2 ulp" against float64 sin / cos over the argument sets that
 tests/test_gpu_phase.py then compares with the device bit for bit, and the per-wavenumber analysis of a frame
-checked against faults the norm-relative 1e-5 cannot see.  No GPU."""
+checked against faults the norm-relative 1e-5 cannot see, in a row's phase and in one twiddle of the four-step
+column transform (csrc/fft4k.hip, restated here at 16 x 16).  No GPU."""
 import math
 from fractions import Fraction
 
@@ -199,3 +200,135 @@ def test_row_check_on_numpy_sincos_and_on_one_ulp_of_omega(frame64):
     rows, cols, rel = _judge(fr, fr["build"](waves=waves))
     print(f"omega + 1 ulp on row {y}: row ratio {rows:.1f}, column ratio {cols:.2f}, rel_err {rel:.2e}")
     assert rows > 2.0 and rel <= 1e-5
+
+
+# ------------------------------------------------------------------ the check of the check, four-step columns
+# csrc/fft4k.hip splits the column transform of N = L1 L0 points, L1 = kL1 = 64 (N = 2048: 64 x 32, N = 4096:
+# 64 x 64), with y = y1 + L1 y0 and k = k0 + L0 k1:
+#   step 1 (k_col4s1)  A[y1][k0] = w_N^(y1 k0) sum_y0 X[y1 + L1 y0] w_L0^(y0 k0), left in the slot of X[y1 + L1 k0];
+#                      w_N^m = two[m % 64] two[64 + m / 64], a product of two fp32 table entries (float64 values
+#                      rounded, abi_context.cpp);
+#   step 2 (k_col4s2)  Y[k0 + L0 k1] = sum_y1 A[y1][k0] w_L1^(y1 k1): it reads the L1 rows of one k0 (the
+#                      transpose) and writes output row k0 + L0 k1, 16-column tiles, bands of whole tiles.
+# Restated here at N = 256 = 16 x 16 (L1 = L0 = 16, the inter-step table split 16 x 16 the same way): the real
+# split needs the float64 analysis of 2048^2 planes, minutes of numpy per variant, and the structure (two
+# sub-transforms, one twiddle per (y1, k0) formed from two table entries, the transpose, bands of 16-column
+# tiles) is the same.  The sub-transforms are radix-2 in complex64 with float64-rounded twiddles; the row pass
+# before them is the same radix-2 over the whole row.
+FS_N, FS_L1, FS_T = 256, 16, 100.0
+FS_C = math.sqrt(2.0) * 1.1  # two independent fp32 roundings of the oracle's size, plus 10 %
+
+
+def _dft_r2(z):
+    """sum_j z[j] w_L^(j k), w = exp(+2 pi i / L), along axis 0 of a complex64 array: radix-2, decimation in
+    time, fp32 arithmetic throughout (twiddles: float64 values rounded to fp32)."""
+    L = z.shape[0]
+    bits = L.bit_length() - 1
+    rev = np.array([int(format(i, f"0{bits}b")[::-1], 2) for i in range(L)])
+    z, rest = z[rev], z.shape[1:]
+    h = 1
+    while h < L:
+        w = np.exp(2j * np.pi * np.arange(h) / (2 * h)).astype(np.complex64).reshape((1, h) + (1,) * len(rest))
+        z = z.reshape((L // (2 * h), 2, h) + rest)
+        a, b = z[:, 0], z[:, 1] * w
+        z = np.stack([a + b, a - b], 1).reshape((L,) + rest)
+        h *= 2
+    assert z.dtype == np.complex64
+    return z
+
+
+def _four_step_columns(z, l1, fault=None, swap=None):
+    """The column transform of z[y][x] (complex64) as fft4k.hip runs it.  fault = (y1, k0, radians): that one
+    inter-step twiddle's angle is off.  swap = (row, x0, x1): output rows `row` and `row + 1` change places in
+    columns [x0, x1)."""
+    n = z.shape[0]
+    l0 = n // l1
+    s1 = _dft_r2(z.reshape(l0, l1, -1))                      # [k0][y1][x]: over y0 of X[y1 + L1 y0]
+    m = np.arange(l0)[:, None] * np.arange(l1)[None, :]     # y1 k0 < N
+    split = l1                                                # the two-level table: lo = m % split, hi = m / split
+    lo = np.exp(2j * np.pi * np.arange(split) / n).astype(np.complex64)
+    hi = np.exp(2j * np.pi * split * np.arange(n // split) / n).astype(np.complex64)
+    w = lo[m % split] * hi[m // split]                        # one complex64 product, as cmul(two[..], two[..])
+    if fault:
+        y1, k0, rad = fault
+        w[k0, y1] = np.complex64(complex(w[k0, y1]) * np.exp(1j * rad))
+    a = (s1 * w[:, :, None]).transpose(1, 0, 2)               # A[y1][k0][x]: the transpose step 2 reads through
+    out = _dft_r2(np.ascontiguousarray(a)).reshape(n, -1)     # [k1][k0] -> row k0 + L0 k1
+    if swap:
+        row, x0, x1 = swap
+        out[[row, row + 1], x0:x1] = out[[row + 1, row], x0:x1]
+    return out
+
+
+@pytest.fixture(scope="module")
+def frame256():
+    """One N = 256 full-band unit at t = 100: the oracle's spectrum planes and frame, the float64 frame, and the
+    frame rebuilt from the same planes by the radix-2 row pass and the four-step column passes."""
+    n, t = FS_N, FS_T
+    oc = O.OracleOcean(n, O.scene_params(), [R.full_band_cascade(n)], O.generate_noise(n, 20251121))
+    planes = [(q[0, ..., 0] + 1j * q[0, ..., 1]).astype(np.complex64) for q in O.evolve(oc.h0, oc.waves, t)]
+    disp, deriv, _ = oc.step(t)
+    ref, spec = R.ref_fields(oc.h0[0], oc.waves[0], t, True)
+    sgn = R._checker(n).astype(f32)
+    rows = [_dft_r2(np.ascontiguousarray(p.T)).T for p in planes]  # the row pass: over x
+
+    def build(**kw):
+        P = [(_four_step_columns(r, FS_L1, **kw) * sgn).astype(np.complex128) for r in rows]
+        return [P[0], P[1].real.copy(), P[2], P[3]]
+
+    return dict(n=n, own=R.out_fields(disp[0], deriv[0]), ref=ref, spec=spec, build=build)
+
+
+def _judge_fields(fr, got):
+    (rows, ry, rp), (cols, cx, cp) = R.frame_ratios(got, fr["own"], fr["ref"], where=True)
+    rel = max(O.rel_err(part(g), part(o)) for g, o in zip(got, fr["own"]) for part in (np.real, np.imag)
+              if np.any(part(o)))
+    return rows, cols, rel, (ry, rp), (cx, cp)
+
+
+def test_four_step_restatement_inside_the_bound(frame256):
+    """(a) The faultless four-step frame stays inside c = sqrt(2) x 1.1 of the radix-2 oracle in every mirror-row
+    pair and every column of every plane, and the scene is not blind at this size either."""
+    fr = frame256
+    rows, cols, rel, _, _ = _judge_fields(fr, fr["build"]())
+    blind = R.blind_share(fr["spec"], fr["own"], fr["ref"])
+    print(f"four-step {FS_L1} x {FS_N // FS_L1}, faultless: row ratio {rows:.3f}, column ratio {cols:.3f}, "
+          f"rel_err {rel:.2e}, rows below the floor {blind:.3f}")
+    assert blind <= 0.5
+    assert rows <= FS_C and cols <= FS_C and rel <= 1e-5
+
+
+def test_row_check_sees_a_four_step_twiddle_the_norm_cannot(frame256):
+    """(b) One inter-step twiddle, (y1, k0) = (5, 3), 1e-5 rad off: it reaches the L0 spectrum rows y = 5 (mod
+    L1) through every column, each with 1 / L0 of the fault, far under the norm and several times the rows' own
+    rounding.  Measured: worst row ratio 7.96, 5.12 times the bound, at a norm-relative error of 2.08e-6 to the
+    oracle; asserted: more than twice the bound, under 1e-5."""
+    fr = frame256
+    rows, cols, rel, (ry, rp), _ = _judge_fields(fr, fr["build"](fault=(5, 3, 1e-5)))
+    print(f"twiddle (y1, k0) = (5, 3) + 1e-5 rad: row ratio {rows:.2f} = {rows / FS_C:.2f} x the bound (row pair "
+          f"{ry}, plane {rp}), column ratio {cols:.2f}, rel_err {rel:.2e}")
+    assert rel <= 1e-5
+    assert rows > 2.0 * FS_C
+    assert ry % FS_L1 in (5, FS_L1 - 5)  # the pair holds a row y = 5 (mod L1): the fault is found where it is
+
+
+def test_column_check_confines_a_row_swap_to_its_band(frame256):
+    """Output rows 100 and 101 changed places in the column band [64, 128) only (a wrong row offset in one band of
+    k_col4s2): the columns of that band fail, every other column keeps the faultless ratio.  (The norm sees
+    this one too; what the per-column check adds is the band.)"""
+    fr = frame256
+    n, (x0, x1) = fr["n"], (64, 128)
+    base, got = fr["build"](), fr["build"](swap=(100, x0, x1))
+    _, cols0, _, _, _ = _judge_fields(fr, base)
+    rows, cols, rel, _, (cx, _) = _judge_fields(fr, got)
+    inside = np.zeros(n, bool)
+    inside[x0:x1] = True
+    per = np.zeros(n)  # the column ratio of worst_ratio, kept per column: worst plane
+    for g, o, r in zip(got, fr["own"], fr["ref"]):
+        own, floor = R.col_rms(o - r)
+        per = np.maximum(per, R.col_rms(g - r)[0] / np.maximum(own, floor))
+    print(f"rows 100 / 101 swapped in columns [{x0}, {x1}): column ratio {cols:.3g} = {cols / FS_C:.3g} x the bound "
+          f"(column {cx}), outside the band {per[~inside].max():.3f}, row ratio {rows:.3g}, rel_err {rel:.2e}")
+    assert x0 <= cx < x1 and cols > 2.0 * FS_C and rows > 2.0 * FS_C
+    assert per[inside].min() > FS_C, "a column of the band passes"
+    assert per[~inside].max() <= cols0 <= FS_C
