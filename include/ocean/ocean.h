@@ -77,7 +77,9 @@ extern "C" {
  *      Added later within version 4 in the same way: OCEAN_WHITECAP_MAX_RECORDS, ocean_whitecaps,
  *      ocean_whitecaps_device, ocean_whitecaps_async.
  *      Added later within version 4 in the same way: OCEAN_CAMERA_HITS, OCEAN_CAMERA_RANGE, OCEAN_CAMERA_COLOR,
- *      ocean_camera, ocean_camera_device, ocean_camera_async. */
+ *      ocean_camera, ocean_camera_device, ocean_camera_async.
+ *      Added later within version 4 in the same way: OCEAN_BODY_STEP_FLOATS, OCEAN_BODY_MAX_SUBSTEPS,
+ *      OCEAN_BODY_STEP_MAX_SAMPLES, ocean_body_step, ocean_body_step_device, ocean_body_step_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -896,11 +898,88 @@ int ocean_camera_device(ocean_ctx *ctx, int tile, int mode, int iterations, int 
 int ocean_camera_async(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine, const float *camera,
                        const float *material, int width, int height, float *out, size_t bytes, ocean_readback **req);
 
+/* Body steps: ocean_body_dynamics with the integrator behind it and a loop of S substeps around both, so that M
+ * rigid bodies advance S substeps in one launch and their state never leaves the device.  The reference's
+ * BuoyantObject.FixedUpdate runs several fixed updates per rendered frame against one frame of water; a host that
+ * does the same with the entries above pays, per substep, one latency-bound launch, a readback of the wrenches, the
+ * integration of M bodies on the CPU and an upload of their poses and motions.  Here a renderer reads the poses from
+ * a device pointer, and a host reads 128 B per body once per frame.  Needs a context created with OCEAN_F_VELOCITY.
+ *
+ *   hull:   float[P][5], exactly as ocean_body_buoyancy takes it.
+ *   state:  record b is float[32]: [0..9] = (c, q, s) as a `bodies` record of ocean_body_buoyancy, [10..15] = (v, o)
+ *           as a `motion` record of ocean_body_dynamics, [16..31] ignored.
+ *   props:  body b is float[4] = (im, jx, jy, jz): the inverse mass and the inverse principal moments of inertia in
+ *           the body frame.  A zero makes the body immovable by forces in that degree of freedom (g, an acceleration,
+ *           acts whatever im is: a body at rest for good has im = 0 in a call whose step has g = 0, or is left out).
+ *   step:   float[OCEAN_BODY_STEP_FLOATS] = (h, g, B, kd, kt, la, aa, 0), a host array in every form, read before the
+ *           call returns (like ocean_camera's `camera`): the substep in seconds, gravity's magnitude, the buoyant
+ *           force per unit of submerged volume (rho g), the coefficients of the drag force and the drag torque (the
+ *           host's k of the dynamics record), and the reference's `drag` and `angularDrag`, which damp against still
+ *           water while any probe is wet.  step[7] is reserved: pass 0.
+ *   out:    record b is float[32]: [0..15] = the state after `substeps` substeps, in the layout of `state`;
+ *           [16..31] = the ocean_body_dynamics record of the last substep, taken at the state that substep started
+ *           from.  `out` of one call is `state` of the next.
+ *
+ * All arithmetic is fp32, each line one rounding per operation in the order written (no fused multiply-add); sqrtf
+ * and / are correctly rounded.  With (u x a) = (u.y * a.z - u.z * a.y,  u.z * a.x - u.x * a.z,  u.x * a.y - u.y * a.x)
+ * and rot(u, w, a) the rotation ocean_body_buoyancy applies to a probe:
+ *       t = (2 * (u x a).x, 2 * (u x a).y, 2 * (u x a).z),    rot(u, w, a) = (a + w * t) + (u x t), componentwise
+ * one substep takes c, q = (u, qw) with u = (qx, qy, qz), s, v, o to c', q', s', v', o':
+ *       rec  = the 16-float record of ocean_body_dynamics for (hull, (c, q, s), (v, o), mode, iterations, law), bit
+ *              for bit (the same lanes, trip count and butterfly)
+ *       acc  = (im * (kd * rec[8]),   im * (B * rec[0] + kd * rec[9]) - g,   im * (kd * rec[10]))
+ *       tau  = (kt * rec[11] - B * rec[3],   kt * rec[12],   kt * rec[13] + B * rec[1])
+ *       tb   = rot((-u.x, -u.y, -u.z), qw, tau)                       (the torque in the body frame)
+ *       alp  = rot(u, qw, (jx * tb.x, jy * tb.y, jz * tb.z))          (no gyroscopic term, by definition)
+ *       v'   = (v.x + h * acc.x, v.y + h * acc.y, v.z + h * acc.z)
+ *       o'   = (o.x + h * alp.x, o.y + h * alp.y, o.z + h * alp.z)
+ *       if rec[15] > 0:   v'.i = v'.i - (v.i * la) * h,   o'.i = o'.i - (o.i * aa) * h   for i = x, y, z
+ *                                                     (the v and o the substep started from: a VelocityChange)
+ *       c'   = (c.x + h * v'.x, c.y + h * v'.y, c.z + h * v'.z)
+ *       hh   = 0.5f * h
+ *       n.i  = u.i + hh * (qw * o'.i + (o' x u).i)   for i = x, y, z
+ *       nw   = qw - hh * ((o'.x * u.x + o'.y * u.y) + o'.z * u.z)
+ *       len  = sqrtf(((n.x * n.x + n.y * n.y) + n.z * n.z) + nw * nw)
+ *       q'   = (n.x / len, n.y / len, n.z / len, nw / len),   s' = s
+ * (semi-implicit Euler: the new velocity moves the body; dq/dt = (o, 0) q / 2 with o in the world frame, then
+ * renormalised).  Substep k + 1 starts from the result of substep k.  The water (DISP, DERIV, VEL) is the frame's and
+ * the same for every substep of a call, as it is for the reference's fixed updates between two Updates.  The
+ * reference's FixedUpdate is the one-probe hull (0, 0.5, 0, 1, 1) in reference mode with im = 1, kd = kt = 0,
+ * B = g * density, la = drag, aa = angularDrag.  The library does not inspect hull, state or props values:
+ * non-finite inputs give unspecified numbers (never an access outside the textures).  Before the first ocean_step
+ * VEL and DISP are zero and the entry is valid.
+ *
+ * The three forms are those of ocean_body_dynamics: ocean_body_step takes host buffers and blocks;
+ * ocean_body_step_device takes device pointers for hull, props, state and out (inputs 4-B aligned, out 16-B aligned,
+ * else OCEAN_E_INVALID_ARG), is async on the ctx stream and bounds count by the sample limits alone; it allows
+ * out == state (in place): only the lanes of body b read or write record b, and they read before they write.  Any
+ * other overlap of out with an input is undefined.  ocean_body_step_async consumes `hull`, `props` and `state`
+ * before it returns, runs behind the steps queued so far and lands count x 128 B in `out` through the readback
+ * slots, with the same ocean_readback_status / _wait / _release / _copy_ms.  *req is NULL after every failure.
+ * All three: OCEAN_E_INVALID_ARG, checked before any device call, for everything ocean_body_dynamics refuses (the
+ * same OCEAN_BODY_MAX_* limits, `state` in the place of `bodies`), a null `step`, `props` or `state`, a `step` value
+ * that is not finite, substeps outside [1, OCEAN_BODY_MAX_SUBSTEPS] or count * probes * substeps >
+ * OCEAN_BODY_STEP_MAX_SAMPLES (in 64 bits); then OCEAN_E_UNSUPPORTED on a context without OCEAN_F_VELOCITY,
+ * OCEAN_E_STATE before ocean_init_spectrum and OCEAN_E_UNSUPPORTED on a column-parity context.  count = 0 is a
+ * no-op in the blocking and device forms and OCEAN_E_INVALID_ARG in the async form.  The launch counts as kind 2 of
+ * ocean_kernel_stats / ocean_kernel_name. */
+#define OCEAN_BODY_STEP_FLOATS 8
+#define OCEAN_BODY_MAX_SUBSTEPS 64
+#define OCEAN_BODY_STEP_MAX_SAMPLES (1 << 24)
+int ocean_body_step(ocean_ctx *ctx, int tile, int mode, int iterations, int law, int substeps, const float *step,
+                    const float *hull, int probes, const float *props, const float *state, int count, float *out);
+int ocean_body_step_device(ocean_ctx *ctx, int tile, int mode, int iterations, int law, int substeps, const float *step,
+                           const float *hull, int probes, const float *props, const float *state, int count,
+                           float *out);
+int ocean_body_step_async(ocean_ctx *ctx, int tile, int mode, int iterations, int law, int substeps, const float *step,
+                          const float *hull, int probes, const float *props, const float *state, int count, float *out,
+                          ocean_readback **req);
+
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
  * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async /
  * ocean_body_buoyancy_async / ocean_query_velocity_async / ocean_raycast_async / ocean_body_dynamics_async /
- * ocean_whitecaps_async / ocean_camera_async request records HIP timing events around its device-to-host copy, for
- * ocean_readback_copy_ms.  Requests made while it is off record only untimed events. */
+ * ocean_whitecaps_async / ocean_camera_async / ocean_body_step_async request records HIP timing events around its
+ * device-to-host copy, for ocean_readback_copy_ms.  Requests made while it is off record only untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 
 /* Duration of a completed request's device-to-host copy in ms (HIP events on the copy stream around

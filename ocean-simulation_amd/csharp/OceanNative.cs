@@ -147,6 +147,18 @@ namespace OceanHip
         public static extern OceanStatus ocean_body_dynamics_device(IntPtr ctx, int tile, int mode, int iterations, int law, IntPtr hull, int probes, IntPtr bodies, IntPtr motion, int count, IntPtr output);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_body_dynamics_async(IntPtr ctx, int tile, int mode, int iterations, int law, [In] float[] hull, int probes, [In] float[] bodies, [In] float[] motion, int count, IntPtr dst, out IntPtr request);
+        // Body steps (added within ABI 4 in the same way; OceanFlags.Velocity contexts).  `substeps` substeps of the rigid
+        // bodies in one launch: step [8] = (h, g, B, kd, kt, la, aa, 0), a host array in every form; props [count][4] =
+        // (1 / mass, 1 / Ix, 1 / Iy, 1 / Iz); state and output [count][32] = (bodies' 10, motion's 6, then the dynamics
+        // record of the last substep, ignored on input): the output of one call is the state of the next, and the
+        // _device form may be given output == state.
+        public const int BodyStepFloats = 8, BodyMaxSubsteps = 64, BodyStepMaxSamples = 1 << 24;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_step(IntPtr ctx, int tile, int mode, int iterations, int law, int substeps, [In] float[] step, [In] float[] hull, int probes, [In] float[] props, [In] float[] state, int count, [Out] float[] output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_step_device(IntPtr ctx, int tile, int mode, int iterations, int law, int substeps, [In] float[] step, IntPtr hull, int probes, IntPtr props, IntPtr state, int count, IntPtr output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_step_async(IntPtr ctx, int tile, int mode, int iterations, int law, int substeps, [In] float[] step, [In] float[] hull, int probes, [In] float[] props, [In] float[] state, int count, IntPtr dst, out IntPtr request);
         // Surface velocity (added within ABI 4 in the same way; OceanFlags.Velocity contexts).  8 floats per point: velocity
         // x, y, z of the water particle on the surface above the point, residual, height, p.x, p.z, dDxz/dt.
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

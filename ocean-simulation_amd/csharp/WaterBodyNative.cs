@@ -247,6 +247,20 @@ namespace OceanHip
             return output;
         }
 
+        // BuoyantObject.FixedUpdate for M bodies of P probes each, `substeps` fixed updates against this frame's water in
+        // one launch (ocean.h ocean_body_step; `velocity` set before Awake): state is [M][32] = (bodies' 10, motion's 6,
+        // 16 ignored), props [M][4] = (1 / mass, 1 / Ix, 1 / Iy, 1 / Iz), step [8] = (h, g, B, kd, kt, la, aa, 0).  Per
+        // body 32 floats: the state after the last substep, then Dynamics' record of that substep; the result is the
+        // next call's state.
+        public float[] StepBodies(float[] hull, float[] state, float[] props, float[] step, int substeps = 1,
+                                  int iterations = 4, int mode = OceanNative.QuerySurface, int law = OceanNative.DragLinear)
+        {
+            var output = new float[state.Length];
+            OceanNative.Check(OceanNative.ocean_body_step(ctx, 0, mode, iterations, law, substeps, step, hull, hull.Length / 5,
+                                                          props, state, state.Length / 32, output), "ocean_body_step");
+            return output;
+        }
+
         // The velocity (x, y, z) of the water particle on the surface above (worldX, worldZ), at the last step's time
         // (ocean.h ocean_query_velocity; `velocity` set before Awake): what drag relative to the water and particle
         // advection need.  The reference has no counterpart: BuoyantObject drags against still water.

@@ -1,5 +1,5 @@
 // C-ABI layer of liboceanhip.so, the point consumers (ocean.h): surface and velocity queries, surface grids,
-// buoyant bodies, body dynamics, ray casts, whitecap emitters and camera views, each in a _device, a blocking host
+// buoyant bodies, body dynamics, body steps, ray casts, whitecap emitters and camera views, each in a _device, a blocking host
 // and an _async form; and world sampling and the surface bounds, which keep bodies of their own.
 //
 // A consumer is stated once, as a struct built from its entry's arguments (a "family"), and its three entries
@@ -293,6 +293,52 @@ struct BodyDynamics : BodyBuoyancy {
     }
 };
 
+// Body steps: the state float[count][32] (in the place of the bodies), the props float[count][4] and the hull, with
+// the eight `step` floats by value -> the stepped state and the last substep's record, float[count][32].  Its records
+// alone fill a MiB of a slot, so its inputs start behind them (StageSlot).  The _device form may be given out == state.
+struct BodyStep : BodyBuoyancy {
+    int law, substeps;
+    const float* step;
+    const float* props;
+
+    // Its own arguments first, none of which needs the context (as the camera's: a host learns of a bad argument
+    // whatever its context is), then everything the bodies refuse.
+    int check(Form form) const {
+        if (!step || !props || !bodies) return fail(OCEAN_E_INVALID_ARG, "null step, props or state");
+        if (law != OCEAN_DRAG_LINEAR && law != OCEAN_DRAG_QUADRATIC) return fail(OCEAN_E_INVALID_ARG, "unknown drag law");
+        for (int k = 0; k < OCEAN_BODY_STEP_FLOATS; ++k)
+            if (!std::isfinite(step[k])) return fail(OCEAN_E_INVALID_ARG, "step[" + std::to_string(k) + "] is not finite");
+        if (substeps < 1 || substeps > OCEAN_BODY_MAX_SUBSTEPS)
+            return fail(OCEAN_E_INVALID_ARG, "substeps = " + std::to_string(substeps) + " outside [1, OCEAN_BODY_MAX_SUBSTEPS]");
+        if (count > 0 && probes > 0) {
+            const uint64_t samples = (uint64_t)count * (uint64_t)probes * (uint64_t)substeps;
+            if (samples > (uint64_t)OCEAN_BODY_STEP_MAX_SAMPLES)
+                return fail(OCEAN_E_INVALID_ARG, "count * probes * substeps = " + std::to_string(samples) +
+                                                     " > OCEAN_BODY_STEP_MAX_SAMPLES");
+        }
+        return BodyBuoyancy::check(form);
+    }
+    StateRule state() const { return {"ocean_body_step", "body steps on", Needs::Velocity}; }
+    StagedInputs inputs() const {
+        return {"hull, props and state",
+                3,
+                {{bodies, (size_t)count * 32 * 4}, {props, (size_t)count * 4 * 4}, {hull, (size_t)probes * 5 * 4}},
+                kStepInputOffset};
+    }
+    size_t out_bytes() const { return (size_t)count * 32 * 4; }
+    int launch(const float* const* in, float* d_out) const {
+        ocean::BodyStepParams sp;
+        std::copy(step, step + OCEAN_BODY_STEP_FLOATS, sp.p);
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] {
+                         return ocean::launch_body_step(v, ctx->vel, tile, mode, iterations, law, substeps, sp, in[2], probes,
+                                                        in[1], in[0], count, d_out, ctx->stream);
+                     },
+                     "body_step");
+    }
+};
+
 // Tile `tile`'s bounds records on the device, float[C][8], current on the ctx stream once this returns: the
 // two bounds launches (kind 2 of ocean_kernel_stats) are enqueued unless the cached records still match DISP.
 // (the caller has entered: OCEAN_ENTER)
@@ -542,6 +588,23 @@ int ocean_body_dynamics(ocean_ctx* ctx, int tile, int mode, int iterations, int 
 int ocean_body_dynamics_async(ocean_ctx* ctx, int tile, int mode, int iterations, int law, const float* hull, int probes,
                               const float* bodies, const float* motion, int count, float* out, ocean_readback** req) {
     return async_form(BodyDynamics{{ctx, tile, mode, iterations, hull, probes, bodies, count, out}, law, motion}, req);
+}
+
+int ocean_body_step_device(ocean_ctx* ctx, int tile, int mode, int iterations, int law, int substeps, const float* step,
+                           const float* hull, int probes, const float* props, const float* state, int count, float* out) {
+    return device_form(BodyStep{{ctx, tile, mode, iterations, hull, probes, state, count, out}, law, substeps, step, props});
+}
+
+int ocean_body_step(ocean_ctx* ctx, int tile, int mode, int iterations, int law, int substeps, const float* step,
+                    const float* hull, int probes, const float* props, const float* state, int count, float* out) {
+    return host_form(BodyStep{{ctx, tile, mode, iterations, hull, probes, state, count, out}, law, substeps, step, props});
+}
+
+int ocean_body_step_async(ocean_ctx* ctx, int tile, int mode, int iterations, int law, int substeps, const float* step,
+                          const float* hull, int probes, const float* props, const float* state, int count, float* out,
+                          ocean_readback** req) {
+    return async_form(BodyStep{{ctx, tile, mode, iterations, hull, probes, state, count, out}, law, substeps, step, props},
+                      req);
 }
 
 int ocean_raycast_device(ocean_ctx* ctx, int tile, int iterations, int steps, int refine, const float* rays, int count,

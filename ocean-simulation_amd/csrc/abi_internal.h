@@ -56,7 +56,12 @@ constexpr size_t kQuerySlotBytes = kQueryPointsOffset + (size_t)OCEAN_QUERY_MAX_
 constexpr size_t kDynamicsInputOffset = (size_t)OCEAN_BODY_MAX_BODIES * 16 * sizeof(float);
 constexpr size_t kDynamicsInputBytes = (size_t)OCEAN_BODY_MAX_BODIES * (10 + 6) * sizeof(float) +
                                        (size_t)OCEAN_BODY_MAX_PROBES * 5 * sizeof(float);
-constexpr size_t kStageInputBytes = std::max(kQuerySlotBytes - kQueryPointsOffset, kDynamicsInputBytes);
+// ocean_body_step_async outgrows both: its records alone are 1 MiB, so its inputs start at kStepInputOffset, right
+// behind them, and it is the largest the pinned copy holds.
+constexpr size_t kStepInputOffset = (size_t)OCEAN_BODY_MAX_BODIES * 32 * sizeof(float);
+constexpr size_t kStepInputBytes = (size_t)OCEAN_BODY_MAX_BODIES * (32 + 4) * sizeof(float) +
+                                   (size_t)OCEAN_BODY_MAX_PROBES * 5 * sizeof(float);
+constexpr size_t kStageInputBytes = std::max({kQuerySlotBytes - kQueryPointsOffset, kDynamicsInputBytes, kStepInputBytes});
 // What each consumer needs of a slot.  Bodies: the bodies, then the hull right behind them (floats both).
 constexpr size_t kBodyInputBytes = (size_t)OCEAN_BODY_MAX_BODIES * 10 * sizeof(float) +
                                    (size_t)OCEAN_BODY_MAX_PROBES * 5 * sizeof(float);
@@ -72,6 +77,14 @@ static_assert(kDynamicsInputBytes == 592 * 1024 && kDynamicsInputOffset == 512 *
 static_assert(kDynamicsInputOffset + kDynamicsInputBytes <= kQuerySlotBytes, "records and inputs fit the smallest slot");
 static_assert(kDynamicsInputBytes <= kStageInputBytes, "a slot's pinned input copy holds every dynamics request");
 static_assert(kDynamicsInputOffset % 16 == 0, "the inputs start float4-aligned");
+// Steps: the state, the props behind it, then the hull (floats all).  At the limits: 8192 x 128 B = 1024 KiB of state
+// + 8192 x 16 B = 128 KiB of props + 80 KiB of hull = 1232 KiB staged, and 8192 x 128 B = 1024 KiB of records, which
+// take the slot's first MiB; the inputs follow them at kStepInputOffset and end at 2256 KiB of the smallest slot's 2560.
+static_assert(kStepInputBytes == 1232 * 1024 && kStepInputOffset == 1024 * 1024, "the arithmetic above");
+static_assert(kQuerySlotBytes == 2560 * 1024, "the smallest slot");
+static_assert(kStepInputOffset + kStepInputBytes <= kQuerySlotBytes, "records and inputs fit the smallest slot");
+static_assert(kStepInputBytes <= kStageInputBytes, "a slot's pinned input copy holds every step request");
+static_assert(kStepInputOffset % 16 == 0, "the inputs start float4-aligned");
 // Rays: the staged rays and their records, 32 B each way, fill a slot's two regions exactly.
 static_assert((size_t)OCEAN_RAY_MAX_RAYS * 8 * sizeof(float) <= kQuerySlotBytes - kQueryPointsOffset,
               "a slot's pinned input copy holds every ray request");

@@ -35,6 +35,11 @@
 // and the sums of F, T and wet and the largest m over the wet probes ride the same lanes, trip count and
 // butterfly as the seven buoyancy terms; lane 0 stores four float4 (64 B per body, the first 32 B being the
 // buoyancy record bit for bit).
+//
+// ocean_body_step* (k_body_step<W>) puts the integrator of ocean.h behind those sums and a loop of S substeps
+// around both: the probe loop and the butterfly are one device function (body_wrench<W>) that both kernels call,
+// after it every lane of a body's segment holds all fourteen sums and advances the body's state in its own
+// registers, and lane 0 stores eight float4 (128 B per body: the state, then the last substep's record).
 #include "ocean_internal.h"
 #include "sample_filter.h"
 #include "spectrum_math.h"
@@ -42,15 +47,14 @@
 namespace ocean {
 namespace {
 
-// Body b's pose, float[10] = (c, q, s); a lane without a body keeps the identity and loads nothing.
+// A body's pose, float[10] = (c, q, s) at B; a lane without a body keeps the identity and loads nothing.
 struct Pose {
     float cx, cy, cz, ux, uy, uz, qw, sx, sy, sz;
 };
 
-__device__ __forceinline__ Pose load_pose(const float* __restrict__ bodies, size_t b, bool live) {
+__device__ __forceinline__ Pose load_pose(const float* B, bool live) {
     Pose q = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 1.0f, 1.0f};
     if (live) {
-        const float* B = bodies + 10 * b;
         q.cx = B[0], q.cy = B[1], q.cz = B[2];
         q.ux = B[3], q.uy = B[4], q.uz = B[5], q.qw = B[6];
         q.sx = B[7], q.sy = B[8], q.sz = B[9];
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(256) void k_body_buoyancy(DevView v, int tile, int 
     const int l = (int)(threadIdx.x % W);
     const size_t b = (size_t)blockIdx.x * kBodies + threadIdx.x / W;
     const bool live = b < (size_t)count;
-    const Pose pose = load_pose(bodies, b, live);
+    const Pose pose = load_pose(bodies + 10 * b, live);
     float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f, t3 = 0.0f, t4 = 0.0f, t5 = 0.0f, t6 = 0.0f, rmax = 0.0f;
     const int trips = (probes + W - 1) / W;  // the same for every lane of the launch
     for (int it = 0; it < trips; ++it) {
@@ -163,26 +167,25 @@ __device__ __forceinline__ void sample_cascades_vel(const DevView& v, const floa
     }
 }
 
-// ocean_body_dynamics*: the buoyancy record and, beside it, the drag of the water's velocity relative to the
-// hull, summed over the wet probes.  motion float[M][6] = (v, omega); out[4 b .. 4 b + 3] = record b (64 B).
-// The same mapping, trip count and butterfly as k_body_buoyancy<W>: fourteen sums and two maxima per lane.
+// Body b's motion, float[6] = (v, omega); a lane without a body is at rest.
+struct Motion {
+    float vx, vy, vz, ox, oy, oz;
+};
+
+// The fourteen sums and two maxima of ocean_body_dynamics, in the record's order: t0..t6 and rmax are the buoyancy
+// record, then sum F, sum T, the largest relative speed on the wet hull and the number of wet probes.
+struct Wrench {
+    float t0, t1, t2, t3, t4, t5, t6, rmax, f0, f1, f2, q0, q1, q2, mmax, wet;
+};
+
+// The probe loop and the butterfly of ocean_body_dynamics* for the body whose segment lane l belongs to, at the pose
+// and motion given: the same mapping, trip count and butterfly as k_body_buoyancy<W>.  Every lane of every wave
+// calls it (the __shfl_xor are executed by all), and every lane of a segment returns the body's sums.
 template <int W>
-__global__ __launch_bounds__(256) void k_body_dynamics(DevView v, const float4* __restrict__ vel, int tile, int mode,
-                                                       int iterations, int law, const float* __restrict__ hull,
-                                                       int probes, const float* __restrict__ bodies,
-                                                       const float* __restrict__ motion, int count,
-                                                       float4* __restrict__ out) {
-    constexpr int kBodies = 256 / W;  // bodies per workgroup
-    const int l = (int)(threadIdx.x % W);
-    const size_t b = (size_t)blockIdx.x * kBodies + threadIdx.x / W;
-    const bool live = b < (size_t)count;
-    const Pose pose = load_pose(bodies, b, live);
-    float vx = 0.0f, vy = 0.0f, vz = 0.0f, ox = 0.0f, oy = 0.0f, oz = 0.0f;
-    if (live) {
-        const float* Mo = motion + 6 * b;
-        vx = Mo[0], vy = Mo[1], vz = Mo[2];
-        ox = Mo[3], oy = Mo[4], oz = Mo[5];
-    }
+__device__ __forceinline__ Wrench body_wrench(const DevView& v, const float4* __restrict__ vel, int tile, int mode,
+                                              int iterations, int law, const float* __restrict__ hull, int probes,
+                                              const Pose& pose, const Motion& mo, int l, bool live) {
+    const float vx = mo.vx, vy = mo.vy, vz = mo.vz, ox = mo.ox, oy = mo.oy, oz = mo.oz;
     float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f, t3 = 0.0f, t4 = 0.0f, t5 = 0.0f, t6 = 0.0f, rmax = 0.0f;
     float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f, q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, wet = 0.0f, mmax = 0.0f;
     const int trips = (probes + W - 1) / W;  // the same for every lane of the launch
@@ -250,11 +253,114 @@ __global__ __launch_bounds__(256) void k_body_dynamics(DevView v, const float4* 
         mmax = fmaxf(mmax, __shfl_xor(mmax, s));
         wet = wet + __shfl_xor(wet, s);
     }
+    return {t0, t1, t2, t3, t4, t5, t6, rmax, f0, f1, f2, q0, q1, q2, mmax, wet};
+}
+
+// ocean_body_dynamics*: the buoyancy record and, beside it, the drag of the water's velocity relative to the
+// hull, summed over the wet probes.  motion float[M][6] = (v, omega); out[4 b .. 4 b + 3] = record b (64 B).
+// The same mapping, trip count and butterfly as k_body_buoyancy<W>: fourteen sums and two maxima per lane.
+template <int W>
+__global__ __launch_bounds__(256) void k_body_dynamics(DevView v, const float4* __restrict__ vel, int tile, int mode,
+                                                       int iterations, int law, const float* __restrict__ hull,
+                                                       int probes, const float* __restrict__ bodies,
+                                                       const float* __restrict__ motion, int count,
+                                                       float4* __restrict__ out) {
+    constexpr int kBodies = 256 / W;  // bodies per workgroup
+    const int l = (int)(threadIdx.x % W);
+    const size_t b = (size_t)blockIdx.x * kBodies + threadIdx.x / W;
+    const bool live = b < (size_t)count;
+    const Pose pose = load_pose(bodies + 10 * b, live);
+    Motion mo = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (live) {
+        const float* Mo = motion + 6 * b;
+        mo.vx = Mo[0], mo.vy = Mo[1], mo.vz = Mo[2];
+        mo.ox = Mo[3], mo.oy = Mo[4], mo.oz = Mo[5];
+    }
+    const Wrench r = body_wrench<W>(v, vel, tile, mode, iterations, law, hull, probes, pose, mo, l, live);
     if (live && l == 0) {
-        out[4 * b] = make_float4(t0, t1, t2, t3);
-        out[4 * b + 1] = make_float4(t4, t5, t6, rmax);
-        out[4 * b + 2] = make_float4(f0, f1, f2, q0);
-        out[4 * b + 3] = make_float4(q1, q2, mmax, wet);
+        out[4 * b] = make_float4(r.t0, r.t1, r.t2, r.t3);
+        out[4 * b + 1] = make_float4(r.t4, r.t5, r.t6, r.rmax);
+        out[4 * b + 2] = make_float4(r.f0, r.f1, r.f2, r.q0);
+        out[4 * b + 3] = make_float4(r.q1, r.q2, r.mmax, r.wet);
+    }
+}
+
+// a rotated by the quaternion (u, w), as place_probe rotates a probe: t = 2 (u x a), (a + w t) + (u x t).
+struct Vec3 {
+    float x, y, z;
+};
+
+__device__ __forceinline__ Vec3 rotate(float ux, float uy, float uz, float w, float ax, float ay, float az) {
+    const float tx = 2.0f * (uy * az - uz * ay), ty = 2.0f * (uz * ax - ux * az), tz = 2.0f * (ux * ay - uy * ax);
+    Vec3 r;
+    r.x = (ax + w * tx) + (uy * tz - uz * ty);
+    r.y = (ay + w * ty) + (uz * tx - ux * tz);
+    r.z = (az + w * tz) + (ux * ty - uy * tx);
+    return r;
+}
+
+// ocean_body_step*: `substeps` substeps of the integrator ocean.h states, each behind the wrench of
+// ocean_body_dynamics at the state it starts from, over one frame of water.  state float[M][32] = (c, q, s, v, omega,
+// 16 ignored); props float[M][4] = (im, jx, jy, jz); sp = (h, g, B, kd, kt, la, aa, 0), uniform; out[8 b .. 8 b + 7] =
+// the state after the last substep (four float4) and that substep's dynamics record (four float4).
+// The mapping of k_body_dynamics<W>.  State and props stay in registers over the substeps; substeps is uniform, so
+// every lane of every wave executes every __shfl_xor of every substep.  After the butterfly every lane of a segment
+// holds the body's sums and integrates redundantly: no broadcast, no branch on the lane.  `out` may be `state`
+// (neither is __restrict__): only body b's lanes touch record b, all of them load it here before lane 0 stores it.
+template <int W>
+__global__ __launch_bounds__(256) void k_body_step(DevView v, const float4* __restrict__ vel, int tile, int mode,
+                                                   int iterations, int law, int substeps, BodyStepParams sp,
+                                                   const float* __restrict__ hull, int probes,
+                                                   const float* __restrict__ props, const float* state, int count,
+                                                   float4* out) {
+    constexpr int kBodies = 256 / W;  // bodies per workgroup
+    const int l = (int)(threadIdx.x % W);
+    const size_t b = (size_t)blockIdx.x * kBodies + threadIdx.x / W;
+    const bool live = b < (size_t)count;
+    Pose pose = load_pose(state + 32 * b, live);
+    Motion mo = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    float im = 0.0f, jx = 0.0f, jy = 0.0f, jz = 0.0f;
+    if (live) {
+        const float* Mo = state + 32 * b + 10;
+        mo.vx = Mo[0], mo.vy = Mo[1], mo.vz = Mo[2];
+        mo.ox = Mo[3], mo.oy = Mo[4], mo.oz = Mo[5];
+        const float* Pr = props + 4 * b;
+        im = Pr[0], jx = Pr[1], jy = Pr[2], jz = Pr[3];
+    }
+    const float h = sp.p[0], g = sp.p[1], B = sp.p[2], kd = sp.p[3], kt = sp.p[4], la = sp.p[5], aa = sp.p[6];
+    const float hh = 0.5f * h;
+    Wrench r = {};
+    for (int step = 0; step < substeps; ++step) {
+        r = body_wrench<W>(v, vel, tile, mode, iterations, law, hull, probes, pose, mo, l, live);
+        const float ax = im * (kd * r.f0), ay = im * (B * r.t0 + kd * r.f1) - g, az = im * (kd * r.f2);
+        const float tx = kt * r.q0 - B * r.t3, ty = kt * r.q1, tz = kt * r.q2 + B * r.t1;
+        const Vec3 tb = rotate(-pose.ux, -pose.uy, -pose.uz, pose.qw, tx, ty, tz);  // the torque in the body frame
+        const Vec3 al = rotate(pose.ux, pose.uy, pose.uz, pose.qw, jx * tb.x, jy * tb.y, jz * tb.z);
+        float vx = mo.vx + h * ax, vy = mo.vy + h * ay, vz = mo.vz + h * az;
+        float ox = mo.ox + h * al.x, oy = mo.oy + h * al.y, oz = mo.oz + h * al.z;
+        if (r.wet > 0.0f) {  // damping against still water while any probe is wet, from the substep's first v, omega
+            vx = vx - (mo.vx * la) * h, vy = vy - (mo.vy * la) * h, vz = vz - (mo.vz * la) * h;
+            ox = ox - (mo.ox * aa) * h, oy = oy - (mo.oy * aa) * h, oz = oz - (mo.oz * aa) * h;
+        }
+        mo = {vx, vy, vz, ox, oy, oz};
+        pose.cx = pose.cx + h * vx, pose.cy = pose.cy + h * vy, pose.cz = pose.cz + h * vz;
+        const float ux = pose.ux, uy = pose.uy, uz = pose.uz, qw = pose.qw;
+        const float nx = ux + hh * (qw * ox + (oy * uz - oz * uy));
+        const float ny = uy + hh * (qw * oy + (oz * ux - ox * uz));
+        const float nz = uz + hh * (qw * oz + (ox * uy - oy * ux));
+        const float nw = qw - hh * ((ox * ux + oy * uy) + oz * uz);
+        const float len = sqrtf(((nx * nx + ny * ny) + nz * nz) + nw * nw);
+        pose.ux = nx / len, pose.uy = ny / len, pose.uz = nz / len, pose.qw = nw / len;
+    }
+    if (live && l == 0) {
+        out[8 * b] = make_float4(pose.cx, pose.cy, pose.cz, pose.ux);
+        out[8 * b + 1] = make_float4(pose.uy, pose.uz, pose.qw, pose.sx);
+        out[8 * b + 2] = make_float4(pose.sy, pose.sz, mo.vx, mo.vy);
+        out[8 * b + 3] = make_float4(mo.vz, mo.ox, mo.oy, mo.oz);
+        out[8 * b + 4] = make_float4(r.t0, r.t1, r.t2, r.t3);
+        out[8 * b + 5] = make_float4(r.t4, r.t5, r.t6, r.rmax);
+        out[8 * b + 6] = make_float4(r.f0, r.f1, r.f2, r.q0);
+        out[8 * b + 7] = make_float4(r.q1, r.q2, r.mmax, r.wet);
     }
 }
 
@@ -275,6 +381,16 @@ void launch_dynamics_w(const DevView& v, const float4* vel, int tile, int mode, 
     const unsigned g = (unsigned)(((size_t)count + kBodies - 1) / kBodies);  // as launch_w
     launch(k_body_dynamics<W>, dim3(g), dim3(256), 0, s, v, vel, tile, mode, iterations, law, hull, probes, bodies, motion,
            count, reinterpret_cast<float4*>(out));
+}
+
+template <int W>
+void launch_step_w(const DevView& v, const float4* vel, int tile, int mode, int iterations, int law, int substeps,
+                   const BodyStepParams& sp, const float* hull, int probes, const float* props, const float* state,
+                   int count, float* out, hipStream_t s) {
+    constexpr int kBodies = 256 / W;
+    const unsigned g = (unsigned)(((size_t)count + kBodies - 1) / kBodies);  // as launch_w
+    launch(k_body_step<W>, dim3(g), dim3(256), 0, s, v, vel, tile, mode, iterations, law, substeps, sp, hull, probes, props,
+           state, count, reinterpret_cast<float4*>(out));
 }
 
 }  // namespace
@@ -318,6 +434,26 @@ hipError_t launch_body_dynamics(const DevView& v, const float4* vel, int tile, i
         default: OCEAN_DYNAMICS_W(64); break;
     }
 #undef OCEAN_DYNAMICS_W
+    return hipGetLastError();
+}
+
+hipError_t launch_body_step(const DevView& v, const float4* vel, int tile, int mode, int iterations, int law, int substeps,
+                            const BodyStepParams& sp, const float* hull, int probes, const float* props,
+                            const float* state, int count, float* out, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    if (probes < 1 || substeps < 1 || !vel) return hipErrorInvalidValue;
+#define OCEAN_STEP_W(w) \
+    launch_step_w<w>(v, vel, tile, mode, iterations, law, substeps, sp, hull, probes, props, state, count, out, s)
+    switch (body_segment_width(probes)) {
+        case 1: OCEAN_STEP_W(1); break;
+        case 2: OCEAN_STEP_W(2); break;
+        case 4: OCEAN_STEP_W(4); break;
+        case 8: OCEAN_STEP_W(8); break;
+        case 16: OCEAN_STEP_W(16); break;
+        case 32: OCEAN_STEP_W(32); break;
+        default: OCEAN_STEP_W(64); break;
+    }
+#undef OCEAN_STEP_W
     return hipGetLastError();
 }
 

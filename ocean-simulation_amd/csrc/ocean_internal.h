@@ -178,6 +178,15 @@ hipError_t launch_body_buoyancy(const DevView& v, int tile, int mode, int iterat
 hipError_t launch_body_dynamics(const DevView& v, const float4* vel, int tile, int mode, int iterations, int law,
                                 const float* hull, int probes, const float* bodies, const float* motion, int count,
                                 float* out, hipStream_t s);
+// body.hip: substeps of the rigid bodies behind that record (ocean_body_step*), device pointers: props float[count][4],
+// state float[count][32], out float[count][32], which may be `state` itself; sp = the entry's eight `step` floats,
+// which travel as a kernel argument
+struct BodyStepParams {
+    float p[OCEAN_BODY_STEP_FLOATS];
+};
+hipError_t launch_body_step(const DevView& v, const float4* vel, int tile, int mode, int iterations, int law, int substeps,
+                            const BodyStepParams& sp, const float* hull, int probes, const float* props,
+                            const float* state, int count, float* out, hipStream_t s);
 // velocity.hip: surface velocity (OCEAN_F_VELOCITY).  `scratch` is the context's two velocity planes, float2
 // [2][U][N][N] plane-major: launch_evolve_velocity writes the packed planes of dh/dt at t there (from v.h0 and
 // v.waves), the operator IFFT transforms them in place as 2 U unit-planes, launch_pack_velocity interleaves them

@@ -4,8 +4,14 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|step]
 //
+// With step the host plays F frames on a velocity context and, behind each, advances a fleet of six boxes of 4 x 3
+// probes by 4 substeps of 1/240 s through one WaterBody::StepBodies in its async form (surface mode, 4 steps,
+// quadratic drag), each call fed by the one before; it writes hull.bin, props.bin (float32 [6][4]), step.bin (float32
+// [8]), state0.bin (float32 [6][32], the first call's input) and step_out.bin (float32 [6][32], the
+// last call's output); the summary line carries those records too ("records", %.9g: exact for fp32);
+// tests/test_gpu_step_host.py checks them.
 // With camera the host reads nothing back per frame: it runs F steps, then one WaterBody::Camera for a fixed camera of
 // 45 x 37 pixels (2 fixed-point steps, 32 march steps, 6 bisections): the shaded picture under a fixed material; it
 // writes camera.bin (float32 [14]), material.bin (float32 [32]) and color.bin (float32 [37][45][4]); the summary line
@@ -60,13 +66,13 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|step]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
     if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity" &&
-        mode != "rays" && mode != "dynamics" && mode != "whitecaps" && mode != "camera") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps or camera\n");
+        mode != "rays" && mode != "dynamics" && mode != "whitecaps" && mode != "camera" && mode != "step") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps, camera or step\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -123,6 +129,50 @@ int main(int argc, char** argv) {
             std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"probes\": %zu, \"bodies\": %zu, \"records\": [", F, n,
                         (int)wb.cascades.size(), hull.size() / 5, bodies.size() / 10);
             for (size_t i = 0; i < rec.size(); ++i) std::printf("%s%.9g", i ? ", " : "", rec[i]);
+            std::printf("]}\n");
+            wb.OnDisable();
+            return 0;
+        }
+        if (mode == "step") {
+            const int substeps = 4;
+            // a box of 4 x 3 cells (x fastest, then z), one layer, as the buoyancy mode's
+            std::vector<float> hull;
+            for (int k = 0; k < 3; ++k)
+                for (int i = 0; i < 4; ++i) {
+                    const float cell[5] = {((float)i + 0.5f) / 4.0f - 0.5f, 0.0f, ((float)k + 0.5f) / 3.0f - 0.5f, 1.0f,
+                                           1.0f / 12.0f};
+                    hull.insert(hull.end(), cell, cell + 5);
+                }
+            // six boxes: origin, quaternion (x, y, z, w), scale, linear and angular velocity; the record behind is zero
+            const float fleet[6][16] = {
+                {0.0f,    0.0f,   0.0f,     0.0f,  0.0f,  0.0f,  1.0f,  4.0f, 1.0f,  2.0f, 0.0f,  0.0f,   0.0f,  0.0f,  0.0f,   0.0f},
+                {37.5f,   0.25f,  -12.25f,  0.5f,  0.5f,  0.5f,  0.5f,  3.0f, 2.0f,  3.0f, 1.0f,  2.0f,   -3.0f, 0.0f,  0.0f,   0.0f},
+                {-410.0f, -0.5f,  250.75f,  0.0f,  0.0f,  0.6f,  0.8f,  6.0f, 1.5f,  2.5f, 0.0f,  0.0f,   0.0f,  0.0f,  1.0f,   0.0f},
+                {1e4f,    0.125f, -3333.0f, 0.28f, 0.0f,  0.0f,  0.96f, 2.0f, 0.75f, 8.0f, -2.5f, 0.125f, 4.0f,  0.25f, -0.5f,  0.75f},
+                {-0.5f,   -0.25f, (float)n, 0.0f,  -0.6f, 0.0f,  0.8f,  5.0f, 3.0f,  1.0f, 0.5f,  -1.0f,  0.25f, -1.5f, 0.125f, 0.0f},
+                {12.0f,   30.0f,  7.0f,     0.0f,  0.0f,  0.0f,  1.0f,  1.0f, 1.0f,  1.0f, 0.0f,  0.0f,   0.0f,  0.0f,  0.0f,   0.5f}};
+            std::vector<float> state(6 * 32, 0.0f);
+            for (int b = 0; b < 6; ++b) std::copy(fleet[b], fleet[b] + 16, state.begin() + 32 * b);
+            // inverse mass and inverse principal moments; the last body is deaf to torques
+            const std::vector<float> props = {0.125f, 0.5f, 0.25f, 1.0f,  0.0625f, 0.125f, 0.125f, 0.125f, 0.05f, 0.1f, 0.02f, 0.2f,
+                                              0.1f,   0.3f, 0.05f, 0.02f, 0.07f,   0.04f,  0.2f,   0.01f,  1.0f,  0.0f, 0.0f,  0.0f};
+            // h, g, B, kd, kt, la, aa, 0
+            const std::vector<float> step = {1.0f / 240.0f, 9.81f, 9.81f, 0.5f, 0.25f, 0.5f, 0.25f, 0.0f};
+            wb.velocity = true;
+            wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
+            wb.Awake();
+            write_bin(out + "/state0.bin", state.data(), state.size());
+            for (int f = 0; f < F; ++f) {
+                wb.Update((float)f / 60.0f);
+                state = wb.StepBodies(hull, state, props, step, substeps, 4, OCEAN_QUERY_SURFACE, OCEAN_DRAG_QUADRATIC, true);
+            }
+            write_bin(out + "/hull.bin", hull.data(), hull.size());
+            write_bin(out + "/props.bin", props.data(), props.size());
+            write_bin(out + "/step.bin", step.data(), step.size());
+            write_bin(out + "/step_out.bin", state.data(), state.size());
+            std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"probes\": %zu, \"bodies\": %zu, \"substeps\": %d, "
+                        "\"records\": [", F, n, (int)wb.cascades.size(), hull.size() / 5, state.size() / 32, substeps);
+            for (size_t i = 0; i < state.size(); ++i) std::printf("%s%.9g", i ? ", " : "", state[i]);
             std::printf("]}\n");
             wb.OnDisable();
             return 0;

@@ -227,6 +227,42 @@ public:
         return out;
     }
 
+    // BuoyantObject.FixedUpdate for M bodies of P probes each, `substeps` fixed updates against this frame's water in
+    // one launch (ocean.h ocean_body_step; `velocity` set before Awake): state [M][32] = (bodies' 10, motion's 6, 16
+    // ignored), props [M][4] = (1 / mass, 1 / Ix, 1 / Iy, 1 / Iz), step [8] = (h, g, B, kd, kt, la, aa, 0) -> 32 floats
+    // per body: the state after the last substep, then Dynamics' record of that substep; the result is the next
+    // call's state.  async: through ocean_body_step_async and a pinned buffer, waited for here (what a host that
+    // overlaps the copy with its frame does, in one place).
+    std::vector<float> StepBodies(const std::vector<float>& hull, const std::vector<float>& state,
+                                  const std::vector<float>& props, const std::vector<float>& step, int substeps = 1,
+                                  int iterations = 4, int mode = OCEAN_QUERY_SURFACE, int law = OCEAN_DRAG_LINEAR,
+                                  bool async = false) const {
+        const int count = (int)(state.size() / 32);
+        if (props.size() / 4 != state.size() / 32) throw std::runtime_error("StepBodies: one props record per body");
+        if (step.size() != OCEAN_BODY_STEP_FLOATS) throw std::runtime_error("StepBodies: step is float[8]");
+        std::vector<float> out(state.size() / 32 * 32);
+        if (!async) {
+            check(ocean_body_step(ctx_, 0, mode, iterations, law, substeps, step.data(), hull.data(), (int)(hull.size() / 5),
+                                  props.data(), state.data(), count, out.data()),
+                  "ocean_body_step");
+            return out;
+        }
+        void* pinned = nullptr;
+        check(ocean_host_alloc(out.size() * sizeof(float), &pinned), "ocean_host_alloc");
+        ocean_readback* req = nullptr;
+        int rc = ocean_body_step_async(ctx_, 0, mode, iterations, law, substeps, step.data(), hull.data(),
+                                       (int)(hull.size() / 5), props.data(), state.data(), count, static_cast<float*>(pinned),
+                                       &req);
+        if (rc == OCEAN_OK) {
+            rc = ocean_readback_wait(req);
+            if (rc == OCEAN_OK) std::copy(static_cast<float*>(pinned), static_cast<float*>(pinned) + out.size(), out.begin());
+            ocean_readback_release(req);
+        }
+        ocean_host_free(pinned);
+        check(rc, "ocean_body_step_async");
+        return out;
+    }
+
     // The water's velocity at M world positions (ocean.h ocean_query_velocity; `velocity` set before Awake):
     // points [M][2] = (world x, world z) -> 8 floats per point: velocity x, y, z of the water particle on the
     // surface above the point, residual, height, p.x, p.z, dDxz/dt.  What drag relative to the water and particle

@@ -74,6 +74,7 @@ EXPORTED_SYMBOLS = (
     "ocean_body_dynamics", "ocean_body_dynamics_device", "ocean_body_dynamics_async",
     "ocean_whitecaps", "ocean_whitecaps_device", "ocean_whitecaps_async",
     "ocean_camera", "ocean_camera_device", "ocean_camera_async",
+    "ocean_body_step", "ocean_body_step_device", "ocean_body_step_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -101,6 +102,10 @@ CAMERA_FLOATS = 14
 CAMERA_MATERIAL_FLOATS = 32
 CAMERA_MAX_PIXELS = 1 << 22
 CAMERA_MAX_SAMPLES = 1 << 28
+# ocean_body_step* array size and limits (ocean.h); modes, laws and the body limits are the dynamics'
+BODY_STEP_FLOATS = 8
+BODY_MAX_SUBSTEPS = 64
+BODY_STEP_MAX_SAMPLES = 1 << 24
 
 
 class OceanError(RuntimeError):
@@ -198,6 +203,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_camera": ([P, i, i, i, i, i, P, P, i, i, P, sz], i),
         "ocean_camera_device": ([P, i, i, i, i, i, P, P, i, i, P, sz], i),
         "ocean_camera_async": ([P, i, i, i, i, i, P, P, i, i, P, sz, ctypes.POINTER(P)], i),
+        "ocean_body_step": ([P, i, i, i, i, i, P, P, i, P, P, i, P], i),
+        "ocean_body_step_device": ([P, i, i, i, i, i, P, P, i, P, P, i, P], i),
+        "ocean_body_step_async": ([P, i, i, i, i, i, P, P, i, P, P, i, P, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -260,6 +268,16 @@ def material(color=(0.02, 0.1, 0.16), roughness: float = 0.3, ex: float = 0.25, 
 
 
 _material = material  # (WaterBody.Camera has a parameter of that name)
+
+
+def step_params(h: float, g: float = 9.81, buoyancy: Optional[float] = None, drag: float = 0.0, drag_torque: float = 0.0,
+                linear_damping: float = 0.0, angular_damping: float = 0.0, density: float = 1.0) -> np.ndarray:
+    """The float32[8] `step` of ocean_body_step (ocean.h) = (h, g, B, kd, kt, la, aa, 0): the substep in seconds,
+    gravity's magnitude, the buoyant force per unit of submerged volume (`buoyancy`, by default g * density, the
+    reference's BuoyantObject), the coefficients of the drag force and torque against the water's velocity, and the
+    reference's `drag` and `angularDrag` (damping against still water while a probe is wet).  Rounded once."""
+    b = float(g) * float(density) if buoyancy is None else float(buoyancy)
+    return np.array([h, g, b, drag, drag_torque, linear_damping, angular_damping, 0.0], np.float32)
 
 
 class OceanContext:
@@ -705,6 +723,73 @@ class OceanContext:
         _check(self.lib.ocean_body_dynamics_device(self._h, tile, mode, iterations, law, vp(hull_ptr), probes,
                                                    vp(bodies_ptr), vp(motion_ptr), count, vp(out_ptr)),
                "ocean_body_dynamics_device")
+
+    @staticmethod
+    def _step_args(hull, state, props, step):
+        h = np.ascontiguousarray(hull, np.float32)
+        s = np.ascontiguousarray(state, np.float32)
+        p = np.ascontiguousarray(props, np.float32)
+        sp = np.ascontiguousarray(step, np.float32).reshape(-1)
+        if h.ndim != 2 or h.shape[1] != 5:
+            raise ValueError(f"hull must be float32[P][5] = (rx, ry, rz, h, v), got {h.shape}")
+        if s.ndim != 2 or s.shape[1] != 32:
+            raise ValueError(f"state must be float32[M][32] = (c, quaternion xyzw, scale, v, omega, 16 more), got {s.shape}")
+        if p.shape != (s.shape[0], 4):
+            raise ValueError(f"props must be float32[M][4] = (1 / mass, 1 / Ix, 1 / Iy, 1 / Iz) for M = {s.shape[0]}, got {p.shape}")
+        if sp.shape[0] != BODY_STEP_FLOATS:
+            raise ValueError(f"step must be float32[{BODY_STEP_FLOATS}] (step_params), got {sp.shape}")
+        return h, s, p, sp
+
+    @staticmethod
+    def body_state(bodies, motion=None) -> np.ndarray:
+        """float32[M][32] for body_step from bodies float[M][10] and motion float[M][6] (at rest by default); the
+        sixteen floats behind them, which the entry ignores on input, are zero."""
+        b = np.ascontiguousarray(bodies, np.float32)
+        s = np.zeros((b.shape[0], 32), np.float32)
+        s[:, :10] = b
+        if motion is not None:
+            s[:, 10:16] = motion
+        return s
+
+    def body_step(self, hull, state, props, step, substeps: int = 1, iterations: int = 4, mode: int = QUERY_SURFACE,
+                  law: int = DRAG_LINEAR, tile: int = 0) -> np.ndarray:
+        """`substeps` substeps of M rigid bodies on the device (ocean.h ocean_body_step; F_VELOCITY contexts),
+        blocking: state float[M][32] = (bodies' record, motion's record, 16 ignored), props float[M][4] = (inverse
+        mass, inverse principal moments), step float[8] (step_params) -> float32[M][32]: the state after the last
+        substep, then body_dynamics' record of that substep.  The result is the next call's `state`."""
+        h, s, p, sp = self._step_args(hull, state, props, step)
+        out = np.empty((s.shape[0], 32), np.float32)
+        _check(self.lib.ocean_body_step(self._h, tile, mode, iterations, law, substeps, sp.ctypes.data, h.ctypes.data,
+                                        h.shape[0], p.ctypes.data, s.ctypes.data, s.shape[0], out.ctypes.data),
+               "ocean_body_step")
+        return out
+
+    def body_step_async(self, hull, state, props, step, substeps: int = 1, iterations: int = 4, mode: int = QUERY_SURFACE,
+                        law: int = DRAG_LINEAR, tile: int = 0, buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_body_step_async), as body_dynamics_async: float32[M][32] lands in pinned host
+        memory; `hull`, `state`, `props` and `step` are consumed by the call.  `buf`: a caller-owned pinned slot of
+        at least M x 128 B."""
+        h, s, p, sp = self._step_args(hull, state, props, step)
+        return Readback(self, (s.shape[0], 32), s.shape[0] * 128, "ocean_body_step_async",
+                        lambda dst, req: self.lib.ocean_body_step_async(self._h, tile, mode, iterations, law, substeps,
+                                                                        sp.ctypes.data, h.ctypes.data, h.shape[0],
+                                                                        p.ctypes.data, s.ctypes.data, s.shape[0], dst, req),
+                        buf)
+
+    def body_step_device(self, hull_ptr: int, probes: int, props_ptr: int, state_ptr: int, count: int, out_ptr: int, step,
+                         substeps: int = 1, iterations: int = 4, mode: int = QUERY_SURFACE, law: int = DRAG_LINEAR,
+                         tile: int = 0) -> None:
+        """The device-pointer form (ocean_body_step_device): hull float[probes][5], props float[count][4], state
+        float[count][32] and out float[count][32] live on this context's device (inputs 4-B, out 16-B aligned), and
+        out_ptr may equal state_ptr (in place); `step` is a host array (step_params).  Async on the context's
+        stream, after the queued steps."""
+        vp = ctypes.c_void_p
+        sp = np.ascontiguousarray(step, np.float32).reshape(-1)
+        if sp.shape[0] != BODY_STEP_FLOATS:
+            raise ValueError(f"step must be float32[{BODY_STEP_FLOATS}] (step_params), got {sp.shape}")
+        _check(self.lib.ocean_body_step_device(self._h, tile, mode, iterations, law, substeps, sp.ctypes.data, vp(hull_ptr),
+                                               probes, vp(props_ptr), vp(state_ptr), count, vp(out_ptr)),
+               "ocean_body_step_device")
 
     @staticmethod
     def box_hull(nx: int, nz: int, ny: int = 1) -> np.ndarray:
@@ -1174,6 +1259,12 @@ class WaterBody:
         (OceanContext.body_dynamics; `velocity=True`).  The reference drags against still water
         (BuoyantObject.FixedUpdate: -rb.velocity * drag)."""
         return self.ctx.body_dynamics(hull, bodies, motion, iterations, mode, law, tile)
+
+    def StepBodies(self, hull, state, props, step, substeps: int = 1, iterations: int = 4, mode: int = QUERY_SURFACE,
+                   law: int = DRAG_LINEAR, tile: int = 0) -> np.ndarray:
+        """BuoyantObject.FixedUpdate for M bodies of P probes each, `substeps` fixed updates against this frame's
+        water in one launch (OceanContext.body_step; `velocity=True`): float32[M][32], the next call's `state`."""
+        return self.ctx.body_step(hull, state, props, step, substeps, iterations, mode, law, tile)
 
     def GetWaterVelocity(self, worldPosition, iterations: int = 4, tile: int = 0) -> np.ndarray:
         """The velocity (x, y, z) of the water particle on the surface above worldPosition (x and z are used, as
