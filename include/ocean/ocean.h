@@ -79,7 +79,10 @@ extern "C" {
  *      Added later within version 4 in the same way: OCEAN_CAMERA_HITS, OCEAN_CAMERA_RANGE, OCEAN_CAMERA_COLOR,
  *      ocean_camera, ocean_camera_device, ocean_camera_async.
  *      Added later within version 4 in the same way: OCEAN_BODY_STEP_FLOATS, OCEAN_BODY_MAX_SUBSTEPS,
- *      OCEAN_BODY_STEP_MAX_SAMPLES, ocean_body_step, ocean_body_step_device, ocean_body_step_async. */
+ *      OCEAN_BODY_STEP_MAX_SAMPLES, ocean_body_step, ocean_body_step_device, ocean_body_step_async.
+ *      Added later within version 4 in the same way: OCEAN_ATMOSPHERE_FLOATS, OCEAN_ATMOSPHERE_MAX_DIM, OCEAN_LUT_*,
+ *      OCEAN_CAMERA_SKY_LUT, ocean_atmosphere, ocean_sky_update, ocean_atmosphere_read, ocean_atmosphere_lut,
+ *      ocean_sun_color. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -836,7 +839,8 @@ int ocean_whitecaps_async(ocean_ctx *ctx, int tile, float lod, float threshold, 
  *   - no shadow map: the shadow factor is 1, so the sun's lobes are not attenuated and the shadow lerp of :370
  *     (whose weight is then 0) is left out, _ShadowsColor and _ShadowsIntensity with it;
  *   - no opaque or depth texture: UnderwaterView is its fog limit, the water colour;
- *   - no cubemap: sky(r) = HZ + saturate(r.y) * (ZN - HZ), per channel.
+ *   - no cubemap: sky(r) = HZ + saturate(r.y) * (ZN - HZ), per channel (with OCEAN_CAMERA_SKY_LUT: the atmosphere's
+ *     sky-view table, "The atmosphere" below).
  * With sat(x) = fminf(fmaxf(x, 0), 1), dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z, pi = (float)3.14159265358979
  * and tiny = 1.175494351e-38f, a HIT pixel is
  *       hr  = V + L;   h = hr / sqrtf(dot(hr, hr))                                  (the halfway vector, three divisions)
@@ -891,6 +895,7 @@ int ocean_whitecaps_async(ocean_ctx *ctx, int tile, float lod, float threshold, 
 #define OCEAN_CAMERA_MATERIAL_FLOATS 32
 #define OCEAN_CAMERA_MAX_PIXELS (1 << 22)
 #define OCEAN_CAMERA_MAX_SAMPLES (1 << 28)
+#define OCEAN_CAMERA_SKY_LUT 16 /* valid only as OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT: see "The atmosphere" below */
 int ocean_camera(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine, const float *camera,
                  const float *material, int width, int height, float *out, size_t bytes);
 int ocean_camera_device(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine, const float *camera,
@@ -974,6 +979,152 @@ int ocean_body_step_device(ocean_ctx *ctx, int tile, int mode, int iterations, i
 int ocean_body_step_async(ocean_ctx *ctx, int tile, int mode, int iterations, int law, int substeps, const float *step,
                           const float *hull, int probes, const float *props, const float *state, int count, float *out,
                           ocean_readback **req);
+
+/* The atmosphere: the sky a sea picture reflects, and the colour of the light on it.  In the reference scene the
+ * water's environment term (Water.shader:181-187) reads a reflection probe of the skybox, which is Atmosphere.shader
+ * over the sky-view table of AtmosphereController.cs, and the light's colour comes from the transmittance table
+ * (AtmosphereController.cs:129-154, :187-188).  Its three compute shaders are restated here; the context owns the three
+ * tables, and OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT shades with the third in place of the two-colour sky.
+ *
+ * `params` is float[OCEAN_ATMOSPHERE_FLOATS], a host array read before the call returns and passed to the kernels by
+ * value (like `camera`); the names are AtmosphereController's fields, the defaults its own:
+ *       [0]      Rp     planetRadius 6360000                     [1]      Ra     atmosphereRadius 6420000
+ *       [2..4]   RS     rayleighScatteringCoefficient (5.802e-6, 13.558e-6, 6.5e-5)
+ *       [5..7]   RA     rayleighAbsorptionCoefficient (0, 0, 0)   [8]      HR     rayleighScaleHeight 8000
+ *       [9..11]  MS     mieScatteringCoefficient (3.996e-6 x 3)
+ *       [12..14] MA     mieAbsorptionCoefficient (4.4e-6 x 3)     [15]     HM     mieScaleHeight 1200
+ *       [16]     g      0.85
+ *       [17..19] OS     ozoneScatteringCoefficient (0, 0, 0)      [20..22] OA     ozoneAbsorptionCoefficient (0.65e-6, 1.881e-6, 0.085e-6)
+ *       [23..25] GA     groundAlbedo (0, 0, 0)
+ *       [26]     SZ     _SunSize of Atmosphere.shader, 0.04
+ *       [27..31] reserved: pass 0
+ *
+ * A table is float4 per texel (the reference's ARGBFloat), row-major: texel (x, y) of a W x H table is element
+ * y * W + x.  All arithmetic is fp32, one rounding per operation in the order written (no fused multiply-add); sqrtf
+ * and / are correctly rounded; expf, sinf, cosf, acosf, atan2f, asinf and powf are the device library's.
+ * PI = 3.14159265f (the compute shaders' own constant).  Shared by the three tables, per channel c:
+ *       RE_c = RS_c + RA_c;   ME_c = MS_c + MA_c;   OE_c = OS_c + OA_c                   (the extinction coefficients)
+ *       at the height h:  dr = expf((-h) / HR);  dm = expf((-h) / HM);  dz = fmaxf(0, 1 - (h - 25000) / 15000)
+ *       ext_c(h) = (RE_c * dr + ME_c * dm) + OE_c * dz;     sca_c(h) = (RS_c * dr + MS_c * dm) + OS_c * dz
+ *       texel (x, y) of a W x H table:  rad = (((float)x + 0.5f) / (float)W) * (Ra - Rp) + Rp,
+ *                                        mu  = -1 + (((float)y + 0.5f) / (float)H) * 2
+ *       clamp01(a) = fminf(fmaxf(a, 0), 1)
+ * LUT reads (the reference's SampleLevel through a clamped bilinear sampler, restated as fp32 bilinear; hardware
+ * filtering's fixed-point weights are not reproduced).  READ(L, u, v) of a W x H table L:
+ *       X = fminf(fmaxf(clamp01(u) * (float)W - 0.5f, 0), (float)(W - 1));  x0 = (int)X;  x1 = min(x0 + 1, W - 1);  fx = X - (float)x0
+ *       Y, y0, y1, fy alike from v and H                                     (texel centres at (i + 0.5) / W)
+ *       lo = L[y0][x0] + fx * (L[y0][x1] - L[y0][x0]);   hi = L[y1][x0] + fx * (L[y1][x1] - L[y1][x0])
+ *       READ = lo + fy * (hi - lo)                                           (x first, then y; per channel)
+ *       LUTAT(L, sr, cosA) = READ(L, (sr - Rp) / (Ra - Rp), 0.5f + 0.5f * cosA)          (SampleTransmittanceLUT)
+ *
+ * Transmittance table T (TransmittanceLUT.compute:25-51), texel (x, y), one lane per texel:
+ *       disc = fmaxf(0, (rad * rad) * (mu * mu - 1) + Ra * Ra);   step = fmaxf(0, (-rad) * mu + sqrtf(disc)) / 500
+ *       E_c = 0;  for i = 0 .. 499:   d = ((float)i + 0.5f) * step
+ *                                      sr = sqrtf((d * d + ((2 * rad) * mu) * d) + rad * rad)
+ *                                      E_c = E_c + ext_c(sr - Rp) * step
+ *       T[y][x] = (expf(-E_r), expf(-E_g), expf(-E_b), 0)
+ * The march of a downward ray runs on through the planet, as the reference's does: the densities overflow to +inf
+ * there and T = 0.
+ *
+ * Multiscatter table M (MultiscatteringLUT.compute:56-127), texel (x, y), one wave per texel, lane i of 64 taking the
+ * reference's direction i:
+ *       z = ((float)i + 0.5f) / 64;   xy = sqrtf(1 - z * z);   az = ((z * 8) * PI) * 2
+ *       dir = (sinf(az) * xy, cosf(az) * xy, z)
+ *       off = (-rad) * dir.y;   rc2 = rad * rad - off * off;   hit = rc2 < Rp * Rp and dir.y < 0
+ *       end = hit ? off - sqrtf(Rp * Rp - rc2) : sqrtf(Ra * Ra - rc2) + off;     step = end / 32
+ *       t_c = 1;  L_c = 0;  F_c = 0;  cur = step * 0.5f
+ *       for j = 0 .. 31:   p = (cur * dir.x, rad + cur * dir.y, cur * dir.z);   sr = sqrtf((p.x * p.x + p.y * p.y) + p.z * p.z)
+ *                          h = sr - Rp;   ins_c = (LUTAT(T, sr, mu)_c * sca_c(h)) * (1 / (4 * PI))
+ *                          nt_c = t_c * expf((-ext_c(h)) * step);   ti_c = (t_c - nt_c) / ext_c(h)
+ *                          L_c = L_c + ti_c * ins_c;   F_c = F_c + ti_c * sca_c(h);   cur = cur + step;   t_c = nt_c
+ *       if hit:  L_c = L_c + ((t_c * LUTAT(T, rad, mu)_c) * (GA_c / PI)) * mu
+ * The 64 lanes' L_c and F_c are summed by the fixed butterfly of ocean_body_buoyancy: for s = 32, 16, ..., 1:
+ * a_i = a_i + a_(i xor s) for every lane i; the sum is a_0 (in numpy: fold the upper half onto the lower half until
+ * one is left).  This replaces the reference's sequential sum over i, a deliberate deviation: the result depends on
+ * neither the launch grid nor the scheduling.  Then
+ *       M[y][x] = (L_r / (64 - F_r), L_g / (64 - F_g), L_b / (64 - F_b), 1)              (the reference's own divisor, :125)
+ *
+ * Sky-view table S (SkyViewLUT.compute:83-148), texel (x, y) of W x H, one lane per texel, for the unit direction
+ * towards the sun (ocean_sky_update normalises `sun` on the host: len = sqrtf((x * x + y * y) + z * z), sun / len by
+ * three divisions; the shader's own normalize is not repeated):
+ *       lon = -PI + (((float)x + 0.5f) / ((float)W - 1)) * (2 * PI);   v = 1 - ((float)y + 0.5f) / ((float)H - 1)
+ *       rad = Rp;   beta = acosf(sqrtf(rad * rad - Rp * Rp) / rad);   zha = PI - beta
+ *       a = v * 2 - 1;   a = a * a;   lat = v < 0.5f ? (1 - a) * zha : zha + a * beta
+ *       dir = (sinf(lon) * sinf(lat), cosf(lat), cosf(lon) * sinf(lat))
+ *       cs = (dir.x * sun.x + dir.y * sun.y) + dir.z * sun.z
+ *       PR = (3 / (16 * PI)) * (1 + cs * cs)
+ *       PM = ((3 / (8 * PI)) * ((1 - g * g) * (1 + cs * cs))) / ((2 + g * g) * powf(fabsf((1 + g * g) - (2 * g) * cs), 1.5f))
+ *       off = (-rad) * dir.y;   rc2 = rad * rad - off * off;   top = sqrtf(Ra * Ra - rc2);   start = fmaxf(0, off - top)
+ *       end = (rc2 < Rp * Rp and dir.y < 0) ? off - sqrtf(Rp * Rp - rc2) : top + off;     step = (end - start) / 32
+ *       t_c = 1;  L_c = 0;  cur = step * 0.5f + start
+ *       for i = 0 .. 31:   p, sr, h as above
+ *                          ins_c = LUTAT(T, sr, sun.y)_c * (dr * (RS_c * PR) + dm * (MS_c * PM))
+ *                          ins_c = ins_c + LUTAT(M, sr, sun.y)_c * sca_c(h)
+ *                          nt_c, ti_c as above;   L_c = L_c + ti_c * ins_c;   cur = cur + step;   t_c = nt_c
+ *       S[y][x] = (powf(fabsf(L_r), G), powf(fabsf(L_g), G), powf(fabsf(L_b), G), 1),   G = 1.0f / 2.2f (one fp32 division)
+ * The reference's quirks are kept: (id + 0.5) / (W - 1) puts the last column and the last row slightly past the end
+ * (row H - 1 lies past the zenith, row 0 looks straight down), the table holds pow(|L|, 1 / 2.2), and the texels
+ * whose ray ends on the planet (about the lower half of the rows) are ill-conditioned in fp32 as they are in the
+ * reference (end = off - sqrtf(Rp^2 - rc2) cancels with rc2 quantised to 4e6 m^2).  They are finite.
+ *
+ * ocean_atmosphere queues the transmittance and then the multiscatter launch on the ctx stream.  The six sizes are
+ * T's, M's and S's width and height; all six 0 selects AtmosphereController's 64 x 256, 64 x 64 and 256 x 128, otherwise
+ * each lies in [2, OCEAN_ATMOSPHERE_MAX_DIM].  The tables are allocated once per context, freed and reallocated by a
+ * call with other sizes, and freed by ocean_destroy.  The sky-view table is stale after every ocean_atmosphere.
+ * Needs no ocean_init_spectrum.
+ * ocean_sky_update queues the sky-view launch on the ctx stream, ordered with the steps and with later camera calls:
+ * the per-frame call (the reference re-runs it in every Update).
+ * ocean_atmosphere_read copies table `which` to the host buffer `out` of width * height * 16 bytes; blocking.
+ * ocean_atmosphere_lut gives table `which`'s device pointer and size; the pointer is valid until the next
+ * ocean_atmosphere with other sizes or ocean_destroy, and a reader orders itself behind the ctx stream.
+ * ocean_sun_color: the colour of the sun's light, the LC a caller puts into the camera's material.  It restates
+ * TurnTransmittanceIntoColorGradient (AtmosphereController.cs:129-154) and Update (:187-188) on the host in fp32, over
+ * a host copy of column 0 of T, fetched (blocking) by the first call after an ocean_atmosphere and kept:
+ *       for k < 8, t_k of (0.01, 0.14, 0.28, 0.36, 0.57, 0.75, 0.86, 0.99):   key_k = READ(T, 0, t_k) * 2.5f   (which is
+ *            column 0: Y = fminf(fmaxf(t_k * (float)H - 0.5f, 0), (float)(H - 1)), lo + fy * (hi - lo), then * 2.5f)
+ *       e = (sun.y / len + 1) * 0.5f                       ((dot(forward, down) + 1) * 0.5 with forward = -sun / len)
+ *       rgb = key_0 if e <= t_0;  key_7 if e >= t_7;  else, with t_k <= e < t_(k+1):
+ *             f = (e - t_k) / (t_(k+1) - t_k);   rgb_c = key_k_c + f * (key_(k+1)_c - key_k_c)
+ * The reference passes the table through an 8-bit RGBA32 texture on the way (and so clamps 2.5 T to 1); this
+ * library does not: a stated deviation.
+ *
+ * The camera sees it: ocean_camera* with mode OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT.  `bytes`, the record layout
+ * and every statement of OCEAN_CAMERA_COLOR hold, except sky() and the MISS pixel; material[26..31] are ignored (but
+ * still refused when not finite).  With pi the camera's own (float)3.14159265358979:
+ *       SKY(r):  len = sqrtf((r.x * r.x + r.y * r.y) + r.z * r.z);   n = (r.x / len, r.y / len, r.z / len)
+ *                az = atan2f(n.x, n.z);   alt = fmaxf(asinf(fminf(n.y, 1)), 0)
+ *                u = (az + pi) / (2 * pi);   v = 0.5f + 0.5f * sqrtf((alt * 2) / pi)
+ *                SKY_c = 2 * READ(S, u, v)_c                  (SampleSkyLUT, Atmosphere.shader:41-53; the 2 is :78)
+ * The clamp of the altitude is this library's: it stands where the two-colour sky has saturate(r.y) (a reflection
+ * below the horizon sees the horizon), and it keeps the lookup off the ill-conditioned rows of S.
+ *   HIT:   r = ((2 * ndv) * n.x - V.x, (2 * ndv) * n.y - V.y, (2 * ndv) * n.z - V.z);   env_c = (SKY(r)_c * pi) * ke.
+ *          The sun's disc is not reflected: the sun's lobes are the BRDF terms.
+ *   MISS:  spot = 0 if d.y <= 0, else (SunShape, :57-63, in fp32):
+ *                 q = L - d;   dist = sqrtf((q.x * q.x + q.y * q.y) + q.z * q.z);   x = clamp01(dist / SZ)
+ *                 spot = 1 - (x * x) * (3 - 2 * x)
+ *          colour_c = SKY(d)_c + (spot * spot) * LC_c        (L, LC of the material, SZ of the atmosphere's params)
+ *   SUBMERGED stays C.
+ * OCEAN_CAMERA_SKY_LUT with OCEAN_CAMERA_HITS or OCEAN_CAMERA_RANGE is OCEAN_E_INVALID_ARG; on a context whose sky-view
+ * table is absent or stale the mode is OCEAN_E_STATE, after the argument checks.
+ *
+ * OCEAN_E_INVALID_ARG, checked before any device call and before the context wherever the context is not needed to
+ * decide: a null pointer; a `params` value that is not finite; Rp <= 0 or Ra <= Rp; HR <= 0 or HM <= 0; a nonzero
+ * reserved float; a size outside [2, OCEAN_ATMOSPHERE_MAX_DIM] (unless all six are 0); a `sun` that is not finite or
+ * whose len is 0 or not finite; an unknown `which`; then a null context; then, of ocean_atmosphere_read, a wrong
+ * `bytes` (after the state tests: the sizes are the context's).  OCEAN_E_STATE: ocean_sky_update, ocean_sun_color,
+ * ocean_atmosphere_read or ocean_atmosphere_lut before ocean_atmosphere, and ocean_atmosphere_read of
+ * OCEAN_LUT_SKYVIEW while it is stale.  The three launches count as kind 2 of ocean_kernel_stats / ocean_kernel_name. */
+#define OCEAN_ATMOSPHERE_FLOATS 32
+#define OCEAN_ATMOSPHERE_MAX_DIM 1024
+#define OCEAN_LUT_TRANSMITTANCE 0
+#define OCEAN_LUT_MULTISCATTER 1
+#define OCEAN_LUT_SKYVIEW 2
+int ocean_atmosphere(ocean_ctx *ctx, const float *params, int transmittance_width, int transmittance_height,
+                     int multiscatter_width, int multiscatter_height, int skyview_width, int skyview_height);
+int ocean_sky_update(ocean_ctx *ctx, const float *sun);
+int ocean_atmosphere_read(ocean_ctx *ctx, int which, float *out, size_t bytes);
+int ocean_atmosphere_lut(ocean_ctx *ctx, int which, void **dev, size_t *width, size_t *height);
+int ocean_sun_color(ocean_ctx *ctx, const float *sun, float *rgb);
 
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
  * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async /

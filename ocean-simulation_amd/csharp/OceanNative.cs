@@ -208,6 +208,22 @@ namespace OceanHip
         public static extern OceanStatus ocean_camera_device(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, IntPtr output, UIntPtr bytes);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_camera_async(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, IntPtr dst, UIntPtr bytes, out IntPtr request);
+        // The atmosphere (added within ABI 4 in the same way; ocean.h "The atmosphere"): the three look-up tables of
+        // AtmosphereController.cs, owned by the context.  `parameters` = 32 floats (ocean.h names them); the six sizes all 0
+        // select the reference's.  ocean_sky_update is the per-frame call; CameraColor | CameraSkyLut then shades the
+        // camera's colour image with the sky-view table, and ocean_sun_color gives the light's colour for a material.
+        public const int AtmosphereFloats = 32, AtmosphereMaxDim = 1024, CameraSkyLut = 16;
+        public const int LutTransmittance = 0, LutMultiscatter = 1, LutSkyView = 2;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_atmosphere(IntPtr ctx, [In] float[] parameters, int transmittanceWidth, int transmittanceHeight, int multiscatterWidth, int multiscatterHeight, int skyviewWidth, int skyviewHeight);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_sky_update(IntPtr ctx, [In] float[] sun);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_atmosphere_read(IntPtr ctx, int which, [Out] float[] output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_atmosphere_lut(IntPtr ctx, int which, out IntPtr dev, out UIntPtr width, out UIntPtr height);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_sun_color(IntPtr ctx, [In] float[] sun, [Out] float[] rgb);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_read_async(IntPtr ctx, OceanTexture tex, int tile, int cascade, IntPtr dst, UIntPtr bytes, out IntPtr request);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

@@ -323,6 +323,41 @@ namespace OceanHip
             return output;
         }
 
+        // The atmosphere of AtmosphereController.cs (ocean.h "The atmosphere"): Awake's two tables, with `parameters` =
+        // 32 floats (null: the reference's defaults) at the reference's sizes.
+        public static readonly float[] DefaultAtmosphere = {
+            6360000f, 6420000f, 5.802e-6f, 13.558e-6f, 6.5e-5f, 0f, 0f, 0f, 8000f, 3.996e-6f, 3.996e-6f, 3.996e-6f,
+            4.4e-6f, 4.4e-6f, 4.4e-6f, 1200f, 0.85f, 0f, 0f, 0f, 0.65e-6f, 1.881e-6f, 0.085e-6f, 0f, 0f, 0f, 0.04f,
+            0f, 0f, 0f, 0f, 0f };
+        public void Atmosphere(float[] parameters = null)
+        {
+            OceanNative.Check(OceanNative.ocean_atmosphere(ctx, parameters ?? DefaultAtmosphere, 0, 0, 0, 0, 0, 0),
+                              "ocean_atmosphere");
+        }
+
+        // AtmosphereController.Update: the sky-view table for the direction towards the sun, and the light's colour
+        // (3 floats) for the camera's material.  Camera(..., OceanNative.CameraColor | OceanNative.CameraSkyLut) then
+        // reflects that sky.
+        public float[] SkyUpdate(float[] sun)
+        {
+            OceanNative.Check(OceanNative.ocean_sky_update(ctx, sun), "ocean_sky_update");
+            var rgb = new float[3];
+            OceanNative.Check(OceanNative.ocean_sun_color(ctx, sun, rgb), "ocean_sun_color");
+            return rgb;
+        }
+
+        // One of the atmosphere's tables (OceanNative.LutTransmittance, LutMultiscatter, LutSkyView): 4 floats per texel.
+        public float[] AtmosphereLut(int which, out int width, out int height)
+        {
+            IntPtr dev; UIntPtr w, h;
+            OceanNative.Check(OceanNative.ocean_atmosphere_lut(ctx, which, out dev, out w, out h), "ocean_atmosphere_lut");
+            width = (int)w; height = (int)h;
+            var output = new float[width * height * 4];
+            OceanNative.Check(OceanNative.ocean_atmosphere_read(ctx, which, output, (UIntPtr)(ulong)(output.Length * 4)),
+                              "ocean_atmosphere_read");
+            return output;
+        }
+
         // The per-cascade bounds of the displacement (ocean.h ocean_surface_bounds): 8 floats per cascade, (min x, y,
         // z, w, max x, y, z, w); their cascade sums bound the displaced mesh (culling, tessellation range).
         public float[] SurfaceBounds()

@@ -32,6 +32,7 @@ struct StateRule {
     const char* entry;  // the family's name in messages, and the stem of its entries' names
     const char* shard;  // "surface query of": ... a column-parity shard
     Needs needs = Needs::Nothing;
+    bool sky = false;  // it reads the sky-view table, which must be there and current (ocean_sky_update)
 };
 int check_state(const ocean_ctx* ctx, const StateRule& s) {
     if (s.needs == Needs::Velocity && !(ctx->flags & OCEAN_F_VELOCITY))
@@ -40,6 +41,8 @@ int check_state(const ocean_ctx* ctx, const StateRule& s) {
         return fail(OCEAN_E_UNSUPPORTED, std::string(s.entry) + " needs the TURB texture (not OCEAN_F_DISPLACEMENT_ONLY)");
     if (!ctx->spectrum_ready) return fail(OCEAN_E_STATE, std::string("ocean_init_spectrum must precede ") + s.entry);
     if (ctx->col_par >= 0) return fail(OCEAN_E_UNSUPPORTED, std::string(s.shard) + " a column-parity shard (half the columns)");
+    if (s.sky && !(ctx->atm.ready && ctx->atm.sky_valid))
+        return fail(OCEAN_E_STATE, std::string(s.entry) + " with OCEAN_CAMERA_SKY_LUT needs ocean_atmosphere and an ocean_sky_update after it");
     return OCEAN_OK;
 }
 
@@ -456,12 +459,16 @@ struct Camera {
     float* out;
     size_t bytes;
 
+    static constexpr int kSkyMode = OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT;
     static size_t pixel_bytes(int mode) { return mode == OCEAN_CAMERA_HITS ? 32 : mode == OCEAN_CAMERA_RANGE ? 4 : 16; }
     int check(Form form) const {
         if (!camera || !out) return fail(OCEAN_E_INVALID_ARG, "null camera or output");
-        if (mode != OCEAN_CAMERA_HITS && mode != OCEAN_CAMERA_RANGE && mode != OCEAN_CAMERA_COLOR)
+        if (mode == (OCEAN_CAMERA_HITS | OCEAN_CAMERA_SKY_LUT) || mode == (OCEAN_CAMERA_RANGE | OCEAN_CAMERA_SKY_LUT))
+            return fail(OCEAN_E_INVALID_ARG, "camera mode: OCEAN_CAMERA_SKY_LUT combines with OCEAN_CAMERA_COLOR only");
+        if (mode != OCEAN_CAMERA_HITS && mode != OCEAN_CAMERA_RANGE && mode != OCEAN_CAMERA_COLOR && mode != kSkyMode)
             return fail(OCEAN_E_INVALID_ARG, "unknown camera mode");
-        if (mode == OCEAN_CAMERA_COLOR && !material) return fail(OCEAN_E_INVALID_ARG, "OCEAN_CAMERA_COLOR needs a material");
+        if ((mode == OCEAN_CAMERA_COLOR || mode == kSkyMode) && !material)
+            return fail(OCEAN_E_INVALID_ARG, "OCEAN_CAMERA_COLOR needs a material");
         if (int r = check_iterations(iterations)) return r;
         if (steps < 1 || steps > OCEAN_RAY_MAX_STEPS)
             return fail(OCEAN_E_INVALID_ARG, "steps = " + std::to_string(steps) + " outside [1, OCEAN_RAY_MAX_STEPS]");
@@ -491,7 +498,7 @@ struct Camera {
                                                  std::to_string(stage_slot_bytes(ctx)) + " B");
         return OCEAN_OK;
     }
-    StateRule state() const { return {"ocean_camera", "camera view of"}; }
+    StateRule state() const { return {"ocean_camera", "camera view of", Needs::Nothing, mode == kSkyMode}; }
     StagedInputs inputs() const { return {nullptr, 0, {}}; }
     size_t out_bytes() const { return bytes; }
     const char* lacks() const { return nullptr; }
@@ -506,6 +513,10 @@ struct Camera {
         const ocean::DevView v = ctx->view();
         return timed(ctx, 2,
                      [&] {
+                         if (mode == kSkyMode)
+                             return ocean::launch_camera_sky(v, tile, iterations, steps, refine, bounds, cam, mat,
+                                                             ctx->atm.view(OCEAN_LUT_SKYVIEW), ctx->atm.params.p[26], width,
+                                                             height, ctx->opt.camera_tile != 0, d_out, ctx->stream);
                          return ocean::launch_camera(v, tile, mode, iterations, steps, refine, bounds, cam, mat, width, height,
                                                      ctx->opt.camera_tile != 0, d_out, ctx->stream);
                      },

@@ -1,7 +1,7 @@
 // What the translation units of the C-ABI layer share (abi_context.cpp, abi_frame.cpp, abi_readback.cpp,
 // abi_consumers.cpp): the error slot, the context, the device rule of every entry, the launch wrapper of
 // kernel timing and the staging of the point consumers.  Not part of the ABI, and except for the context
-// itself not visible outside the library.
+// itself not visible outside the library.  abi_atmosphere.cpp (the atmosphere's tables) is written over the same.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -189,6 +189,20 @@ struct ocean_ctx {
     // the staging block of the blocking host forms (run_staged_impl): inputs, then the output; grown on demand
     void* stage_block = nullptr;
     size_t stage_block_bytes = 0;
+    // the atmosphere (abi_atmosphere.cpp): the three tables in one allocation (`block`: transmittance, multiscatter,
+    // sky view, in this order), allocated by ocean_atmosphere and again when its dims change; the params they were
+    // made with; sky_valid: the sky view matches them (ocean_sky_update since the last ocean_atmosphere); column: the
+    // host copy of column 0 of the transmittance table, float4[h[0]], fetched by the first ocean_sun_color after an
+    // ocean_atmosphere
+    struct Atmosphere {
+        float4* block = nullptr;
+        float4* lut[3] = {nullptr, nullptr, nullptr};
+        int w[3] = {0, 0, 0}, h[3] = {0, 0, 0};
+        ocean::AtmosphereParams params{};
+        bool ready = false, sky_valid = false, column_valid = false;
+        std::vector<float> column;
+        ocean::LutView view(int k) const { return {lut[k], w[k], h[k]}; }
+    } atm;
     float4* deriv_mips = nullptr;  // OCEAN_F_MIPS chains (levels 1..log2 N per slice)
     float4* turb_mips = nullptr;
     size_t mip_chain = 0;

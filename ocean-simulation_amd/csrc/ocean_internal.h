@@ -222,6 +222,26 @@ hipError_t launch_camera(const DevView& v, int tile, int mode, int iterations, i
                          const CameraRays& cam, const CameraMaterial& mt, int width, int height, bool tiled, float* out,
                          hipStream_t s);
 
+// atmosphere.hip: the atmosphere's look-up tables (ocean_atmosphere, ocean_sky_update), device pointers, float4 per
+// texel, row-major [h][w].  The entry's 32 `params` floats travel as a kernel argument; `sun` is the unit direction
+// towards the sun (host array of three).  Every width and height lies in [2, OCEAN_ATMOSPHERE_MAX_DIM].
+struct AtmosphereParams {
+    float p[OCEAN_ATMOSPHERE_FLOATS];
+};
+struct LutView {
+    const float4* texels;
+    int w, h;
+};
+hipError_t launch_transmittance(const AtmosphereParams& a, int w, int h, float4* lut, hipStream_t s);
+hipError_t launch_multiscatter(const AtmosphereParams& a, const LutView& tr, int w, int h, float4* lut, hipStream_t s);
+hipError_t launch_skyview(const AtmosphereParams& a, const LutView& tr, const LutView& ms, const float* sun, int w, int h,
+                          float4* lut, hipStream_t s);
+// view.hip: launch_camera's colour image with the sky of OCEAN_CAMERA_SKY_LUT: `sky` is the sky-view table and
+// sun_size the atmosphere's params[26].  Its own kernel: the three kernels of launch_camera keep their arguments.
+hipError_t launch_camera_sky(const DevView& v, int tile, int iterations, int steps, int refine, const float* bounds,
+                             const CameraRays& cam, const CameraMaterial& mt, const LutView& sky, float sun_size, int width,
+                             int height, bool tiled, float* out, hipStream_t s);
+
 // whitecaps.hip: whitecap emitters (ocean_whitecaps*), device pointers: out = (capacity + 1) records of 32 B, the
 // header then the selected nodes of the grid in ascending node order, 16-B aligned; vel = the context's VEL or null
 // (records carry a zero velocity); scratch: whitecap_scratch_bytes() bytes, 8-B aligned, the ballot masks of the

@@ -2,7 +2,10 @@
 // image, a G-buffer of ray records or a shaded picture.  include/ocean/ocean.h has the definition: pixel (i, j)'s
 // ray follows from the camera, meets the water where ocean_raycast says that ray does (ray_march.h: the same
 // statements), and in colour mode the fragment stage of Water.shader (:336-373) is evaluated at the point met,
-// with the header's headless substitutions (no shadow map, no opaque texture, a two-colour sky).
+// with the header's headless substitutions (no shadow map, no opaque texture, a two-colour sky).  With
+// OCEAN_CAMERA_SKY_LUT the sky is the atmosphere's sky-view table instead (sky_lut: SampleSkyLUT of Atmosphere.shader),
+// and a miss adds the sun's disc: that image is a kernel of its own (k_camera_sky), so the other three keep their
+// arguments and registers.
 //
 // One lane per pixel, no LDS.  A pixel is the ray kernel's chain of dependent L2 / Infinity-Cache round trips:
 // latency bound, hidden by occupancy.  What the image adds is coherence: neighbouring pixels' rays pass over
@@ -14,6 +17,7 @@
 // The mode is a template argument: the range image needs no sample at the point met and the G-buffer none of
 // the shading, so each kernel carries only its own registers.  Camera and material are kernel arguments
 // (14 + 32 floats): every lane reads them from scalar registers, and there is no staged input.
+#include "atmosphere_math.h"
 #include "ocean_internal.h"
 #include "ray_march.h"
 #include "sample_filter.h"
@@ -35,10 +39,24 @@ __device__ __forceinline__ float sky(float horizon, float zenith, float ry) {
     return horizon + saturate(ry) * (zenith - horizon);
 }
 
+// sky(r) of ocean.h with OCEAN_CAMERA_SKY_LUT: twice the sky-view table at the direction r (any length)
+__device__ __forceinline__ float3 sky_lut(const LutView& sk, float rx, float ry, float rz) {
+    const float len = sqrtf((rx * rx + ry * ry) + rz * rz);
+    const float nx = rx / len, ny = ry / len, nz = rz / len;
+    const float az = atan2f(nx, nz);
+    const float alt = fmaxf(asinf(fminf(ny, 1.0f)), 0.0f);  // below the horizon: the horizon
+    const float u = (az + kPi) / (2.0f * kPi);
+    const float v = 0.5f + 0.5f * sqrtf((alt * 2.0f) / kPi);
+    const float4 t = lut_read(sk, u, lut_row(sk, v));
+    return make_float3(2.0f * t.x, 2.0f * t.y, 2.0f * t.z);
+}
+
 // The colour of a hit pixel (ocean.h, "Colour of a hit"): the ray direction d, the normal n, the wave height and
 // the foam at the point met.  has_foam: the context has DERIV and TURB (not DISPLACEMENT_ONLY).
+// SKY: the sky is sky_lut over `sk`, else the two-colour sky of the material.
+template <bool SKY>
 __device__ __forceinline__ float3 shade_hit(const CameraMaterial& mt, float dx, float dy, float dz, float nx, float ny,
-                                            float nz, float height, float foam, bool has_foam) {
+                                            float nz, float height, float foam, bool has_foam, const LutView& sk) {
     const float* m = mt.m;
     const float r0 = m[3], rough = m[6];
     const float lx = m[20], ly = m[21], lz = m[22];
@@ -59,6 +77,11 @@ __device__ __forceinline__ float3 shade_hit(const CameraMaterial& mt, float dx, 
     const float coeff = fmaxf(0.0f, height) * ((sl * sl) * (sl * sl));
     // the sky at -reflect(V, n) = 2 dot(n, V) n - V: only its y is needed
     const float ry = (2.0f * ndv) * ny - vy;
+    float env_sky[3] = {0.0f, 0.0f, 0.0f};
+    if (SKY) {  // all of -reflect(V, n)
+        const float3 e = sky_lut(sk, (2.0f * ndv) * nx - vx, ry, (2.0f * ndv) * nz - vz);
+        env_sky[0] = e.x, env_sky[1] = e.y, env_sky[2] = e.z;
+    }
     // the sun's two lobes: zero for a light at or below the horizon
     const bool sun_up = ly > 0.0f;
     float as = 0.0f, dist = 0.0f, geom = 0.0f, ctden = 1.0f;
@@ -82,7 +105,7 @@ __device__ __forceinline__ float3 shade_hit(const CameraMaterial& mt, float dx, 
     for (int c = 0; c < 3; ++c) {
         const float light = m[23 + c];
         const float refr = m[c] + (coeff * m[12 + c]) * light;
-        const float env = (sky(m[26 + c], m[29 + c], ry) * kPi) * m[10];
+        const float env = ((SKY ? env_sky[c] : sky(m[26 + c], m[29 + c], ry)) * kPi) * m[10];
         const float cook = sun_up ? ((light * dist) * geom) / ctden : 0.0f;
         const float ashk = sun_up ? light * as : 0.0f;
         const float refl = env + (cook + ashk * sndv) * m[11];
@@ -95,10 +118,12 @@ __device__ __forceinline__ float3 shade_hit(const CameraMaterial& mt, float dx, 
 
 // Pixel (i, j) -> element k = j * width + i of `out`.  TILED: a workgroup is a 16 x 16 pixel tile, wave w its
 // 8 x 8 quadrant (w & 1, w >> 1), lane l the pixel (l & 7, l >> 3) of it; else 256 consecutive k per workgroup.
-template <int MODE, bool TILED>
-__global__ __launch_bounds__(256) void k_camera(DevView v, int tile, int iterations, int steps, int refine,
-                                                const float* __restrict__ bounds, CameraRays cam, CameraMaterial mt,
-                                                int width, int height, float* __restrict__ out) {
+// SKY (colour mode only): the sky and the sun's disc of OCEAN_CAMERA_SKY_LUT over `sk`.
+template <int MODE, bool TILED, bool SKY>
+__device__ __forceinline__ void camera_pixel(const DevView& v, int tile, int iterations, int steps, int refine,
+                                             const float* __restrict__ bounds, const CameraRays& cam,
+                                             const CameraMaterial& mt, int width, int height, float* __restrict__ out,
+                                             const LutView& sk, float sun_size) {
     int i, j;
     if (TILED) {
         const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
@@ -128,7 +153,18 @@ __global__ __launch_bounds__(256) void k_camera(DevView v, int tile, int iterati
     }
     if (MODE == OCEAN_CAMERA_COLOR && m.status != OCEAN_RAY_HIT) {
         float4 c;
-        if (m.status == OCEAN_RAY_MISS)
+        if (m.status == OCEAN_RAY_MISS && SKY) {
+            const float3 e = sky_lut(sk, dx, dy, dz);
+            float spot = 0.0f;  // SunShape (Atmosphere.shader:57-63)
+            if (dy > 0.0f) {
+                const float ex = mt.m[20] - dx, ey = mt.m[21] - dy, ez = mt.m[22] - dz;
+                const float dist = sqrtf((ex * ex + ey * ey) + ez * ez);
+                const float x = saturate(dist / sun_size);
+                spot = 1.0f - (x * x) * (3.0f - 2.0f * x);
+            }
+            const float s2 = spot * spot;
+            c = make_float4(e.x + s2 * mt.m[23], e.y + s2 * mt.m[24], e.z + s2 * mt.m[25], 0.0f);
+        } else if (m.status == OCEAN_RAY_MISS)
             c = make_float4(sky(mt.m[26], mt.m[29], dy), sky(mt.m[27], mt.m[30], dy), sky(mt.m[28], mt.m[31], dy), 0.0f);
         else
             c = make_float4(mt.m[0], mt.m[1], mt.m[2], 0.0f);
@@ -146,9 +182,25 @@ __global__ __launch_bounds__(256) void k_camera(DevView v, int tile, int iterati
     } else {
         const WorldSample s = sample_cascades(v, tile, p.x, p.y, t * mt.m[7]);
         const float4 n = normal_from_deriv(s.deriv.x, s.deriv.y, s.deriv.z, s.deriv.w);  // (0, 1, 0) without DERIV
-        const float3 c = shade_hit(mt, dx, dy, dz, n.x, n.y, n.z, s.disp.y, s.turb, v.deriv != nullptr);
+        const float3 c = shade_hit<SKY>(mt, dx, dy, dz, n.x, n.y, n.z, s.disp.y, s.turb, v.deriv != nullptr, sk);
         reinterpret_cast<float4*>(out)[k] = make_float4(c.x, c.y, c.z, (float)m.status);
     }
+}
+
+template <int MODE, bool TILED>
+__global__ __launch_bounds__(256) void k_camera(DevView v, int tile, int iterations, int steps, int refine,
+                                                const float* __restrict__ bounds, CameraRays cam, CameraMaterial mt,
+                                                int width, int height, float* __restrict__ out) {
+    camera_pixel<MODE, TILED, false>(v, tile, iterations, steps, refine, bounds, cam, mt, width, height, out, LutView{}, 0.0f);
+}
+
+template <bool TILED>
+__global__ __launch_bounds__(256) void k_camera_sky(DevView v, int tile, int iterations, int steps, int refine,
+                                                    const float* __restrict__ bounds, CameraRays cam, CameraMaterial mt,
+                                                    LutView sk, float sun_size, int width, int height,
+                                                    float* __restrict__ out) {
+    camera_pixel<OCEAN_CAMERA_COLOR, TILED, true>(v, tile, iterations, steps, refine, bounds, cam, mt, width, height, out, sk,
+                                                  sun_size);
 }
 
 template <int MODE>
@@ -181,6 +233,20 @@ hipError_t launch_camera(const DevView& v, int tile, int mode, int iterations, i
         default:
             return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_camera_sky(const DevView& v, int tile, int iterations, int steps, int refine, const float* bounds,
+                             const CameraRays& cam, const CameraMaterial& mt, const LutView& sky, float sun_size, int width,
+                             int height, bool tiled, float* out, hipStream_t s) {
+    if (width < 1 || height < 1 || (size_t)width * height > (size_t)OCEAN_CAMERA_MAX_PIXELS) return hipErrorInvalidValue;
+    if (!sky.texels || sky.w < 2 || sky.h < 2) return hipErrorInvalidValue;
+    if (tiled)
+        launch(k_camera_sky<true>, dim3((width + 15) / 16, (height + 15) / 16), dim3(256), 0, s, v, tile, iterations, steps,
+               refine, bounds, cam, mt, sky, sun_size, width, height, out);
+    else
+        launch(k_camera_sky<false>, dim3((unsigned)(((size_t)width * height + 255) / 256)), dim3(256), 0, s, v, tile,
+               iterations, steps, refine, bounds, cam, mt, sky, sun_size, width, height, out);
     return hipGetLastError();
 }
 

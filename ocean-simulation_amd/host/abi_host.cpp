@@ -4,7 +4,7 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|step]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|sky|step]
 //
 // With step the host plays F frames on a velocity context and, behind each, advances a fleet of six boxes of 4 x 3
 // probes by 4 substeps of 1/240 s through one WaterBody::StepBodies in its async form (surface mode, 4 steps,
@@ -16,6 +16,11 @@
 // 45 x 37 pixels (2 fixed-point steps, 32 march steps, 6 bisections): the shaded picture under a fixed material; it
 // writes camera.bin (float32 [14]), material.bin (float32 [32]) and color.bin (float32 [37][45][4]); the summary line
 // carries the number of pixels of each status; tests/test_gpu_camera_host.py checks them.
+// With sky it does the same behind the atmosphere: WaterBody::Atmosphere at the sizes 12 x 20, 3 x 5 and 20 x 12, one
+// SkyUpdate, and the camera in OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT mode under the light colour SkyUpdate returned;
+// it writes transmittance.bin, multiscatter.bin, skyview.bin (float32 [h][w][4] each), sun.bin (float32 [3]),
+// sun_color.bin (float32 [3]), camera.bin, material.bin and sky_color.bin (float32 [24][32][4]);
+// tests/test_gpu_atmosphere_host.py checks them.
 // With whitecaps the host reads nothing back per frame: it runs F steps on a velocity context, then one
 // WaterBody::Whitecaps over a 101 x 101 grid (threshold 0.1, capacity 4096, lod 0) and writes whitecaps.bin (float32
 // [4097][8]: the header, the W records, zeros); the summary line carries the header's T and W and the W records
@@ -45,6 +50,7 @@
 // buoyancy1.bin (after OnValidate + one frame), heights.bin (float32
 // [F][4]: GetWaterHeight at 4 world points after each Update), sample.bin (float32
 // [8][12], SampleWorld of 8 points) and prints one JSON summary line.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -66,13 +72,13 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|step]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|sky|step]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
     if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity" &&
-        mode != "rays" && mode != "dynamics" && mode != "whitecaps" && mode != "camera" && mode != "step") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps, camera or step\n");
+        mode != "rays" && mode != "dynamics" && mode != "whitecaps" && mode != "camera" && mode != "sky" && mode != "step") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps, camera, sky or step\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -238,6 +244,45 @@ int main(int argc, char** argv) {
             std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"width\": %d, \"height\": %d, \"miss\": %d, "
                         "\"hit\": %d, \"submerged\": %d}\n", F, n, (int)wb.cascades.size(), width, height, status[0], status[1],
                         status[2]);
+            wb.OnDisable();
+            return 0;
+        }
+        if (mode == "sky") {
+            // the camera looks towards the sun, the horizon across the image and the sun's disc inside it
+            const int width = 32, height = 24;
+            const std::vector<float> sun = {0.3f, 0.25f, 0.9f};
+            const std::vector<float> camera = {3.0f, 20.0f, -4.0f, -0.01f, 0.3f, 0.9f, 0.02f, 0.0f, 0.0f,
+                                               0.0f, -0.03f, 0.0f, 0.0f, 600.0f};
+            std::vector<float> material = {0.02f, 0.1f,  0.16f, 0.0203731f, 2.2308f, 4.72995f, 0.3f,  0.004f,
+                                           0.25f, 0.25f, 1.0f,  1.0f,       0.0f,    0.3f,     0.25f, 0.25f,
+                                           1.0f,  1.0f,  1.0f,  0.5f,       0.0f,    0.0f,     0.0f,  0.0f,
+                                           0.0f,  0.0f,  0.0f,  0.0f,       0.0f,    0.0f,     0.0f,  0.0f};
+            const float len = std::sqrt((sun[0] * sun[0] + sun[1] * sun[1]) + sun[2] * sun[2]);
+            for (int k = 0; k < 3; ++k) material[20 + k] = sun[k] / len;
+            wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
+            wb.Awake();
+            wb.Atmosphere(ocean_host::WaterBody::DefaultAtmosphere(), {12, 20, 3, 5, 20, 12});
+            for (int f = 0; f < F; ++f) wb.Update((float)f / 60.0f);
+            const std::vector<float> rgb = wb.SkyUpdate(sun);
+            for (int k = 0; k < 3; ++k) material[23 + k] = rgb[k];
+            const std::vector<float> color =
+                wb.Camera(camera, width, height, OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT, material, 2, 32, 6);
+            const char* names[3] = {"/transmittance.bin", "/multiscatter.bin", "/skyview.bin"};
+            int dims[6];
+            for (int k = 0; k < 3; ++k) {
+                const std::vector<float> lut = wb.AtmosphereLut(k, &dims[2 * k], &dims[2 * k + 1]);
+                write_bin(out + names[k], lut.data(), lut.size());
+            }
+            write_bin(out + "/sun.bin", sun.data(), sun.size());
+            write_bin(out + "/sun_color.bin", rgb.data(), rgb.size());
+            write_bin(out + "/camera.bin", camera.data(), camera.size());
+            write_bin(out + "/material.bin", material.data(), material.size());
+            write_bin(out + "/sky_color.bin", color.data(), color.size());
+            int status[3] = {0, 0, 0};
+            for (int k = 0; k < width * height; ++k) ++status[(int)color[4 * k + 3]];
+            std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"width\": %d, \"height\": %d, \"miss\": %d, "
+                        "\"hit\": %d, \"submerged\": %d, \"dims\": [%d, %d, %d, %d, %d, %d]}\n", F, n, (int)wb.cascades.size(),
+                        width, height, status[0], status[1], status[2], dims[0], dims[1], dims[2], dims[3], dims[4], dims[5]);
             wb.OnDisable();
             return 0;
         }

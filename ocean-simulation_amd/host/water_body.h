@@ -305,6 +305,45 @@ public:
         return out;
     }
 
+    // The atmosphere of AtmosphereController.cs (ocean.h "The atmosphere"): its Awake, the transmittance and the
+    // multiscatter table from the 32 floats of `params` (ocean.h names them; DefaultAtmosphere() has the reference's),
+    // at the reference's sizes when `dims` is empty, else (Tw, Th, Mw, Mh, Sw, Sh).  Needs no spectrum.
+    static std::vector<float> DefaultAtmosphere() {
+        return {6360000.0f, 6420000.0f, 5.802e-6f, 13.558e-6f, 6.5e-5f, 0.0f,  0.0f,  0.0f,      8000.0f,   3.996e-6f, 3.996e-6f,
+                3.996e-6f,  4.4e-6f,    4.4e-6f,   4.4e-6f,    1200.0f, 0.85f, 0.0f,  0.0f,      0.0f,      0.65e-6f,  1.881e-6f,
+                0.085e-6f,  0.0f,       0.0f,      0.0f,       0.04f,   0.0f,  0.0f,  0.0f,      0.0f,      0.0f};
+    }
+    void Atmosphere(const std::vector<float>& params = DefaultAtmosphere(), const std::vector<int>& dims = {}) const {
+        if (params.size() != OCEAN_ATMOSPHERE_FLOATS || (!dims.empty() && dims.size() != 6))
+            throw std::runtime_error("Atmosphere: params is 32 floats, dims six sizes or none");
+        const int zero[6] = {0, 0, 0, 0, 0, 0};
+        const int* d = dims.empty() ? zero : dims.data();
+        check(ocean_atmosphere(ctx_, params.data(), d[0], d[1], d[2], d[3], d[4], d[5]), "ocean_atmosphere");
+    }
+
+    // AtmosphereController.Update: the sky-view table for the direction towards the sun (any length), and the colour
+    // of its light, which goes into a camera material's [23..25].  Camera(..., OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT)
+    // then reflects that sky.
+    std::vector<float> SkyUpdate(const std::vector<float>& sun) const {
+        if (sun.size() != 3) throw std::runtime_error("SkyUpdate: sun is 3 floats");
+        check(ocean_sky_update(ctx_, sun.data()), "ocean_sky_update");
+        std::vector<float> rgb(3);
+        check(ocean_sun_color(ctx_, sun.data(), rgb.data()), "ocean_sun_color");
+        return rgb;
+    }
+
+    // One of the atmosphere's tables (OCEAN_LUT_*): float4 [height][width].
+    std::vector<float> AtmosphereLut(int which, int* width, int* height) const {
+        void* dev = nullptr;
+        size_t w = 0, h = 0;
+        check(ocean_atmosphere_lut(ctx_, which, &dev, &w, &h), "ocean_atmosphere_lut");
+        std::vector<float> out(w * h * 4);
+        check(ocean_atmosphere_read(ctx_, which, out.data(), out.size() * sizeof(float)), "ocean_atmosphere_read");
+        *width = (int)w;
+        *height = (int)h;
+        return out;
+    }
+
     // Where the sea is breaking (ocean.h ocean_whitecaps): the nodes (i, j) at (x0 + i dx, z0 + j dz) whose foam
     // reaches `threshold`, in ascending j * nx + i.  Returns the list as the library writes it, capacity + 1 records
     // of 8 floats: the header (eight uint32: T selected, W = min(T, capacity) written, nx * ny, capacity, 0, 0, 0, 0;

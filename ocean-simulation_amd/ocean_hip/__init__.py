@@ -75,6 +75,7 @@ EXPORTED_SYMBOLS = (
     "ocean_whitecaps", "ocean_whitecaps_device", "ocean_whitecaps_async",
     "ocean_camera", "ocean_camera_device", "ocean_camera_async",
     "ocean_body_step", "ocean_body_step_device", "ocean_body_step_async",
+    "ocean_atmosphere", "ocean_sky_update", "ocean_atmosphere_read", "ocean_atmosphere_lut", "ocean_sun_color",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -102,6 +103,13 @@ CAMERA_FLOATS = 14
 CAMERA_MATERIAL_FLOATS = 32
 CAMERA_MAX_PIXELS = 1 << 22
 CAMERA_MAX_SAMPLES = 1 << 28
+# the colour image with the atmosphere's sky: valid only as CAMERA_COLOR | CAMERA_SKY_LUT (ocean.h, "The atmosphere")
+CAMERA_SKY_LUT = 16
+# ocean_atmosphere*: the params array, the tables' ids, default sizes and the size limit (ocean.h)
+ATMOSPHERE_FLOATS = 32
+ATMOSPHERE_MAX_DIM = 1024
+LUT_TRANSMITTANCE, LUT_MULTISCATTER, LUT_SKYVIEW = 0, 1, 2
+ATMOSPHERE_DEFAULT_DIMS = (64, 256, 64, 64, 256, 128)
 # ocean_body_step* array size and limits (ocean.h); modes, laws and the body limits are the dynamics'
 BODY_STEP_FLOATS = 8
 BODY_MAX_SUBSTEPS = 64
@@ -206,6 +214,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_body_step": ([P, i, i, i, i, i, P, P, i, P, P, i, P], i),
         "ocean_body_step_device": ([P, i, i, i, i, i, P, P, i, P, P, i, P], i),
         "ocean_body_step_async": ([P, i, i, i, i, i, P, P, i, P, P, i, P, ctypes.POINTER(P)], i),
+        "ocean_atmosphere": ([P, P, i, i, i, i, i, i], i),
+        "ocean_sky_update": ([P, P], i),
+        "ocean_atmosphere_read": ([P, i, P, sz], i),
+        "ocean_atmosphere_lut": ([P, i, ctypes.POINTER(P), ctypes.POINTER(sz), ctypes.POINTER(sz)], i),
+        "ocean_sun_color": ([P, P, P], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -268,6 +281,22 @@ def material(color=(0.02, 0.1, 0.16), roughness: float = 0.3, ex: float = 0.25, 
 
 
 _material = material  # (WaterBody.Camera has a parameter of that name)
+
+
+def atmosphere_params(planet_radius: float = 6360000.0, atmosphere_radius: float = 6420000.0,
+                      rayleigh_scattering=(5.802e-6, 13.558e-6, 6.5e-5), rayleigh_absorption=(0.0, 0.0, 0.0),
+                      rayleigh_scale_height: float = 8000.0, mie_scattering=(3.996e-6, 3.996e-6, 3.996e-6),
+                      mie_absorption=(4.4e-6, 4.4e-6, 4.4e-6), mie_scale_height: float = 1200.0, g: float = 0.85,
+                      ozone_scattering=(0.0, 0.0, 0.0), ozone_absorption=(0.65e-6, 1.881e-6, 0.085e-6),
+                      ground_albedo=(0.0, 0.0, 0.0), sun_size: float = 0.04) -> np.ndarray:
+    """The float32[32] `params` of ocean_atmosphere (ocean.h names the fields): AtmosphereController's public fields
+    with its defaults, and Atmosphere.shader's _SunSize.  Rounded once; [27..31] are reserved and zero."""
+    p = np.zeros(ATMOSPHERE_FLOATS, np.float64)
+    p[0], p[1] = planet_radius, atmosphere_radius
+    p[2:5], p[5:8], p[8] = rayleigh_scattering, rayleigh_absorption, rayleigh_scale_height
+    p[9:12], p[12:15], p[15], p[16] = mie_scattering, mie_absorption, mie_scale_height, g
+    p[17:20], p[20:23], p[23:26], p[26] = ozone_scattering, ozone_absorption, ground_albedo, sun_size
+    return p.astype(np.float32)
 
 
 def step_params(h: float, g: float = 9.81, buoyancy: Optional[float] = None, drag: float = 0.0, drag_torque: float = 0.0,
@@ -500,6 +529,52 @@ class OceanContext:
         _check(self.lib.ocean_raycast_device(self._h, tile, iterations, steps, refine, vp(rays_ptr), count,
                                              vp(out_ptr)), "ocean_raycast_device")
 
+    # -- the atmosphere (ocean.h, "The atmosphere") ---------------------------------
+    def atmosphere(self, params=None, dims=None) -> None:
+        """The transmittance and the multiscatter table (ocean_atmosphere), queued on the context's stream: `params`
+        float32[32] (atmosphere_params(), its defaults when None), `dims` the six sizes (Tw, Th, Mw, Mh, Sw, Sh),
+        AtmosphereController's when None.  The sky-view table is stale until the next sky_update."""
+        p = np.ascontiguousarray(atmosphere_params() if params is None else params, np.float32).reshape(-1)
+        if p.shape[0] != ATMOSPHERE_FLOATS:
+            raise ValueError(f"params must be float32[{ATMOSPHERE_FLOATS}] (atmosphere_params()), got {p.shape}")
+        d = [0] * 6 if dims is None else [int(v) for v in dims]
+        if len(d) != 6:
+            raise ValueError("dims must be the six sizes (Tw, Th, Mw, Mh, Sw, Sh)")
+        _check(self.lib.ocean_atmosphere(self._h, p.ctypes.data, *d), "ocean_atmosphere")
+
+    def sky_update(self, sun) -> None:
+        """The sky-view table for the direction towards the sun, any length > 0 (ocean_sky_update): the per-frame
+        call, queued on the context's stream before later camera calls."""
+        s = np.ascontiguousarray(sun, np.float32).reshape(-1)
+        if s.shape[0] != 3:
+            raise ValueError("sun must be three floats")
+        _check(self.lib.ocean_sky_update(self._h, s.ctypes.data), "ocean_sky_update")
+
+    def atmosphere_lut_ptr(self, which: int):
+        """(device pointer, width, height) of table `which` (ocean_atmosphere_lut)."""
+        dev, w, h = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_size_t()
+        _check(self.lib.ocean_atmosphere_lut(self._h, which, ctypes.byref(dev), ctypes.byref(w), ctypes.byref(h)),
+               "ocean_atmosphere_lut")
+        return dev.value, int(w.value), int(h.value)
+
+    def atmosphere_lut(self, which: int) -> np.ndarray:
+        """Table `which` (LUT_TRANSMITTANCE, LUT_MULTISCATTER, LUT_SKYVIEW) as float32[height][width][4]; blocking
+        (ocean_atmosphere_read)."""
+        _, w, h = self.atmosphere_lut_ptr(which)
+        out = np.empty((h, w, 4), np.float32)
+        _check(self.lib.ocean_atmosphere_read(self._h, which, out.ctypes.data, out.nbytes), "ocean_atmosphere_read")
+        return out
+
+    def sun_color(self, sun) -> np.ndarray:
+        """The colour of the sun's light for the direction towards the sun, float32[3]: the reference's
+        colorBySunElevation gradient over the transmittance table (ocean_sun_color); a material's light_color."""
+        s = np.ascontiguousarray(sun, np.float32).reshape(-1)
+        if s.shape[0] != 3:
+            raise ValueError("sun must be three floats")
+        rgb = np.empty(3, np.float32)
+        _check(self.lib.ocean_sun_color(self._h, s.ctypes.data, rgb.ctypes.data), "ocean_sun_color")
+        return rgb
+
     @staticmethod
     def _camera_args(camera, material, mode: int, width: int, height: int):
         """(camera float32[14], material float32[32] or None, result shape, bytes)."""
@@ -514,7 +589,8 @@ class OceanContext:
         w, h = max(int(width), 0), max(int(height), 0)
         if w * h > CAMERA_MAX_PIXELS:  # refused by the library as well; no host buffer of that size first
             w = h = 0
-        shape = {CAMERA_HITS: (h, w, 8), CAMERA_RANGE: (h, w), CAMERA_COLOR: (h, w, 4)}.get(mode, (0,))
+        shape = {CAMERA_HITS: (h, w, 8), CAMERA_RANGE: (h, w), CAMERA_COLOR: (h, w, 4),
+                 CAMERA_COLOR | CAMERA_SKY_LUT: (h, w, 4)}.get(mode, (0,))
         return cam, mat, shape, int(np.prod(shape, dtype=np.int64)) * 4
 
     def camera(self, camera, width: int, height: int, mode: int = CAMERA_COLOR, material=None, tile: int = 0,
