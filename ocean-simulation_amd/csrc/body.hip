@@ -37,9 +37,16 @@
 // buoyancy record bit for bit).
 //
 // ocean_body_step* (k_body_step<W>) puts the integrator of ocean.h behind those sums and a loop of S substeps
-// around both: the probe loop and the butterfly are one device function (body_wrench<W>) that both kernels call,
-// after it every lane of a body's segment holds all fourteen sums and advances the body's state in its own
-// registers, and lane 0 stores eight float4 (128 B per body: the state, then the last substep's record).
+// around both: after the butterfly every lane of a body's segment holds all fourteen sums and advances the body's
+// state in its own registers, and lane 0 stores eight float4 (128 B per body: the state, then the last substep's
+// record).
+//
+// The probe loop and the butterfly are one device function, body_wrench<W, DRAG>, that all three kernels call:
+// k_body_buoyancy<W> with DRAG = false, which compiles the VEL taps, the drag terms, their accumulators and their
+// shuffles out, the other two with DRAG = true.  The three launchers share one map from P to a compile-time W
+// (with_segment_width) and one grid size (body_groups).
+#include <type_traits>
+
 #include "ocean_internal.h"
 #include "sample_filter.h"
 #include "spectrum_math.h"
@@ -62,6 +69,34 @@ __device__ __forceinline__ Pose load_pose(const float* B, bool live) {
     return q;
 }
 
+// A body's motion, float[6] = (v, omega) at Mo; a lane without a body is at rest and loads nothing.
+struct Motion {
+    float vx, vy, vz, ox, oy, oz;
+};
+
+__device__ __forceinline__ Motion load_motion(const float* Mo, bool live) {
+    Motion mo = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (live) {
+        mo.vx = Mo[0], mo.vy = Mo[1], mo.vz = Mo[2];
+        mo.ox = Mo[3], mo.oy = Mo[4], mo.oz = Mo[5];
+    }
+    return mo;
+}
+
+// a rotated by the quaternion (u, w): t = 2 (u x a), (a + w t) + (u x t).
+struct Vec3 {
+    float x, y, z;
+};
+
+__device__ __forceinline__ Vec3 rotate(float ux, float uy, float uz, float w, float ax, float ay, float az) {
+    const float tx = 2.0f * (uy * az - uz * ay), ty = 2.0f * (uz * ax - ux * az), tz = 2.0f * (ux * ay - uy * ax);
+    Vec3 r;
+    r.x = (ax + w * tx) + (uy * tz - uz * ty);
+    r.y = (ay + w * ty) + (uz * tx - ux * tz);
+    r.z = (az + w * tz) + (ux * ty - uy * tx);
+    return r;
+}
+
 // Probe j of a body: d (scaled, rotated), w = c + d, and the scaled cell h', v'.
 struct Placed {
     float dx, dy, dz, wx, wy, wz, hs, vs;
@@ -69,12 +104,9 @@ struct Placed {
 
 __device__ __forceinline__ Placed place_probe(const Pose& q, const float* __restrict__ H) {
     const float rx = H[0], ry = H[1], rz = H[2], h = H[3], vol = H[4];
-    const float ax = q.sx * rx, ay = q.sy * ry, az = q.sz * rz;
-    const float tx = 2.0f * (q.uy * az - q.uz * ay), ty = 2.0f * (q.uz * ax - q.ux * az), tz = 2.0f * (q.ux * ay - q.uy * ax);
+    const Vec3 d = rotate(q.ux, q.uy, q.uz, q.qw, q.sx * rx, q.sy * ry, q.sz * rz);
     Placed p;
-    p.dx = (ax + q.qw * tx) + (q.uy * tz - q.uz * ty);
-    p.dy = (ay + q.qw * ty) + (q.uz * tx - q.ux * tz);
-    p.dz = (az + q.qw * tz) + (q.ux * ty - q.uy * tx);
+    p.dx = d.x, p.dy = d.y, p.dz = d.z;
     p.wx = q.cx + p.dx, p.wy = q.cy + p.dy, p.wz = q.cz + p.dz;
     p.hs = h * q.sy, p.vs = ((vol * q.sx) * q.sy) * q.sz;
     return p;
@@ -94,6 +126,110 @@ __device__ __forceinline__ Wet submerge(const Placed& p, float eta) {
     return w;
 }
 
+// The fourteen sums and two maxima of ocean_body_dynamics, in the record's order: t0..t6 and rmax are the buoyancy
+// record, then sum F, sum T, the largest relative speed on the wet hull and the number of wet probes.
+struct Wrench {
+    float t0, t1, t2, t3, t4, t5, t6, rmax, f0, f1, f2, q0, q1, q2, mmax, wet;
+};
+
+// A dynamics record: the Wrench as four float4 at o.
+__device__ __forceinline__ void store_wrench(float4* o, const Wrench& r) {
+    o[0] = make_float4(r.t0, r.t1, r.t2, r.t3);
+    o[1] = make_float4(r.t4, r.t5, r.t6, r.rmax);
+    o[2] = make_float4(r.f0, r.f1, r.f2, r.q0);
+    o[3] = make_float4(r.q1, r.q2, r.mmax, r.wet);
+}
+
+// The probe loop and the butterfly of all three kernels for the body whose segment lane l belongs to, at the pose
+// and motion given.  Every lane of every wave calls it (the __shfl_xor are executed by all), and every lane of a
+// segment returns the body's sums.  DRAG = false (ocean_body_buoyancy*) reads neither vel, law nor the motion and
+// leaves the second half of the Wrench at +0: no VEL tap, no drag term, no accumulator and no shuffle for them.
+template <int W, bool DRAG>
+__device__ __forceinline__ Wrench body_wrench(const DevView& v, const float4* __restrict__ vel, int tile, int mode,
+                                              int iterations, int law, const float* __restrict__ hull, int probes,
+                                              const Pose& pose, const Motion& mo, int l, bool live) {
+    [[maybe_unused]] const float vx = mo.vx, vy = mo.vy, vz = mo.vz, ox = mo.ox, oy = mo.oy, oz = mo.oz;
+    float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f, t3 = 0.0f, t4 = 0.0f, t5 = 0.0f, t6 = 0.0f, rmax = 0.0f;
+    [[maybe_unused]] float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f, q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, wet = 0.0f, mmax = 0.0f;
+    const int trips = (probes + W - 1) / W;  // the same for every lane of the launch
+    for (int it = 0; it < trips; ++it) {
+        const int j = it * W + l;
+        if (live && j < probes) {
+            const Placed pr = place_probe(pose, hull + 5 * (size_t)j);
+            float eta, r = 0.0f, nx = 0.0f, ny = 1.0f, nz = 0.0f;
+            [[maybe_unused]] float4 vs;
+            if (mode != OCEAN_QUERY_REFERENCE) {  // the surface branch first (docs/MEASUREMENTS.md section 15)
+                const float2 p = surface_fixed_point(v, tile, pr.wx, pr.wz, iterations);
+                WorldSample s;
+                if constexpr (DRAG)
+                    sample_cascades_vel(v, vel, tile, p.x, p.y, s, vs);
+                else
+                    s = sample_cascades(v, tile, p.x, p.y, 0.0f);
+                const SurfaceRecord rec = surface_record(s, p, pr.wx, pr.wz);
+                eta = rec.at.x, r = rec.at.w, nx = rec.nf.x, ny = rec.nf.y, nz = rec.nf.z;
+            } else {
+                const int px = reference_texel(pr.wx, v.n), py = reference_texel(pr.wz, v.n);
+                const size_t at = (size_t)tile * v.C * v.n * v.n + (size_t)py * v.n + px;  // cascade 0 of the tile
+                eta = v.disp[at].y;
+                if constexpr (DRAG) vs = vel[at];
+            }
+            const Wet w = submerge(pr, eta);
+            [[maybe_unused]] float m, Fx, Fy, Fz;  // the drag terms are formed before the sums, as the statement order
+            if constexpr (DRAG) {                  // decides the dynamics kernels' machine code (MEASUREMENTS section 27)
+                const float ex = pr.dx, ey = w.ey, ez = pr.dz;
+                const float bx = vx + (oy * ez - oz * ey), by = vy + (oz * ex - ox * ez), bz = vz + (ox * ey - oy * ex);
+                const float ux = vs.x - bx, uy = vs.y - by, uz = vs.z - bz;
+                m = sqrtf((ux * ux + uy * uy) + uz * uz);
+                const float sc = law == OCEAN_DRAG_QUADRATIC ? w.g * m : w.g;
+                Fx = sc * ux, Fy = sc * uy, Fz = sc * uz;
+            }
+            t0 = t0 + w.g;
+            t1 = t1 + w.g * pr.dx;
+            t2 = t2 + w.g * w.ey;
+            t3 = t3 + w.g * pr.dz;
+            t4 = t4 + w.g * nx;
+            t5 = t5 + w.g * ny;
+            t6 = t6 + w.g * nz;
+            rmax = fmaxf(rmax, r);
+            if constexpr (DRAG) {
+                const float ex = pr.dx, ey = w.ey, ez = pr.dz;
+                f0 = f0 + Fx;
+                f1 = f1 + Fy;
+                f2 = f2 + Fz;
+                q0 = q0 + (ey * Fz - ez * Fy);
+                q1 = q1 + (ez * Fx - ex * Fz);
+                q2 = q2 + (ex * Fy - ey * Fx);
+                if (w.f > 0.0f) {
+                    wet = wet + 1.0f;
+                    mmax = fmaxf(mmax, m);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = W / 2; s > 0; s >>= 1) {  // every lane of the wave takes part; l xor s stays in the segment
+        t0 = t0 + __shfl_xor(t0, s);
+        t1 = t1 + __shfl_xor(t1, s);
+        t2 = t2 + __shfl_xor(t2, s);
+        t3 = t3 + __shfl_xor(t3, s);
+        t4 = t4 + __shfl_xor(t4, s);
+        t5 = t5 + __shfl_xor(t5, s);
+        t6 = t6 + __shfl_xor(t6, s);
+        rmax = fmaxf(rmax, __shfl_xor(rmax, s));
+        if constexpr (DRAG) {
+            f0 = f0 + __shfl_xor(f0, s);
+            f1 = f1 + __shfl_xor(f1, s);
+            f2 = f2 + __shfl_xor(f2, s);
+            q0 = q0 + __shfl_xor(q0, s);
+            q1 = q1 + __shfl_xor(q1, s);
+            q2 = q2 + __shfl_xor(q2, s);
+            mmax = fmaxf(mmax, __shfl_xor(mmax, s));
+            wet = wet + __shfl_xor(wet, s);
+        }
+    }
+    return {t0, t1, t2, t3, t4, t5, t6, rmax, f0, f1, f2, q0, q1, q2, mmax, wet};
+}
+
 // hull float[P][5] = (rx, ry, rz, h, v); bodies float[M][10] = (c, q, s); out[2 b], out[2 b + 1] = record b.
 template <int W>
 __global__ __launch_bounds__(256) void k_body_buoyancy(DevView v, int tile, int mode, int iterations,
@@ -105,155 +241,11 @@ __global__ __launch_bounds__(256) void k_body_buoyancy(DevView v, int tile, int 
     const size_t b = (size_t)blockIdx.x * kBodies + threadIdx.x / W;
     const bool live = b < (size_t)count;
     const Pose pose = load_pose(bodies + 10 * b, live);
-    float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f, t3 = 0.0f, t4 = 0.0f, t5 = 0.0f, t6 = 0.0f, rmax = 0.0f;
-    const int trips = (probes + W - 1) / W;  // the same for every lane of the launch
-    for (int it = 0; it < trips; ++it) {
-        const int j = it * W + l;
-        if (live && j < probes) {
-            const Placed pr = place_probe(pose, hull + 5 * (size_t)j);
-            float eta, r = 0.0f, nx = 0.0f, ny = 1.0f, nz = 0.0f;
-            if (mode != OCEAN_QUERY_REFERENCE) {
-                const float2 p = surface_fixed_point(v, tile, pr.wx, pr.wz, iterations);
-                const SurfaceRecord rec = surface_record(sample_cascades(v, tile, p.x, p.y, 0.0f), p, pr.wx, pr.wz);
-                eta = rec.at.x, r = rec.at.w, nx = rec.nf.x, ny = rec.nf.y, nz = rec.nf.z;
-            } else {
-                const int px = reference_texel(pr.wx, v.n), py = reference_texel(pr.wz, v.n);
-                eta = (v.disp + (size_t)tile * v.C * v.n * v.n)[(size_t)py * v.n + px].y;  // cascade 0 of the tile
-            }
-            const Wet w = submerge(pr, eta);
-            t0 = t0 + w.g;
-            t1 = t1 + w.g * pr.dx;
-            t2 = t2 + w.g * w.ey;
-            t3 = t3 + w.g * pr.dz;
-            t4 = t4 + w.g * nx;
-            t5 = t5 + w.g * ny;
-            t6 = t6 + w.g * nz;
-            rmax = fmaxf(rmax, r);
-        }
-    }
-#pragma unroll
-    for (int s = W / 2; s > 0; s >>= 1) {  // every lane of the wave takes part; l xor s stays in the segment
-        t0 = t0 + __shfl_xor(t0, s);
-        t1 = t1 + __shfl_xor(t1, s);
-        t2 = t2 + __shfl_xor(t2, s);
-        t3 = t3 + __shfl_xor(t3, s);
-        t4 = t4 + __shfl_xor(t4, s);
-        t5 = t5 + __shfl_xor(t5, s);
-        t6 = t6 + __shfl_xor(t6, s);
-        rmax = fmaxf(rmax, __shfl_xor(rmax, s));
-    }
+    const Wrench r = body_wrench<W, false>(v, nullptr, tile, mode, iterations, 0, hull, probes, pose, Motion{}, l, live);
     if (live && l == 0) {
-        out[2 * b] = make_float4(t0, t1, t2, t3);
-        out[2 * b + 1] = make_float4(t4, t5, t6, rmax);
+        out[2 * b] = make_float4(r.t0, r.t1, r.t2, r.t3);
+        out[2 * b + 1] = make_float4(r.t4, r.t5, r.t6, r.rmax);
     }
-}
-
-// The full sample at the fixed point's end p with the VEL taps beside it: per cascade one Bil serves the DISP,
-// DERIV and VEL texels.  disp and deriv are sample_cascades(v, tile, x, z, 0)'s bit for bit (lod 0 is level 0
-// with and without mip chains), vs is k_query_velocity's Vs(p); TURB, which no body term reads, is not tapped.
-__device__ __forceinline__ void sample_cascades_vel(const DevView& v, const float4* __restrict__ vel, int tile, float x,
-                                                    float z, WorldSample& s, float4& vs) {
-    s.disp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    s.deriv = s.disp;
-    s.turb = 0.0f;
-    vs = s.disp;
-    for (int c = 0; c < v.C; ++c) {
-        const float L = v.casc[c * 5];
-        const size_t slice = (size_t)(tile * v.C + c) * v.n * v.n;
-        const Bil b = bil(x / L, z / L, v.n);
-        s.disp = add4(s.disp, tap(v.disp + slice, v.n, b));
-        if (v.deriv) s.deriv = add4(s.deriv, tap(v.deriv + slice, v.n, b));
-        vs = add4(vs, tap(vel + slice, v.n, b));
-    }
-}
-
-// Body b's motion, float[6] = (v, omega); a lane without a body is at rest.
-struct Motion {
-    float vx, vy, vz, ox, oy, oz;
-};
-
-// The fourteen sums and two maxima of ocean_body_dynamics, in the record's order: t0..t6 and rmax are the buoyancy
-// record, then sum F, sum T, the largest relative speed on the wet hull and the number of wet probes.
-struct Wrench {
-    float t0, t1, t2, t3, t4, t5, t6, rmax, f0, f1, f2, q0, q1, q2, mmax, wet;
-};
-
-// The probe loop and the butterfly of ocean_body_dynamics* for the body whose segment lane l belongs to, at the pose
-// and motion given: the same mapping, trip count and butterfly as k_body_buoyancy<W>.  Every lane of every wave
-// calls it (the __shfl_xor are executed by all), and every lane of a segment returns the body's sums.
-template <int W>
-__device__ __forceinline__ Wrench body_wrench(const DevView& v, const float4* __restrict__ vel, int tile, int mode,
-                                              int iterations, int law, const float* __restrict__ hull, int probes,
-                                              const Pose& pose, const Motion& mo, int l, bool live) {
-    const float vx = mo.vx, vy = mo.vy, vz = mo.vz, ox = mo.ox, oy = mo.oy, oz = mo.oz;
-    float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f, t3 = 0.0f, t4 = 0.0f, t5 = 0.0f, t6 = 0.0f, rmax = 0.0f;
-    float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f, q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, wet = 0.0f, mmax = 0.0f;
-    const int trips = (probes + W - 1) / W;  // the same for every lane of the launch
-    for (int it = 0; it < trips; ++it) {
-        const int j = it * W + l;
-        if (live && j < probes) {
-            const Placed pr = place_probe(pose, hull + 5 * (size_t)j);
-            float eta, r = 0.0f, nx = 0.0f, ny = 1.0f, nz = 0.0f;
-            float4 vs;
-            if (mode != OCEAN_QUERY_REFERENCE) {
-                const float2 p = surface_fixed_point(v, tile, pr.wx, pr.wz, iterations);
-                WorldSample s;
-                sample_cascades_vel(v, vel, tile, p.x, p.y, s, vs);
-                const SurfaceRecord rec = surface_record(s, p, pr.wx, pr.wz);
-                eta = rec.at.x, r = rec.at.w, nx = rec.nf.x, ny = rec.nf.y, nz = rec.nf.z;
-            } else {
-                const int px = reference_texel(pr.wx, v.n), py = reference_texel(pr.wz, v.n);
-                const size_t at = (size_t)tile * v.C * v.n * v.n + (size_t)py * v.n + px;  // cascade 0 of the tile
-                eta = v.disp[at].y;
-                vs = vel[at];
-            }
-            const Wet w = submerge(pr, eta);
-            const float ex = pr.dx, ey = w.ey, ez = pr.dz;
-            const float bx = vx + (oy * ez - oz * ey), by = vy + (oz * ex - ox * ez), bz = vz + (ox * ey - oy * ex);
-            const float ux = vs.x - bx, uy = vs.y - by, uz = vs.z - bz;
-            const float m = sqrtf((ux * ux + uy * uy) + uz * uz);
-            const float sc = law == OCEAN_DRAG_QUADRATIC ? w.g * m : w.g;
-            const float Fx = sc * ux, Fy = sc * uy, Fz = sc * uz;
-            t0 = t0 + w.g;
-            t1 = t1 + w.g * pr.dx;
-            t2 = t2 + w.g * w.ey;
-            t3 = t3 + w.g * pr.dz;
-            t4 = t4 + w.g * nx;
-            t5 = t5 + w.g * ny;
-            t6 = t6 + w.g * nz;
-            rmax = fmaxf(rmax, r);
-            f0 = f0 + Fx;
-            f1 = f1 + Fy;
-            f2 = f2 + Fz;
-            q0 = q0 + (ey * Fz - ez * Fy);
-            q1 = q1 + (ez * Fx - ex * Fz);
-            q2 = q2 + (ex * Fy - ey * Fx);
-            if (w.f > 0.0f) {
-                wet = wet + 1.0f;
-                mmax = fmaxf(mmax, m);
-            }
-        }
-    }
-#pragma unroll
-    for (int s = W / 2; s > 0; s >>= 1) {  // every lane of the wave takes part; l xor s stays in the segment
-        t0 = t0 + __shfl_xor(t0, s);
-        t1 = t1 + __shfl_xor(t1, s);
-        t2 = t2 + __shfl_xor(t2, s);
-        t3 = t3 + __shfl_xor(t3, s);
-        t4 = t4 + __shfl_xor(t4, s);
-        t5 = t5 + __shfl_xor(t5, s);
-        t6 = t6 + __shfl_xor(t6, s);
-        rmax = fmaxf(rmax, __shfl_xor(rmax, s));
-        f0 = f0 + __shfl_xor(f0, s);
-        f1 = f1 + __shfl_xor(f1, s);
-        f2 = f2 + __shfl_xor(f2, s);
-        q0 = q0 + __shfl_xor(q0, s);
-        q1 = q1 + __shfl_xor(q1, s);
-        q2 = q2 + __shfl_xor(q2, s);
-        mmax = fmaxf(mmax, __shfl_xor(mmax, s));
-        wet = wet + __shfl_xor(wet, s);
-    }
-    return {t0, t1, t2, t3, t4, t5, t6, rmax, f0, f1, f2, q0, q1, q2, mmax, wet};
 }
 
 // ocean_body_dynamics*: the buoyancy record and, beside it, the drag of the water's velocity relative to the
@@ -270,33 +262,9 @@ __global__ __launch_bounds__(256) void k_body_dynamics(DevView v, const float4* 
     const size_t b = (size_t)blockIdx.x * kBodies + threadIdx.x / W;
     const bool live = b < (size_t)count;
     const Pose pose = load_pose(bodies + 10 * b, live);
-    Motion mo = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (live) {
-        const float* Mo = motion + 6 * b;
-        mo.vx = Mo[0], mo.vy = Mo[1], mo.vz = Mo[2];
-        mo.ox = Mo[3], mo.oy = Mo[4], mo.oz = Mo[5];
-    }
-    const Wrench r = body_wrench<W>(v, vel, tile, mode, iterations, law, hull, probes, pose, mo, l, live);
-    if (live && l == 0) {
-        out[4 * b] = make_float4(r.t0, r.t1, r.t2, r.t3);
-        out[4 * b + 1] = make_float4(r.t4, r.t5, r.t6, r.rmax);
-        out[4 * b + 2] = make_float4(r.f0, r.f1, r.f2, r.q0);
-        out[4 * b + 3] = make_float4(r.q1, r.q2, r.mmax, r.wet);
-    }
-}
-
-// a rotated by the quaternion (u, w), as place_probe rotates a probe: t = 2 (u x a), (a + w t) + (u x t).
-struct Vec3 {
-    float x, y, z;
-};
-
-__device__ __forceinline__ Vec3 rotate(float ux, float uy, float uz, float w, float ax, float ay, float az) {
-    const float tx = 2.0f * (uy * az - uz * ay), ty = 2.0f * (uz * ax - ux * az), tz = 2.0f * (ux * ay - uy * ax);
-    Vec3 r;
-    r.x = (ax + w * tx) + (uy * tz - uz * ty);
-    r.y = (ay + w * ty) + (uz * tx - ux * tz);
-    r.z = (az + w * tz) + (ux * ty - uy * tx);
-    return r;
+    const Motion mo = load_motion(motion + 6 * b, live);
+    const Wrench r = body_wrench<W, true>(v, vel, tile, mode, iterations, law, hull, probes, pose, mo, l, live);
+    if (live && l == 0) store_wrench(out + 4 * b, r);
 }
 
 // ocean_body_step*: `substeps` substeps of the integrator ocean.h states, each behind the wrench of
@@ -318,12 +286,9 @@ __global__ __launch_bounds__(256) void k_body_step(DevView v, const float4* __re
     const size_t b = (size_t)blockIdx.x * kBodies + threadIdx.x / W;
     const bool live = b < (size_t)count;
     Pose pose = load_pose(state + 32 * b, live);
-    Motion mo = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    Motion mo = load_motion(state + 32 * b + 10, live);
     float im = 0.0f, jx = 0.0f, jy = 0.0f, jz = 0.0f;
     if (live) {
-        const float* Mo = state + 32 * b + 10;
-        mo.vx = Mo[0], mo.vy = Mo[1], mo.vz = Mo[2];
-        mo.ox = Mo[3], mo.oy = Mo[4], mo.oz = Mo[5];
         const float* Pr = props + 4 * b;
         im = Pr[0], jx = Pr[1], jy = Pr[2], jz = Pr[3];
     }
@@ -331,7 +296,7 @@ __global__ __launch_bounds__(256) void k_body_step(DevView v, const float4* __re
     const float hh = 0.5f * h;
     Wrench r = {};
     for (int step = 0; step < substeps; ++step) {
-        r = body_wrench<W>(v, vel, tile, mode, iterations, law, hull, probes, pose, mo, l, live);
+        r = body_wrench<W, true>(v, vel, tile, mode, iterations, law, hull, probes, pose, mo, l, live);
         const float ax = im * (kd * r.f0), ay = im * (B * r.t0 + kd * r.f1) - g, az = im * (kd * r.f2);
         const float tx = kt * r.q0 - B * r.t3, ty = kt * r.q1, tz = kt * r.q2 + B * r.t1;
         const Vec3 tb = rotate(-pose.ux, -pose.uy, -pose.uz, pose.qw, tx, ty, tz);  // the torque in the body frame
@@ -357,40 +322,29 @@ __global__ __launch_bounds__(256) void k_body_step(DevView v, const float4* __re
         out[8 * b + 1] = make_float4(pose.uy, pose.uz, pose.qw, pose.sx);
         out[8 * b + 2] = make_float4(pose.sy, pose.sz, mo.vx, mo.vy);
         out[8 * b + 3] = make_float4(mo.vz, mo.ox, mo.oy, mo.oz);
-        out[8 * b + 4] = make_float4(r.t0, r.t1, r.t2, r.t3);
-        out[8 * b + 5] = make_float4(r.t4, r.t5, r.t6, r.rmax);
-        out[8 * b + 6] = make_float4(r.f0, r.f1, r.f2, r.q0);
-        out[8 * b + 7] = make_float4(r.q1, r.q2, r.mmax, r.wet);
+        store_wrench(out + 8 * b + 4, r);
     }
 }
 
-template <int W>
-void launch_w(const DevView& v, int tile, int mode, int iterations, const float* hull, int probes,
-              const float* bodies, int count, float* out, hipStream_t s) {
-    constexpr int kBodies = 256 / W;
-    // count * probes <= OCEAN_BODY_MAX_SAMPLES = 2^22 and W < 2 probes: at most 2^22 / 4 + 1 workgroups
-    const unsigned g = (unsigned)(((size_t)count + kBodies - 1) / kBodies);
-    launch(k_body_buoyancy<W>, dim3(g), dim3(256), 0, s, v, tile, mode, iterations, hull, probes, bodies, count,
-           reinterpret_cast<float4*>(out));
+// f(std::integral_constant<int, W>) for W = body_segment_width(probes): the one place that names the seven widths.
+template <class F>
+void with_segment_width(int probes, F&& f) {
+    switch (body_segment_width(probes)) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        case 16: f(std::integral_constant<int, 16>{}); break;
+        case 32: f(std::integral_constant<int, 32>{}); break;
+        default: f(std::integral_constant<int, 64>{}); break;
+    }
 }
 
-template <int W>
-void launch_dynamics_w(const DevView& v, const float4* vel, int tile, int mode, int iterations, int law, const float* hull,
-                       int probes, const float* bodies, const float* motion, int count, float* out, hipStream_t s) {
-    constexpr int kBodies = 256 / W;
-    const unsigned g = (unsigned)(((size_t)count + kBodies - 1) / kBodies);  // as launch_w
-    launch(k_body_dynamics<W>, dim3(g), dim3(256), 0, s, v, vel, tile, mode, iterations, law, hull, probes, bodies, motion,
-           count, reinterpret_cast<float4*>(out));
-}
-
-template <int W>
-void launch_step_w(const DevView& v, const float4* vel, int tile, int mode, int iterations, int law, int substeps,
-                   const BodyStepParams& sp, const float* hull, int probes, const float* props, const float* state,
-                   int count, float* out, hipStream_t s) {
-    constexpr int kBodies = 256 / W;
-    const unsigned g = (unsigned)(((size_t)count + kBodies - 1) / kBodies);  // as launch_w
-    launch(k_body_step<W>, dim3(g), dim3(256), 0, s, v, vel, tile, mode, iterations, law, substeps, sp, hull, probes, props,
-           state, count, reinterpret_cast<float4*>(out));
+// Workgroups of 256 / w bodies each for `count` bodies.
+// count * probes <= OCEAN_BODY_MAX_SAMPLES = 2^22 and W < 2 probes: at most 2^22 / 4 + 1 workgroups
+dim3 body_groups(int count, int w) {
+    const size_t per = 256 / w;
+    return dim3((unsigned)(((size_t)count + per - 1) / per));
 }
 
 }  // namespace
@@ -405,15 +359,10 @@ hipError_t launch_body_buoyancy(const DevView& v, int tile, int mode, int iterat
                                 const float* bodies, int count, float* out, hipStream_t s) {
     if (count <= 0) return hipSuccess;
     if (probes < 1) return hipErrorInvalidValue;
-    switch (body_segment_width(probes)) {
-        case 1: launch_w<1>(v, tile, mode, iterations, hull, probes, bodies, count, out, s); break;
-        case 2: launch_w<2>(v, tile, mode, iterations, hull, probes, bodies, count, out, s); break;
-        case 4: launch_w<4>(v, tile, mode, iterations, hull, probes, bodies, count, out, s); break;
-        case 8: launch_w<8>(v, tile, mode, iterations, hull, probes, bodies, count, out, s); break;
-        case 16: launch_w<16>(v, tile, mode, iterations, hull, probes, bodies, count, out, s); break;
-        case 32: launch_w<32>(v, tile, mode, iterations, hull, probes, bodies, count, out, s); break;
-        default: launch_w<64>(v, tile, mode, iterations, hull, probes, bodies, count, out, s); break;
-    }
+    with_segment_width(probes, [&](auto w) {
+        launch(k_body_buoyancy<w()>, body_groups(count, w()), dim3(256), 0, s, v, tile, mode, iterations, hull, probes,
+               bodies, count, reinterpret_cast<float4*>(out));
+    });
     return hipGetLastError();
 }
 
@@ -422,18 +371,10 @@ hipError_t launch_body_dynamics(const DevView& v, const float4* vel, int tile, i
                                 float* out, hipStream_t s) {
     if (count <= 0) return hipSuccess;
     if (probes < 1 || !vel) return hipErrorInvalidValue;
-#define OCEAN_DYNAMICS_W(w) \
-    launch_dynamics_w<w>(v, vel, tile, mode, iterations, law, hull, probes, bodies, motion, count, out, s)
-    switch (body_segment_width(probes)) {
-        case 1: OCEAN_DYNAMICS_W(1); break;
-        case 2: OCEAN_DYNAMICS_W(2); break;
-        case 4: OCEAN_DYNAMICS_W(4); break;
-        case 8: OCEAN_DYNAMICS_W(8); break;
-        case 16: OCEAN_DYNAMICS_W(16); break;
-        case 32: OCEAN_DYNAMICS_W(32); break;
-        default: OCEAN_DYNAMICS_W(64); break;
-    }
-#undef OCEAN_DYNAMICS_W
+    with_segment_width(probes, [&](auto w) {
+        launch(k_body_dynamics<w()>, body_groups(count, w()), dim3(256), 0, s, v, vel, tile, mode, iterations, law, hull,
+               probes, bodies, motion, count, reinterpret_cast<float4*>(out));
+    });
     return hipGetLastError();
 }
 
@@ -442,18 +383,10 @@ hipError_t launch_body_step(const DevView& v, const float4* vel, int tile, int m
                             const float* state, int count, float* out, hipStream_t s) {
     if (count <= 0) return hipSuccess;
     if (probes < 1 || substeps < 1 || !vel) return hipErrorInvalidValue;
-#define OCEAN_STEP_W(w) \
-    launch_step_w<w>(v, vel, tile, mode, iterations, law, substeps, sp, hull, probes, props, state, count, out, s)
-    switch (body_segment_width(probes)) {
-        case 1: OCEAN_STEP_W(1); break;
-        case 2: OCEAN_STEP_W(2); break;
-        case 4: OCEAN_STEP_W(4); break;
-        case 8: OCEAN_STEP_W(8); break;
-        case 16: OCEAN_STEP_W(16); break;
-        case 32: OCEAN_STEP_W(32); break;
-        default: OCEAN_STEP_W(64); break;
-    }
-#undef OCEAN_STEP_W
+    with_segment_width(probes, [&](auto w) {
+        launch(k_body_step<w()>, body_groups(count, w()), dim3(256), 0, s, v, vel, tile, mode, iterations, law, substeps,
+               sp, hull, probes, props, state, count, reinterpret_cast<float4*>(out));
+    });
     return hipGetLastError();
 }
 

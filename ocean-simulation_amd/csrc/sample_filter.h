@@ -114,6 +114,37 @@ __device__ __forceinline__ float4 sample_disp(const DevView& v, int tile, float 
     return disp;
 }
 
+// Vs(x, z) of ocean_query_velocity: the bilinear taps of VEL (level 0) summed over the cascades like DISP.
+__device__ __forceinline__ float4 sample_velocity(const DevView& v, const float4* __restrict__ vel, int tile, float x,
+                                                  float z) {
+    float4 vs = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int c = 0; c < v.C; ++c) {
+        const float L = v.casc[c * 5];
+        const int slice = tile * v.C + c;
+        vs = add4(vs, tap(vel + (size_t)slice * v.n * v.n, v.n, bil(x / L, z / L, v.n)));
+    }
+    return vs;
+}
+
+// The full sample at (x, z) with the VEL taps beside it: per cascade one Bil serves the DISP, DERIV and VEL texels.
+// disp and deriv are sample_cascades(v, tile, x, z, 0)'s bit for bit (lod 0 is level 0 with and without mip
+// chains), vs is sample_velocity's; TURB, which no body term reads, is not tapped.
+__device__ __forceinline__ void sample_cascades_vel(const DevView& v, const float4* __restrict__ vel, int tile, float x,
+                                                    float z, WorldSample& s, float4& vs) {
+    s.disp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    s.deriv = s.disp;
+    s.turb = 0.0f;
+    vs = s.disp;
+    for (int c = 0; c < v.C; ++c) {
+        const float L = v.casc[c * 5];
+        const size_t slice = (size_t)(tile * v.C + c) * v.n * v.n;
+        const Bil b = bil(x / L, z / L, v.n);
+        s.disp = add4(s.disp, tap(v.disp + slice, v.n, b));
+        if (v.deriv) s.deriv = add4(s.deriv, tap(v.deriv + slice, v.n, b));
+        vs = add4(vs, tap(vel + slice, v.n, b));
+    }
+}
+
 // The .x channel of tap / tri alone: the same texels, weights and operations on that channel, 4 B per texel.
 __device__ __forceinline__ float tap_x(const float4* __restrict__ t, int m, const Bil& b) {
     const float t00 = t[(size_t)b.y0 * m + b.x0].x, t10 = t[(size_t)b.y0 * m + b.x1].x;

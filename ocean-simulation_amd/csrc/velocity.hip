@@ -65,12 +65,7 @@ __global__ __launch_bounds__(256) void k_query_velocity(DevView v, const float4*
     if (i >= count) return;
     const float qx = pts[2 * (size_t)i], qz = pts[2 * (size_t)i + 1];
     const float2 p = surface_fixed_point(v, tile, qx, qz, iterations);
-    float4 vs = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    for (int c = 0; c < v.C; ++c) {
-        const float L = v.casc[c * 5];
-        const int slice = tile * v.C + c;
-        vs = add4(vs, tap(vel + (size_t)slice * v.n * v.n, v.n, bil(p.x / L, p.y / L, v.n)));
-    }
+    const float4 vs = sample_velocity(v, vel, tile, p.x, p.y);
     const float4 d = sample_disp(v, tile, p.x, p.y);
     out[2 * (size_t)i] = make_float4(vs.x, vs.y, vs.z, surface_residual(d, p, qx, qz));
     out[2 * (size_t)i + 1] = make_float4(d.y, p.x, p.y, vs.w);

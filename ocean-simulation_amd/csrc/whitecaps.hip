@@ -117,12 +117,7 @@ __global__ __launch_bounds__(kThreads) void k_whitecap_emit(DevView v, const flo
         const float2 q = node_at(k, nx, x0, z0, dx, dz);
         const float4 d = sample_disp(v, tile, q.x, q.y);
         float4 vs = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (vel)  // ocean_query_velocity's Vs(q) with no fixed-point step
-            for (int c = 0; c < v.C; ++c) {
-                const float L = v.casc[c * 5];
-                const int slice = tile * v.C + c;
-                vs = add4(vs, tap(vel + (size_t)slice * v.n * v.n, v.n, bil(q.x / L, q.y / L, v.n)));
-            }
+        if (vel) vs = sample_velocity(v, vel, tile, q.x, q.y);  // ocean_query_velocity's Vs(q) with no fixed-point step
         float4* o = records + 2 * (size_t)rank;
         o[0] = make_float4(q.x + d.x, d.y, q.y + d.z, sample_foam(v, tile, q.x, q.y, lod));
         o[1] = make_float4(vs.x, vs.y, vs.z, (float)k);  // k < 2^22: exact
