@@ -82,7 +82,10 @@ extern "C" {
  *      OCEAN_BODY_STEP_MAX_SAMPLES, ocean_body_step, ocean_body_step_device, ocean_body_step_async.
  *      Added later within version 4 in the same way: OCEAN_ATMOSPHERE_FLOATS, OCEAN_ATMOSPHERE_MAX_DIM, OCEAN_LUT_*,
  *      OCEAN_CAMERA_SKY_LUT, ocean_atmosphere, ocean_sky_update, ocean_atmosphere_read, ocean_atmosphere_lut,
- *      ocean_sun_color. */
+ *      ocean_sun_color.
+ *      Added later within version 4 in the same way: OCEAN_SPRAY_FLOATS, OCEAN_SPRAY_MAX_PARTICLES,
+ *      OCEAN_SPRAY_MAX_STAGED, OCEAN_SPRAY_MAX_SUBSTEPS, ocean_spray_step, ocean_spray_step_device,
+ *      ocean_spray_step_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -696,7 +699,8 @@ int ocean_surface_bounds_device(ocean_ctx *ctx, int tile, float *out, size_t byt
  * of the cascades' max y plus a derived rounding margin) and samples only the nodes at or below it; every
  * result bit is as defined above, only the time differs.  A ray cast on a context whose bounds are stale
  * (see their cache rule) first enqueues the two bounds kernels on the ctx stream.  OCEAN_RAY_BOUNDS=0 in the
- * environment (read by ocean_create) turns the skip and those launches off.
+ * environment (read by ocean_create) turns the skip and those launches off, here, in ocean_camera* and in
+ * ocean_spray_step*, which skip the same way.
  *
  * The three forms, their ordering and `*req` are those of ocean_query_surface, ocean_query_surface_device and
  * ocean_query_surface_async: ocean_raycast takes host buffers and blocks; ocean_raycast_device takes device
@@ -1126,11 +1130,100 @@ int ocean_atmosphere_read(ocean_ctx *ctx, int which, float *out, size_t bytes);
 int ocean_atmosphere_lut(ocean_ctx *ctx, int which, void **dev, size_t *width, size_t *height);
 int ocean_sun_color(ocean_ctx *ctx, const float *sun, float *rgb);
 
+/* Spray particles: the particle system that reads the whitecap list.  ocean_whitecaps_device leaves the emitters on
+ * the device; without this entry a host that wants spray lands that list, integrates its particles on the CPU,
+ * uploads their positions, asks ocean_query_surface which of them fell back into the sea, lands the answers and
+ * compacts the survivors, every frame and every substep: the loop ocean_body_step removed for hulls.  Here one
+ * call spawns from the list, takes S substeps, retires and compacts, and a pool of particles stays on the device
+ * from frame to frame.  The reference has no counterpart.
+ *
+ * `pool` and `out` each hold capacity + 1 records of 32 B; `bytes` must equal (capacity + 1) * 32.  Record 0 is a
+ * header of eight uint32 in the whitecap list's layout: T, W, M, capacity, 0, 0, 0, 0.  Records 1 .. W are
+ * particles of eight floats:
+ *       [0..2] = the position p      [3] = the age a, in seconds
+ *       [4..6] = the velocity v      [7] = a tag, carried bit for bit
+ * An all-zero header is an empty pool.  Of the input pool's header only [1] is read, on the device, as
+ * n = min(header[1], capacity).  `emitters` is NULL (no spawning; emit_capacity must be 0) or a list exactly as
+ * ocean_whitecaps* writes it, of emit_capacity + 1 records, with e = min(header[1], emit_capacity).  The two clamps
+ * are the kernel's guard against a header this library did not write: no record beyond `capacity` or
+ * `emit_capacity` is ever read.
+ *
+ * `spray` is a host array of OCEAN_SPRAY_FLOATS floats in every form, read before the call returns and passed to the
+ * kernel by value, like `camera`:
+ *       [0] h  the substep, seconds      [1] g   gravity              [2] kd    linear drag against the wind, 1/s
+ *       [3..5] wind                      [6] life  seconds            [7] jet   scale of the water's velocity at spawn
+ *       [8] lift  upward speed per unit of the emitter's foam         [9..15]   reserved, must be 0
+ *
+ * Definition.  All arithmetic is fp32, one rounding per operation in the order written, no fused multiply-add.
+ * Candidates j = 0 .. M - 1, M = n + e:
+ *       j < n:   pool record 1 + j:   (p, a, v, tag) = ([0..2], [3], [4..6], [7])
+ *       else:    r = emitters record 1 + (j - n):   p = r[0..2],  a = 0,  tag = r[7],
+ *                v = (jet * r[4],  jet * r[5] + lift * r[3],  jet * r[6])
+ * A spawned particle is stepped like the rest, from age 0.  One substep of a live candidate (semi-implicit Euler, as
+ * ocean_body_step):
+ *       acc = (kd * (wind.x - v.x),  kd * (wind.y - v.y) - g,  kd * (wind.z - v.z))
+ *       v'  = (v.x + h * acc.x,  v.y + h * acc.y,  v.z + h * acc.z)
+ *       p'  = (p.x + h * v'.x,   p.y + h * v'.y,   p.z + h * v'.z)
+ *       a'  = a + h
+ *       eta = rec(p'.x, p'.z)[0]        rec = OCEAN_QUERY_SURFACE's record for that point with K = `iterations`, bit for bit
+ *       alive iff (p'.y > eta) and (a' < life)                 (fp32 compares: a NaN fails both and retires the particle)
+ * A candidate takes S = `substeps` substeps, or stops at the first it does not survive.  Then
+ *       T = the number of survivors,   rank(j) = the number of survivors j' < j,   W = min(T, capacity)
+ * and every survivor with rank(j) < capacity writes record 1 + rank(j) = (p', a', v', tag) of its last substep.
+ * Records W + 1 .. capacity are not written.  On overflow the first `capacity` survivors in candidate order are
+ * kept, so old particles outlive new spawns, and T still counts every survivor.  S substeps in one call equal S
+ * chained calls of one substep with NULL emitters after the first, bit for bit.
+ * The water is the frame's, the same for all substeps, and only DISP is read.  OCEAN_F_VELOCITY is not required: a
+ * context without it spawns from +0 velocities, as its whitecap list says.  DISPLACEMENT_ONLY contexts are valid
+ * (they have no whitecap lists of their own: pass NULL or a list from elsewhere).
+ *
+ * Three launches (step, scan, emit; kind 2 of ocean_kernel_stats / ocean_kernel_name) with no atomics and no
+ * workgroup that waits for another, the whitecaps' compaction: the result does not depend on the launch grid or on
+ * scheduling.  Each candidate is stepped once per call.  The launch grid follows capacity + emit_capacity, M being
+ * known only on the device.  Their scratch (32 B per candidate of capacity + emit_capacity, plus masks and counts)
+ * belongs to the context: allocated by the first call that needs it, grown when a call needs more, freed by
+ * ocean_destroy.
+ * Air skip, as ocean_raycast's: with H the height no wave reaches (there), p'.y > H over a finite (p'.x, p'.z) decides
+ * the first clause of `alive` true without a sample (a position whose x or z is a NaN or infinite has eta = NaN and is
+ * retired as defined); every result bit is as defined above, only the time differs.  The bounds launches
+ * on a context whose bounds are stale, and OCEAN_RAY_BOUNDS=0, are exactly ocean_raycast's.
+ *
+ * ocean_spray_step: `pool`, `emitters` and `out` are host buffers; blocks.
+ * ocean_spray_step_device: they are device pointers, each 16-B aligned (else OCEAN_E_INVALID_ARG); async on the ctx
+ * stream, ordered after the queued steps.  `out` may overlap neither input: ping-pong two pools.
+ * ocean_spray_step_async: `pool` and `emitters` are host buffers, consumed before the call returns; `out` is a host
+ * destination (pinned, ocean_host_alloc).  The pool is stepped into a readback slot on the ctx stream, after the
+ * steps queued so far and before later ones, and all (capacity + 1) * 32 bytes (at most 2 MiB: every result fits a
+ * slot) are copied on the copy stream, with the same ocean_readback_status / _wait / _release / _copy_ms.  The
+ * inputs outgrow a slot: they are staged in a pinned block and a device block that the slot owns beside its own
+ * memory, allocated by the slot's first spray request.  *req is NULL after every failure.
+ * The host and async forms stage pool and list and take at most OCEAN_SPRAY_MAX_STAGED particles; the device form
+ * takes OCEAN_SPRAY_MAX_PARTICLES.
+ * All three: OCEAN_E_INVALID_ARG, checked before any device call and before the context wherever the context is not
+ * needed: a null `spray`, `pool`, `out` or `req`; iterations outside [0, 16]; substeps outside
+ * [1, OCEAN_SPRAY_MAX_SUBSTEPS]; a `spray` value that is not finite or a nonzero reserved float; capacity outside
+ * [1, limit of the form]; emit_capacity outside [1, OCEAN_WHITECAP_MAX_RECORDS] when `emitters` is not NULL, or
+ * nonzero when it is NULL; (capacity + emit_capacity) * substeps > 1 << 24 (in 64 bits); a wrong `bytes`; a misaligned
+ * device pointer; then a null ctx and a tile out of range.  Then OCEAN_E_STATE before ocean_init_spectrum and
+ * OCEAN_E_UNSUPPORTED on a column-parity context (as the queries). */
+#define OCEAN_SPRAY_FLOATS 16
+#define OCEAN_SPRAY_MAX_PARTICLES ((1 << 20) - 1) /* device form */
+#define OCEAN_SPRAY_MAX_STAGED 65535              /* host and async forms, which stage pool and list */
+#define OCEAN_SPRAY_MAX_SUBSTEPS 64
+int ocean_spray_step(ocean_ctx *ctx, int tile, int iterations, int substeps, const float *spray, const float *pool,
+                     int capacity, const float *emitters, int emit_capacity, float *out, size_t bytes);
+int ocean_spray_step_device(ocean_ctx *ctx, int tile, int iterations, int substeps, const float *spray,
+                            const float *pool, int capacity, const float *emitters, int emit_capacity, float *out,
+                            size_t bytes);
+int ocean_spray_step_async(ocean_ctx *ctx, int tile, int iterations, int substeps, const float *spray, const float *pool,
+                           int capacity, const float *emitters, int emit_capacity, float *out, size_t bytes,
+                           ocean_readback **req);
+
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
  * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async /
  * ocean_body_buoyancy_async / ocean_query_velocity_async / ocean_raycast_async / ocean_body_dynamics_async /
- * ocean_whitecaps_async / ocean_camera_async / ocean_body_step_async request records HIP timing events around its
- * device-to-host copy, for ocean_readback_copy_ms.  Requests made while it is off record only untimed events. */
+ * ocean_whitecaps_async / ocean_camera_async / ocean_body_step_async / ocean_spray_step_async request records HIP
+ * timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it is off record only untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 
 /* Duration of a completed request's device-to-host copy in ms (HIP events on the copy stream around

@@ -194,6 +194,21 @@ namespace OceanHip
         public static extern OceanStatus ocean_whitecaps_device(IntPtr ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz, int nx, int ny, int capacity, IntPtr output, UIntPtr bytes);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_whitecaps_async(IntPtr ctx, int tile, float lod, float threshold, float x0, float z0, float dx, float dz, int nx, int ny, int capacity, IntPtr dst, UIntPtr bytes, out IntPtr request);
+        // Spray particles (added within ABI 4 in the same way).  pool and output = capacity + 1 records of 32 B, bytes =
+        // (capacity + 1) * 32: record 0 = eight uint (T survivors, W = min(T, capacity) written, M candidates, capacity, 0, 0,
+        // 0, 0), then 8 floats per particle: position x, y, z, age, velocity x, y, z, tag.  emitters = a whitecap list of
+        // emitCapacity + 1 records, or null with emitCapacity 0.  spray = 16 floats (h, g, kd, wind x, y, z, life, jet, lift,
+        // zeros).  The host and async forms take SprayMaxStaged particles, the device form SprayMaxParticles.
+        public const int SprayFloats = 16;
+        public const int SprayMaxParticles = (1 << 20) - 1;
+        public const int SprayMaxStaged = 65535;
+        public const int SprayMaxSubsteps = 64;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_spray_step(IntPtr ctx, int tile, int iterations, int substeps, [In] float[] spray, [In] float[] pool, int capacity, [In] float[] emitters, int emitCapacity, [Out] float[] output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_spray_step_device(IntPtr ctx, int tile, int iterations, int substeps, [In] float[] spray, IntPtr pool, int capacity, IntPtr emitters, int emitCapacity, IntPtr output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_spray_step_async(IntPtr ctx, int tile, int iterations, int substeps, [In] float[] spray, [In] float[] pool, int capacity, [In] float[] emitters, int emitCapacity, IntPtr dst, UIntPtr bytes, out IntPtr request);
         // Camera views (added within ABI 4 in the same way).  camera = 14 floats (eye, the direction through pixel (0, 0),
         // its change per column and per row, t0, t1); pixel (i, j) is element j * width + i.  CameraHits: ocean_raycast's 8
         // floats per pixel; CameraRange: the distance along the ray, +infinity after a miss, 1 float; CameraColor: r, g, b,

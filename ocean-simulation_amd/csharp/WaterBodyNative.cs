@@ -306,6 +306,23 @@ namespace OceanHip
             return total;
         }
 
+        // Spray particles (ocean.h ocean_spray_step): `pool` = (capacity + 1) * 8 floats, the header and the particles (8
+        // floats each: position, age, velocity, tag); one fresh particle is spawned per record of the whitecap list
+        // `emitters` ((emitCapacity + 1) * 8 floats as ocean_whitecaps writes it, or null); all take `substeps` substeps
+        // under the 16 floats of `spray` against this frame's water, and those that fall back into the sea or outlive
+        // their life are retired.  Returns the stepped pool, which is the next call's `pool`.  The reference has no
+        // particles.
+        public float[] Spray(float[] spray, float[] pool, float[] emitters = null, int substeps = 1, int iterations = 2)
+        {
+            int capacity = pool.Length / 8 - 1;
+            int emitCapacity = emitters == null ? 0 : emitters.Length / 8 - 1;
+            var output = new float[pool.Length];
+            OceanNative.Check(OceanNative.ocean_spray_step(ctx, 0, iterations, substeps, spray, pool, capacity, emitters,
+                                                           emitCapacity, output, (UIntPtr)(ulong)(output.Length * 4)),
+                              "ocean_spray_step");
+            return output;
+        }
+
         // What a camera sees of the water (ocean.h ocean_camera): `camera` = 14 floats (eye, the direction through pixel
         // (0, 0), its change per column and per row, t0, t1).  OceanNative.CameraColor shades the fragment stage of
         // Water.shader with the 32 floats of `material` and returns r, g, b, status per pixel; CameraRange returns

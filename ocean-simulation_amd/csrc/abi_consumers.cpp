@@ -1,5 +1,6 @@
 // C-ABI layer of liboceanhip.so, the point consumers (ocean.h): surface and velocity queries, surface grids,
-// buoyant bodies, body dynamics, body steps, ray casts, whitecap emitters and camera views, each in a _device, a blocking host
+// buoyant bodies, body dynamics, body steps, ray casts, whitecap emitters, spray particles and camera views, each in a
+// _device, a blocking host
 // and an _async form; and world sampling and the surface bounds, which keep bodies of their own.
 //
 // A consumer is stated once, as a struct built from its entry's arguments (a "family"), and its three entries
@@ -524,6 +525,87 @@ struct Camera {
     }
 };
 
+// Spray particles: the pool, (capacity + 1) records of 32 B, and the emitter list or none -> the stepped pool, with
+// the sixteen `spray` floats by value.  As for the whitecaps, what does not need the context is checked first, the
+// _device form's alignment (16 B for all three pointers: the kernels load and store float4) with it.  The staged
+// forms take OCEAN_SPRAY_MAX_STAGED particles, and the async form's inputs outgrow a slot (StageSlot).  The three
+// kernels run over the context's scratch, which grows to the largest call, behind the bounds launches exactly as
+// the ray casts' kernel does.
+struct Spray {
+    ocean_ctx* ctx;
+    int tile, iterations, substeps;
+    const float* spray;
+    const float* pool;
+    int capacity;
+    const float* emitters;
+    int emit_capacity;
+    float* out;
+    size_t bytes;
+
+    int check(Form form) const {
+        if (!spray || !pool || !out) return fail(OCEAN_E_INVALID_ARG, "null spray, pool or output");
+        if (int r = check_iterations(iterations)) return r;
+        if (substeps < 1 || substeps > OCEAN_SPRAY_MAX_SUBSTEPS)
+            return fail(OCEAN_E_INVALID_ARG, "substeps = " + std::to_string(substeps) + " outside [1, OCEAN_SPRAY_MAX_SUBSTEPS]");
+        for (int k = 0; k < OCEAN_SPRAY_FLOATS; ++k) {
+            if (!std::isfinite(spray[k])) return fail(OCEAN_E_INVALID_ARG, "spray[" + std::to_string(k) + "] is not finite");
+            if (k >= 9 && spray[k] != 0.0f)
+                return fail(OCEAN_E_INVALID_ARG, "spray[" + std::to_string(k) + "] is reserved and must be 0");
+        }
+        const int limit = form == Form::Device ? OCEAN_SPRAY_MAX_PARTICLES : OCEAN_SPRAY_MAX_STAGED;
+        if (capacity < 1 || capacity > limit)
+            return fail(OCEAN_E_INVALID_ARG, "capacity = " + std::to_string(capacity) + " outside [1, " +
+                                                 (form == Form::Device ? "OCEAN_SPRAY_MAX_PARTICLES]" : "OCEAN_SPRAY_MAX_STAGED]"));
+        if (emitters ? emit_capacity < 1 || emit_capacity > OCEAN_WHITECAP_MAX_RECORDS : emit_capacity != 0)
+            return fail(OCEAN_E_INVALID_ARG, "emit_capacity = " + std::to_string(emit_capacity) +
+                                                 (emitters ? " outside [1, OCEAN_WHITECAP_MAX_RECORDS]" : " without emitters (must be 0)"));
+        const uint64_t steps = ((uint64_t)capacity + (uint64_t)emit_capacity) * (uint64_t)substeps;
+        if (steps > ((uint64_t)1 << 24))
+            return fail(OCEAN_E_INVALID_ARG, "(capacity + emit_capacity) * substeps = " + std::to_string(steps) + " > 1 << 24");
+        const size_t want = ((size_t)capacity + 1) * 32;
+        if (bytes != want)
+            return fail(OCEAN_E_INVALID_ARG, "byte count " + std::to_string(bytes) + " != (capacity + 1) * 32 = " +
+                                                 std::to_string(want));
+        if (form == Form::Device && ((((uintptr_t)pool | (uintptr_t)emitters | (uintptr_t)out) & 15) != 0))
+            return fail(OCEAN_E_INVALID_ARG, "ocean_spray_step_device: pool, emitters and out must be 16-byte aligned");
+        if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+        return check_tile(ctx, tile);
+    }
+    StateRule state() const { return {"ocean_spray_step", "spray steps on"}; }
+    StagedInputs inputs() const {
+        return {"pool and emitters",
+                emitters ? 2 : 1,
+                {{pool, bytes}, {emitters, emitters ? ((size_t)emit_capacity + 1) * 32 : 0}},
+                0,
+                true};
+    }
+    size_t out_bytes() const { return bytes; }
+    const char* lacks() const { return nullptr; }
+    int launch(const float* const* in, float* d_out) const {
+        const size_t need = ocean::spray_scratch_bytes(capacity, emit_capacity);
+        if (need > ctx->spray_dev_bytes) {  // (hipFree waits for the launches that still read the old block)
+            if (ctx->spray_dev) OCEAN_HIP(hipFree(ctx->spray_dev));
+            ctx->spray_dev = nullptr;
+            ctx->spray_dev_bytes = 0;
+            OCEAN_HIP(hipMalloc(&ctx->spray_dev, need));
+            ctx->spray_dev_bytes = need;
+        }
+        const float* bounds = nullptr;
+        if (ctx->opt.ray_bounds)
+            if (int r = ensure_bounds(ctx, tile, &bounds)) return r;
+        ocean::SprayParams sp;
+        std::copy(spray, spray + OCEAN_SPRAY_FLOATS, sp.p);
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] {
+                         return ocean::launch_spray_step(v, tile, iterations, substeps, sp, bounds, in[0], capacity,
+                                                         emitters ? in[1] : nullptr, emit_capacity, ctx->spray_dev, d_out,
+                                                         ctx->stream);
+                     },
+                     "spray_step");
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -661,6 +743,23 @@ int ocean_camera(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, 
 int ocean_camera_async(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, int refine, const float* camera,
                        const float* material, int width, int height, float* out, size_t bytes, ocean_readback** req) {
     return async_form(Camera{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes}, req);
+}
+
+int ocean_spray_step_device(ocean_ctx* ctx, int tile, int iterations, int substeps, const float* spray, const float* pool,
+                            int capacity, const float* emitters, int emit_capacity, float* out, size_t bytes) {
+    return device_form(Spray{ctx, tile, iterations, substeps, spray, pool, capacity, emitters, emit_capacity, out, bytes});
+}
+
+int ocean_spray_step(ocean_ctx* ctx, int tile, int iterations, int substeps, const float* spray, const float* pool,
+                     int capacity, const float* emitters, int emit_capacity, float* out, size_t bytes) {
+    return host_form(Spray{ctx, tile, iterations, substeps, spray, pool, capacity, emitters, emit_capacity, out, bytes});
+}
+
+int ocean_spray_step_async(ocean_ctx* ctx, int tile, int iterations, int substeps, const float* spray, const float* pool,
+                           int capacity, const float* emitters, int emit_capacity, float* out, size_t bytes,
+                           ocean_readback** req) {
+    return async_form(Spray{ctx, tile, iterations, substeps, spray, pool, capacity, emitters, emit_capacity, out, bytes},
+                      req);
 }
 
 // World sampling has no async form and enters the device scope before its checks.

@@ -92,9 +92,18 @@ static_assert((size_t)OCEAN_RAY_MAX_RAYS * 8 * sizeof(float) <= kQueryPointsOffs
 // Whitecaps: the largest list, header included, fits the smallest slot.  (A surface grid's size depends on its
 // arguments: ocean_surface_grid_async checks it against stage_slot_bytes.)
 static_assert(((size_t)OCEAN_WHITECAP_MAX_RECORDS + 1) * 32 <= kQuerySlotBytes, "a readback slot holds every whitecap list");
+// Spray: the stepped pool, header included, fits the smallest slot like a whitecap list.  Its inputs do not: the pool
+// and the emitter list are 2 MiB each at the limits, more than the slot has left and more than the pinned copy
+// holds.  ocean_spray_step_async stages them in a block pair of the slot's own (StagedInputs::own_block), which the
+// slot's first spray request allocates, so a context that never steps spray holds what it always did.
+constexpr size_t kSprayInputBytes = ((size_t)OCEAN_SPRAY_MAX_STAGED + 1) * 32 + ((size_t)OCEAN_WHITECAP_MAX_RECORDS + 1) * 32;
+static_assert(((size_t)OCEAN_SPRAY_MAX_STAGED + 1) * 32 <= kQuerySlotBytes, "a readback slot holds every staged pool");
+static_assert(kSprayInputBytes == 4096 * 1024, "the arithmetic above");
 struct StageSlot {
     void* mem = nullptr;
     void* pts_host = nullptr;    // pinned, kStageInputBytes: the inputs of the request holding the slot
+    void* big_host = nullptr;    // pinned, kSprayInputBytes, and its device twin: a spray request's inputs
+    void* big_dev = nullptr;
     hipEvent_t after = nullptr;  // the snapshot is in the slot (the copy stream waits for it)
     hipEvent_t done = nullptr;   // the host copy has landed (untimed requests)
     hipEvent_t tstart = nullptr, tdone = nullptr;  // timed requests: around the host copy itself
@@ -186,6 +195,10 @@ struct ocean_ctx {
     // whitecap emitters (whitecaps.hip): the ballot masks and per-chunk counts of the largest grid, allocated by the
     // first ocean_whitecaps* call and reused by every later one
     void* whitecap_dev = nullptr;
+    // spray particles (spray.hip): the stepped records, ballot masks and per-chunk counts of the largest call so far,
+    // allocated by the first ocean_spray_step* call and grown when a call needs more
+    void* spray_dev = nullptr;
+    size_t spray_dev_bytes = 0;
     // the staging block of the blocking host forms (run_staged_impl): inputs, then the output; grown on demand
     void* stage_block = nullptr;
     size_t stage_block_bytes = 0;
@@ -371,6 +384,7 @@ struct StagedInputs {
     int n;
     HostInput v[kMaxInputs];
     size_t slot_offset = kQueryPointsOffset;  // where an async request puts them in its slot (StageSlot)
+    bool own_block = false;  // an async request stages them in the slot's big_host / big_dev pair instead (spray)
 };
 
 // Bytes of a readback slot of this context: the largest slice (float4 textures), or a full surface query's

@@ -17,6 +17,8 @@ struct StagePool {
         for (StageSlot* sl : all) {
             if (sl->mem) (void)hipFree(sl->mem);
             if (sl->pts_host) (void)hipHostFree(sl->pts_host);
+            if (sl->big_host) (void)hipHostFree(sl->big_host);
+            if (sl->big_dev) (void)hipFree(sl->big_dev);
             for (hipEvent_t e : {sl->after, sl->done, sl->tstart, sl->tdone})
                 if (e) (void)hipEventDestroy(e);
             delete sl;
@@ -165,16 +167,25 @@ int start_staged_readback_impl(ocean_ctx* ctx, const StagedInputs& in, void* dst
         ctx, dst, out_bytes,
         [&](StageSlot* sl) -> int {
             char* base = static_cast<char*>(sl->mem) + in.slot_offset;
+            void* host = nullptr;
             const float* d_in[kMaxInputs] = {};
-            if (in.n != 0) {
+            if (in.n != 0 && in.own_block) {  // inputs that outgrow the slot: its own block pair
+                if (!sl->big_host) OCEAN_HIP(hipHostMalloc(&sl->big_host, kSprayInputBytes, hipHostMallocDefault));
+                if (!sl->big_dev) OCEAN_HIP(hipMalloc(&sl->big_dev, kSprayInputBytes));
+                base = static_cast<char*>(sl->big_dev);
+                host = sl->big_host;
+            } else if (in.n != 0) {
                 if (!sl->pts_host) OCEAN_HIP(hipHostMalloc(&sl->pts_host, kStageInputBytes, hipHostMallocDefault));
+                host = sl->pts_host;
+            }
+            if (in.n != 0) {
                 size_t in_bytes = 0;
                 for (int k = 0; k < in.n; ++k) {
                     d_in[k] = reinterpret_cast<const float*>(base + in_bytes);
-                    std::memcpy(static_cast<char*>(sl->pts_host) + in_bytes, in.v[k].ptr, in.v[k].bytes);
+                    std::memcpy(static_cast<char*>(host) + in_bytes, in.v[k].ptr, in.v[k].bytes);
                     in_bytes += in.v[k].bytes;
                 }
-                OCEAN_HIP(hipMemcpyAsync(base, sl->pts_host, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+                OCEAN_HIP(hipMemcpyAsync(base, host, in_bytes, hipMemcpyHostToDevice, ctx->stream));
             }
             return launch(arg, d_in, static_cast<float*>(sl->mem));
         },

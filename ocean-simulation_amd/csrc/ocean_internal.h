@@ -249,6 +249,24 @@ hipError_t launch_camera_sky(const DevView& v, int tile, int iterations, int ste
 size_t whitecap_scratch_bytes();
 hipError_t launch_whitecaps(const DevView& v, const float4* vel, int tile, float lod, float threshold, float x0, float z0,
                             float dx, float dz, int nx, int ny, int capacity, void* scratch, float* out, hipStream_t s);
+// whitecaps.hip: the scan between a compaction's count and emit launches, one workgroup: counts[0 .. items) become
+// exclusive offsets in place and `out` gets the header record (T, min(T, capacity), third, capacity, 0, 0, 0, 0),
+// third = *nodes_dev when that is not null, else nodes.
+hipError_t launch_compact_scan(unsigned* counts, unsigned items, unsigned nodes, const unsigned* nodes_dev,
+                               unsigned capacity, float* out, hipStream_t s);
+
+// spray.hip: spray particles (ocean_spray_step*), device pointers: pool and out = (capacity + 1) records of 32 B, the
+// header then the particles, emitters = a whitecap list of (emit_capacity + 1) records or null with emit_capacity 0,
+// all 16-B aligned; sp = the entry's sixteen `spray` floats, which travel as a kernel argument; bounds as
+// launch_raycast takes them; scratch: spray_scratch_bytes(capacity, emit_capacity) bytes, 16-B aligned.  Three
+// launches: step, scan, emit.
+struct SprayParams {
+    float p[OCEAN_SPRAY_FLOATS];
+};
+size_t spray_scratch_bytes(int capacity, int emit_capacity);
+hipError_t launch_spray_step(const DevView& v, int tile, int iterations, int substeps, const SprayParams& sp,
+                             const float* bounds, const float* pool, int capacity, const float* emitters,
+                             int emit_capacity, void* scratch, float* out, hipStream_t s);
 
 // fft4k.hip (N = 2048, 4096: pass_c4_supported): four-step column passes C1 (in place on the
 // 16-wide tile-major intermediate) + C2 (with the pass-B epilogue); replace pass B.

@@ -63,10 +63,11 @@ __global__ __launch_bounds__(kThreads) void k_whitecap_count(DevView v, int tile
 }
 
 // One workgroup.  Lane t owns the items [t * per, (t + 1) * per): it sums them, the workgroup scans the 256
-// sums, and the lane writes its items' exclusive offsets from its own.
+// sums, and the lane writes its items' exclusive offsets from its own.  The header's third field is `nodes`, or
+// *nodes_dev where the candidates are counted on the device (the spray particles, spray.hip).
 __global__ __launch_bounds__(kThreads) void k_whitecap_scan(unsigned* __restrict__ counts, unsigned items,
-                                                            unsigned nodes, unsigned capacity,
-                                                            uint4* __restrict__ header) {
+                                                            unsigned nodes, const unsigned* __restrict__ nodes_dev,
+                                                            unsigned capacity, uint4* __restrict__ header) {
     __shared__ unsigned wsum[kWaves];
     const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const unsigned per = (items + kThreads - 1) / kThreads;
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(kThreads) void k_whitecap_scan(unsigned* __restrict
         run += c;
     }
     if (threadIdx.x == 0) {
-        header[0] = make_uint4(total, min(total, capacity), nodes, capacity);
+        header[0] = make_uint4(total, min(total, capacity), nodes_dev ? *nodes_dev : nodes, capacity);
         header[1] = make_uint4(0u, 0u, 0u, 0u);
     }
 }
@@ -126,6 +127,13 @@ __global__ __launch_bounds__(kThreads) void k_whitecap_emit(DevView v, const flo
 
 }  // namespace
 
+hipError_t launch_compact_scan(unsigned* counts, unsigned items, unsigned nodes, const unsigned* nodes_dev,
+                               unsigned capacity, float* out, hipStream_t s) {
+    launch(k_whitecap_scan, dim3(1), dim3(kThreads), 0, s, counts, items, nodes, nodes_dev, capacity,
+           reinterpret_cast<uint4*>(out));
+    return hipGetLastError();
+}
+
 size_t whitecap_scratch_bytes() {
     return (size_t)(OCEAN_GRID_MAX_NODES / 64) * sizeof(unsigned long long) +
            (size_t)(OCEAN_GRID_MAX_NODES / kThreads) * sizeof(unsigned);
@@ -143,9 +151,7 @@ hipError_t launch_whitecaps(const DevView& v, const float4* vel, int tile, float
     hipError_t e = launch_items(k_whitecap_count, kThreads, it, s, v, tile, lod, threshold, x0, z0, dx, dz, (unsigned)nx,
                                 nodes, items, masks, counts);
     if (e != hipSuccess) return e;
-    launch(k_whitecap_scan, dim3(1), dim3(kThreads), 0, s, counts, items, nodes, (unsigned)capacity,
-           reinterpret_cast<uint4*>(out));
-    e = hipGetLastError();
+    e = launch_compact_scan(counts, items, nodes, nullptr, (unsigned)capacity, out, s);
     if (e != hipSuccess) return e;
     return launch_items(k_whitecap_emit, kThreads, it, s, v, vel, tile, lod, x0, z0, dx, dz, (unsigned)nx, items,
                         (unsigned)capacity, (const unsigned long long*)masks, (const unsigned*)counts,

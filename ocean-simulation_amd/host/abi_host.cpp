@@ -4,7 +4,7 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|sky|step]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|sky|step|spray]
 //
 // With step the host plays F frames on a velocity context and, behind each, advances a fleet of six boxes of 4 x 3
 // probes by 4 substeps of 1/240 s through one WaterBody::StepBodies in its async form (surface mode, 4 steps,
@@ -21,6 +21,10 @@
 // it writes transmittance.bin, multiscatter.bin, skyview.bin (float32 [h][w][4] each), sun.bin (float32 [3]),
 // sun_color.bin (float32 [3]), camera.bin, material.bin and sky_color.bin (float32 [24][32][4]);
 // tests/test_gpu_atmosphere_host.py checks them.
+// With spray the host runs F steps on a velocity context, takes the whitecaps mode's list, and makes two
+// WaterBody::Spray calls of four substeps (K = 2): one that spawns from the list into an empty pool of 8192, one that
+// advances that pool without spawning.  It writes spray_emitters.bin (float32 [4097][8]), spray0.bin and spray1.bin
+// (float32 [8193][8]: the header, the W particles, zeros); tests/test_gpu_spray_host.py checks them.
 // With whitecaps the host reads nothing back per frame: it runs F steps on a velocity context, then one
 // WaterBody::Whitecaps over a 101 x 101 grid (threshold 0.1, capacity 4096, lod 0) and writes whitecaps.bin (float32
 // [4097][8]: the header, the W records, zeros); the summary line carries the header's T and W and the W records
@@ -72,13 +76,14 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|sky|step]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|sky|step|spray]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
     if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity" &&
-        mode != "rays" && mode != "dynamics" && mode != "whitecaps" && mode != "camera" && mode != "sky" && mode != "step") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps, camera, sky or step\n");
+        mode != "rays" && mode != "dynamics" && mode != "whitecaps" && mode != "camera" && mode != "sky" && mode != "step" &&
+        mode != "spray") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps, camera, sky, step or spray\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -216,6 +221,34 @@ int main(int argc, char** argv) {
                         "\"written\": %u, \"records\": [", F, n, (int)wb.cascades.size(), head[2], head[3], head[0], head[1]);
             for (size_t i = 0; i < (size_t)head[1] * 8; ++i) std::printf("%s%.9g", i ? ", " : "", list[8 + i]);
             std::printf("]}\n");
+            wb.OnDisable();
+            return 0;
+        }
+        if (mode == "spray") {
+            // the whitecaps mode's region and list, then two spray calls of four substeps of 1/240 s: the first spawns
+            // from the list into an empty pool of 8192, the second advances that pool without spawning
+            const float threshold = 0.1f, x0 = -500.0f, z0 = -500.0f, dx = 10.0f, dz = 10.0f;
+            const int nx = 101, ny = 101, capacity = 4096, pool_capacity = 8192, substeps = 4, iterations = 2;
+            // h, g, kd, wind, life, jet, lift, reserved
+            const std::vector<float> spray = {1.0f / 240.0f, 9.81f, 0.5f, 3.0f, 0.0f, 1.0f, 2.0f, 1.0f,
+                                              8.0f,          0.0f,  0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            wb.velocity = true;
+            wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
+            wb.Awake();
+            for (int f = 0; f < F; ++f) wb.Update((float)f / 60.0f);
+            const std::vector<float> list = wb.Whitecaps(threshold, x0, z0, dx, dz, nx, ny, capacity);
+            const std::vector<float> first =
+                wb.Spray(spray, ocean_host::WaterBody::EmptyPool(pool_capacity), list, substeps, iterations);
+            const std::vector<float> second = wb.Spray(spray, first, {}, substeps, iterations);
+            uint32_t h1[8], h2[8];
+            ocean_host::WaterBody::WhitecapHeader(first, h1);
+            ocean_host::WaterBody::WhitecapHeader(second, h2);
+            write_bin(out + "/spray_emitters.bin", list.data(), list.size());
+            write_bin(out + "/spray0.bin", first.data(), first.size());
+            write_bin(out + "/spray1.bin", second.data(), second.size());
+            std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"capacity\": %u, \"candidates\": [%u, %u], "
+                        "\"survivors\": [%u, %u], \"written\": [%u, %u]}\n", F, n, (int)wb.cascades.size(), h1[3], h1[2],
+                        h2[2], h1[0], h2[0], h1[1], h2[1]);
             wb.OnDisable();
             return 0;
         }

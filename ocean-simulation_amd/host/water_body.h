@@ -367,6 +367,30 @@ public:
         std::memcpy(head, list.data(), 8 * sizeof(uint32_t));
     }
 
+    // Spray particles (ocean.h ocean_spray_step): `pool` holds capacity + 1 records of 8 floats, the header and the
+    // particles (position, age, velocity, tag); one fresh particle is spawned per record of the whitecap list `emitters`
+    // (as Whitecaps returns it, or empty for none); all take `substeps` substeps under the 16 floats of `spray` (h, g,
+    // kd, wind x, y, z, life, jet, lift, zeros) against this frame's water, and those that fall back into the sea or
+    // outlive their life are retired.  Returns the stepped pool, the records past W zero: the next call's `pool`.
+    // EmptyPool(capacity) starts one.  The reference has no particles.
+    std::vector<float> Spray(const std::vector<float>& spray, const std::vector<float>& pool,
+                             const std::vector<float>& emitters = {}, int substeps = 1, int iterations = 2) const {
+        if (spray.size() != OCEAN_SPRAY_FLOATS || pool.size() < 8 || pool.size() % 8 || emitters.size() % 8)
+            throw std::runtime_error("Spray: spray is 16 floats, pool and emitters records of 8");
+        const int capacity = (int)(pool.size() / 8) - 1;
+        const int emit_capacity = emitters.empty() ? 0 : (int)(emitters.size() / 8) - 1;
+        std::vector<float> out(pool.size());
+        check(ocean_spray_step(ctx_, 0, iterations, substeps, spray.data(), pool.data(), capacity,
+                               emitters.empty() ? nullptr : emitters.data(), emit_capacity, out.data(),
+                               out.size() * sizeof(float)),
+              "ocean_spray_step");
+        uint32_t head[8];
+        WhitecapHeader(out, head);  // the same layout
+        std::fill(out.begin() + 8 * ((size_t)head[1] + 1), out.end(), 0.0f);  // unspecified in the library's output
+        return out;
+    }
+    static std::vector<float> EmptyPool(int capacity) { return std::vector<float>(((size_t)capacity + 1) * 8, 0.0f); }
+
     // The per-cascade bounds of the displacement (ocean.h ocean_surface_bounds): 8 floats per cascade, (min x, y,
     // z, w, max x, y, z, w); their cascade sums bound the displaced mesh.
     std::vector<float> SurfaceBounds() const {

@@ -76,6 +76,7 @@ EXPORTED_SYMBOLS = (
     "ocean_camera", "ocean_camera_device", "ocean_camera_async",
     "ocean_body_step", "ocean_body_step_device", "ocean_body_step_async",
     "ocean_atmosphere", "ocean_sky_update", "ocean_atmosphere_read", "ocean_atmosphere_lut", "ocean_sun_color",
+    "ocean_spray_step", "ocean_spray_step_device", "ocean_spray_step_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -114,6 +115,12 @@ ATMOSPHERE_DEFAULT_DIMS = (64, 256, 64, 64, 256, 128)
 BODY_STEP_FLOATS = 8
 BODY_MAX_SUBSTEPS = 64
 BODY_STEP_MAX_SAMPLES = 1 << 24
+# ocean_spray_step* array size and limits (ocean.h): the device form's particles, and those of the host and async
+# forms, which stage pool and list
+SPRAY_FLOATS = 16
+SPRAY_MAX_PARTICLES = (1 << 20) - 1
+SPRAY_MAX_STAGED = 65535
+SPRAY_MAX_SUBSTEPS = 64
 
 
 class OceanError(RuntimeError):
@@ -219,6 +226,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_atmosphere_read": ([P, i, P, sz], i),
         "ocean_atmosphere_lut": ([P, i, ctypes.POINTER(P), ctypes.POINTER(sz), ctypes.POINTER(sz)], i),
         "ocean_sun_color": ([P, P, P], i),
+        "ocean_spray_step": ([P, i, i, i, P, P, i, P, i, P, sz], i),
+        "ocean_spray_step_device": ([P, i, i, i, P, P, i, P, i, P, sz], i),
+        "ocean_spray_step_async": ([P, i, i, i, P, P, i, P, i, P, sz, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -715,6 +725,89 @@ class OceanContext:
                                                ctypes.c_void_p(out_ptr), (int(capacity) + 1) * 32), "ocean_whitecaps_device")
 
     @staticmethod
+    def spray_params(h: float, g: float = 9.81, kd: float = 0.0, wind=(0.0, 0.0, 0.0), life: float = 4.0,
+                     jet: float = 1.0, lift: float = 0.0) -> np.ndarray:
+        """The float32[16] `spray` of ocean_spray_step (ocean.h): (h, g, kd, wind xyz, life, jet, lift, zeros)."""
+        sp = np.zeros(SPRAY_FLOATS, np.float32)
+        sp[:9] = (h, g, kd, wind[0], wind[1], wind[2], life, jet, lift)
+        return sp
+
+    @staticmethod
+    def spray_pool(records, capacity: int) -> np.ndarray:
+        """A pool float32[capacity + 1][8] as ocean_spray_step reads it, holding `records` float32[W][8] = (position,
+        age, velocity, tag) behind the header (W, W, W, capacity, 0, 0, 0, 0); the rest is zero."""
+        rec = np.ascontiguousarray(records, np.float32).reshape(-1, 8)
+        if rec.shape[0] > capacity:
+            raise ValueError(f"{rec.shape[0]} records > capacity {capacity}")
+        buf = np.zeros((int(capacity) + 1, 8), np.float32)
+        buf[0].view(np.uint32)[:4] = (rec.shape[0], rec.shape[0], rec.shape[0], capacity)
+        buf[1:1 + rec.shape[0]] = rec
+        return buf
+
+    @staticmethod
+    def parse_spray(buf: np.ndarray):
+        """(T, M, records float32[W][8]) of a pool float32[capacity + 1][8] as ocean_spray_step writes it: the header's
+        eight uint32 (T, W, M, capacity, 0, 0, 0, 0), then the W surviving particles in candidate order (a copy)."""
+        buf = np.ascontiguousarray(buf, np.float32).reshape(-1, 8)
+        head = buf[0].view(np.uint32)
+        return int(head[0]), int(head[2]), buf[1:1 + int(head[1])].copy()
+
+    @staticmethod
+    def _spray_args(spray, pool, emitters):
+        """(spray float32[16], pool float32[capacity + 1][8], capacity, emitters or None, emit_capacity)."""
+        sp = np.ascontiguousarray(spray, np.float32).reshape(-1)
+        if sp.shape[0] != SPRAY_FLOATS:
+            raise ValueError(f"spray must be float32[{SPRAY_FLOATS}] (spray_params), got {sp.shape}")
+        pl = np.ascontiguousarray(pool, np.float32)
+        if pl.ndim != 2 or pl.shape[1] != 8 or pl.shape[0] < 1:
+            raise ValueError(f"pool must be float32[capacity + 1][8], got {pl.shape}")
+        em = None
+        if emitters is not None:
+            em = np.ascontiguousarray(emitters, np.float32)
+            if em.ndim != 2 or em.shape[1] != 8 or em.shape[0] < 1:
+                raise ValueError(f"emitters must be float32[emit_capacity + 1][8], got {em.shape}")
+        return sp, pl, pl.shape[0] - 1, em, (em.shape[0] - 1 if em is not None else 0)
+
+    def spray_step(self, spray, pool, emitters=None, substeps: int = 1, iterations: int = 2, tile: int = 0) -> np.ndarray:
+        """Spray particles (ocean.h ocean_spray_step), blocking: the candidates of `pool` float32[capacity + 1][8]
+        and, behind them, one fresh particle per record of the whitecap list `emitters` float32[emit_capacity + 1][8]
+        (or None) take `substeps` substeps under `spray` (spray_params) and the survivors come back compacted, in
+        candidate order -> float32[capacity + 1][8], the records past W zero; parse_spray reads it."""
+        sp, pl, capacity, em, emit_capacity = self._spray_args(spray, pool, emitters)
+        out = np.zeros_like(pl)
+        _check(self.lib.ocean_spray_step(self._h, tile, iterations, substeps, sp.ctypes.data, pl.ctypes.data, capacity,
+                                         em.ctypes.data if em is not None else None, emit_capacity, out.ctypes.data,
+                                         out.nbytes), "ocean_spray_step")
+        out[1 + min(int(out[0].view(np.uint32)[1]), capacity):] = 0  # unspecified in the library's output
+        return out
+
+    def spray_step_async(self, spray, pool, emitters=None, substeps: int = 1, iterations: int = 2, tile: int = 0,
+                         buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_spray_step_async): `pool` and `emitters` are consumed by the call, the pool is
+        stepped behind the queued steps and its float32[capacity + 1][8] lands in pinned host memory.  Poll .done() /
+        .wait(), then .spray() -> (T, M, records[W][8])."""
+        sp, pl, capacity, em, emit_capacity = self._spray_args(spray, pool, emitters)
+        nbytes = pl.nbytes
+        return Readback(self, pl.shape, nbytes, "ocean_spray_step_async",
+                        lambda dst, req: self.lib.ocean_spray_step_async(
+                            self._h, tile, iterations, substeps, sp.ctypes.data, pl.ctypes.data, capacity,
+                            em.ctypes.data if em is not None else None, emit_capacity, dst, nbytes, req), buf)
+
+    def spray_step_device(self, out_ptr: int, spray, pool_ptr: int, capacity: int, emitters_ptr: int = 0,
+                          emit_capacity: int = 0, substeps: int = 1, iterations: int = 2, tile: int = 0) -> None:
+        """The device-pointer form (ocean_spray_step_device): pool and out float[capacity + 1][8], emitters
+        float[emit_capacity + 1][8] or 0, on this context's device, 16-B aligned; async on the context's stream, after
+        the queued steps.  `out_ptr` overlaps neither input: ping-pong two pools.  `spray` is a host array."""
+        sp = np.ascontiguousarray(spray, np.float32).reshape(-1)
+        if sp.shape[0] != SPRAY_FLOATS:
+            raise ValueError(f"spray must be float32[{SPRAY_FLOATS}] (spray_params), got {sp.shape}")
+        _check(self.lib.ocean_spray_step_device(self._h, tile, iterations, substeps, sp.ctypes.data,
+                                                ctypes.c_void_p(pool_ptr), capacity,
+                                                ctypes.c_void_p(emitters_ptr) if emitters_ptr else None, emit_capacity,
+                                                ctypes.c_void_p(out_ptr), (int(capacity) + 1) * 32),
+               "ocean_spray_step_device")
+
+    @staticmethod
     def _body_args(hull, bodies):
         h = np.ascontiguousarray(hull, np.float32)
         b = np.ascontiguousarray(bodies, np.float32)
@@ -1052,6 +1145,10 @@ class Readback:
         """A completed whitecaps_async request parsed: (T, records float32[W][8]) (waits if still pending)."""
         return OceanContext.parse_whitecaps(self.view())
 
+    def spray(self):
+        """A completed spray_step_async request parsed: (T, M, records float32[W][8]) (waits if still pending)."""
+        return OceanContext.parse_spray(self.view())
+
     def release(self) -> None:
         if self._h:
             self.lib.ocean_readback_release(self._h)
@@ -1385,6 +1482,14 @@ class WaterBody:
         as (T, float32[W][8]): spawn points for spray and foam particles with the water's velocity beside them
         (`velocity=True`).  The reference has the foam only as a shading term (Water.shader:343).  Blocking."""
         return self.ctx.whitecaps(threshold, x0, z0, dx, dz, nx, ny, capacity, lod, tile)
+
+    def Spray(self, spray, pool, emitters=None, substeps: int = 1, iterations: int = 2, tile: int = 0):
+        """Spray particles (OceanContext.spray_step): the pool float32[capacity + 1][8] and one fresh particle per
+        record of the whitecap list `emitters` take `substeps` substeps against this frame's water; those that fall
+        back into the sea or outlive `life` are retired -> (T, M, float32[W][8]) and the stepped pool itself, which
+        is the next call's `pool`.  The reference has no particles.  Blocking."""
+        out = self.ctx.spray_step(spray, pool, emitters, substeps, iterations, tile)
+        return OceanContext.parse_spray(out) + (out,)
 
     def SurfaceBounds(self, tile: int = 0) -> np.ndarray:
         """(min xyz, max xyz) float32[2][3] of the cascade-summed displacement, from the per-cascade records
