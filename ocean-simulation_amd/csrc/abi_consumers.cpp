@@ -348,18 +348,25 @@ struct BodyStep : BodyBuoyancy {
 // (the caller has entered: OCEAN_ENTER)
 int ensure_bounds(ocean_ctx* ctx, int tile, const float** records) {
     const size_t rec_floats = ctx->units() * 8;
-    if (!ctx->bounds_dev)
-        OCEAN_HIP(hipMalloc((void**)&ctx->bounds_dev, (rec_floats + ocean::bounds_partial_floats(ctx->C)) * sizeof(float)));
-    float* rec = ctx->bounds_dev + (size_t)tile * ctx->C * 8;
+    if (int r = ctx->bounds_dev.ensure((rec_floats + ocean::bounds_partial_floats(ctx->C)) * sizeof(float))) return r;
+    float* base = static_cast<float*>(ctx->bounds_dev.ptr);
+    float* rec = base + (size_t)tile * ctx->C * 8;
     *records = rec;
     if (ctx->bounds_valid[tile] && !ctx->disp_exposed) return OCEAN_OK;
     const ocean::DevView v = ctx->view();
     if (int r = timed(ctx, 2,
-                      [&] { return ocean::launch_surface_bounds(v, tile, ctx->bounds_dev + rec_floats, rec, ctx->stream); },
+                      [&] { return ocean::launch_surface_bounds(v, tile, base + rec_floats, rec, ctx->stream); },
                       "surface_bounds"))
         return r;
     ctx->bounds_valid[tile] = !ctx->disp_exposed;
     return OCEAN_OK;
+}
+
+// What a kernel with the air skip takes as `bounds`: those records, or null where OCEAN_RAY_BOUNDS=0 turns the skip
+// (and the bounds launches) off.
+int air_skip_bounds(ocean_ctx* ctx, int tile, const float** bounds) {
+    *bounds = nullptr;
+    return ctx->opt.ray_bounds ? ensure_bounds(ctx, tile, bounds) : OCEAN_OK;
 }
 
 // Ray casts: rays float[count][8] -> records float[count][8]; the staged forms take at most OCEAN_RAY_MAX_RAYS.
@@ -391,9 +398,8 @@ struct RayCast {
     size_t out_bytes() const { return (size_t)count * 8 * 4; }
     const char* lacks() const { return count == 0 ? "rays" : nullptr; }
     int launch(const float* const* in, float* d_out) const {
-        const float* bounds = nullptr;
-        if (ctx->opt.ray_bounds)
-            if (int r = ensure_bounds(ctx, tile, &bounds)) return r;
+        const float* bounds;
+        if (int r = air_skip_bounds(ctx, tile, &bounds)) return r;
         const ocean::DevView v = ctx->view();
         return timed(ctx, 2,
                      [&] {
@@ -436,12 +442,12 @@ struct Whitecaps {
     size_t out_bytes() const { return bytes; }
     const char* lacks() const { return nullptr; }
     int launch(const float* const*, float* d_out) const {
-        if (!ctx->whitecap_dev) OCEAN_HIP(hipMalloc(&ctx->whitecap_dev, ocean::whitecap_scratch_bytes()));
+        if (int r = ctx->whitecap_dev.ensure(ocean::whitecap_scratch_bytes())) return r;
         const ocean::DevView v = ctx->view();
         return timed(ctx, 2,
                      [&] {
                          return ocean::launch_whitecaps(v, ctx->vel, tile, lod, threshold, x0, z0, dx, dz, nx, ny, capacity,
-                                                        ctx->whitecap_dev, d_out, ctx->stream);
+                                                        ctx->whitecap_dev.ptr, d_out, ctx->stream);
                      },
                      "whitecaps");
     }
@@ -504,9 +510,8 @@ struct Camera {
     size_t out_bytes() const { return bytes; }
     const char* lacks() const { return nullptr; }
     int launch(const float* const*, float* d_out) const {
-        const float* bounds = nullptr;
-        if (ctx->opt.ray_bounds)
-            if (int r = ensure_bounds(ctx, tile, &bounds)) return r;
+        const float* bounds;
+        if (int r = air_skip_bounds(ctx, tile, &bounds)) return r;
         ocean::CameraRays cam;
         ocean::CameraMaterial mat = {};
         std::copy(camera, camera + OCEAN_CAMERA_FLOATS, cam.c);
@@ -582,24 +587,16 @@ struct Spray {
     size_t out_bytes() const { return bytes; }
     const char* lacks() const { return nullptr; }
     int launch(const float* const* in, float* d_out) const {
-        const size_t need = ocean::spray_scratch_bytes(capacity, emit_capacity);
-        if (need > ctx->spray_dev_bytes) {  // (hipFree waits for the launches that still read the old block)
-            if (ctx->spray_dev) OCEAN_HIP(hipFree(ctx->spray_dev));
-            ctx->spray_dev = nullptr;
-            ctx->spray_dev_bytes = 0;
-            OCEAN_HIP(hipMalloc(&ctx->spray_dev, need));
-            ctx->spray_dev_bytes = need;
-        }
-        const float* bounds = nullptr;
-        if (ctx->opt.ray_bounds)
-            if (int r = ensure_bounds(ctx, tile, &bounds)) return r;
+        if (int r = ctx->spray_dev.ensure(ocean::spray_scratch_bytes(capacity, emit_capacity))) return r;
+        const float* bounds;
+        if (int r = air_skip_bounds(ctx, tile, &bounds)) return r;
         ocean::SprayParams sp;
         std::copy(spray, spray + OCEAN_SPRAY_FLOATS, sp.p);
         const ocean::DevView v = ctx->view();
         return timed(ctx, 2,
                      [&] {
                          return ocean::launch_spray_step(v, tile, iterations, substeps, sp, bounds, in[0], capacity,
-                                                         emitters ? in[1] : nullptr, emit_capacity, ctx->spray_dev, d_out,
+                                                         emitters ? in[1] : nullptr, emit_capacity, ctx->spray_dev.ptr, d_out,
                                                          ctx->stream);
                      },
                      "spray_step");

@@ -71,7 +71,7 @@ namespace {
 void free_all(ocean_ctx* c) {
     void* ptrs[] = {c->noise, c->h0, c->h0k, c->waves, c->plane[0], c->disp, c->deriv,
                     c->turb,  c->normal, c->tw,    c->casc,     c->tplane, c->foam, c->deriv_mips, c->turb_mips,
-                    c->qside, c->vel, c->vplane, c->prune_dev, c->bounds_dev, c->whitecap_dev, c->spray_dev,
+                    c->qside, c->vel, c->vplane, c->prune_dev, c->bounds_dev.ptr, c->whitecap_dev.ptr, c->spray_dev.ptr,
                     c->stage_block, c->atm.block};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);

@@ -30,6 +30,23 @@ int hip_fail(hipError_t e, const char* what);
         if (_e != hipSuccess) return hip_fail(_e, #call); \
     } while (0)
 
+// A block of device memory that a context owns and one of its entries sizes: allocated by the first call that
+// needs it, grown by free-then-malloc only when a call asks for more than it holds (hipFree waits for the launches
+// that still read the old block), never shrunk, and freed by ocean_destroy.  (the caller has entered: OCEAN_ENTER)
+struct DeviceScratch {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    int ensure(size_t need) {
+        if (need <= bytes) return OCEAN_OK;
+        if (ptr) OCEAN_HIP(hipFree(ptr));
+        ptr = nullptr;
+        bytes = 0;
+        OCEAN_HIP(hipMalloc(&ptr, need));
+        bytes = need;
+        return OCEAN_OK;
+    }
+};
+
 struct TimedLaunch {
     int kind;
     hipEvent_t a, b;
@@ -189,16 +206,15 @@ struct ocean_ctx {
     // then pass 1's partials.  bounds_valid[t]: tile t's records match DISP (dropped by every entry that writes
     // DISP).  disp_exposed: ocean_get_device_ptr has handed DISP out, a foreign writer cannot be seen, so
     // nothing is cached any more and every use recomputes.
-    float* bounds_dev = nullptr;
+    DeviceScratch bounds_dev;
     std::vector<bool> bounds_valid;
     bool disp_exposed = false;
     // whitecap emitters (whitecaps.hip): the ballot masks and per-chunk counts of the largest grid, allocated by the
     // first ocean_whitecaps* call and reused by every later one
-    void* whitecap_dev = nullptr;
+    DeviceScratch whitecap_dev;
     // spray particles (spray.hip): the stepped records, ballot masks and per-chunk counts of the largest call so far,
     // allocated by the first ocean_spray_step* call and grown when a call needs more
-    void* spray_dev = nullptr;
-    size_t spray_dev_bytes = 0;
+    DeviceScratch spray_dev;
     // the staging block of the blocking host forms (run_staged_impl): inputs, then the output; grown on demand
     void* stage_block = nullptr;
     size_t stage_block_bytes = 0;

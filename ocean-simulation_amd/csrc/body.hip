@@ -44,9 +44,7 @@
 // The probe loop and the butterfly are one device function, body_wrench<W, DRAG>, that all three kernels call:
 // k_body_buoyancy<W> with DRAG = false, which compiles the VEL taps, the drag terms, their accumulators and their
 // shuffles out, the other two with DRAG = true.  The three launchers share one map from P to a compile-time W
-// (with_segment_width) and one grid size (body_groups).
-#include <type_traits>
-
+// (with_segment_width, over with_constant of ocean_internal.h) and one grid size (body_groups).
 #include "ocean_internal.h"
 #include "sample_filter.h"
 #include "spectrum_math.h"
@@ -329,15 +327,7 @@ __global__ __launch_bounds__(256) void k_body_step(DevView v, const float4* __re
 // f(std::integral_constant<int, W>) for W = body_segment_width(probes): the one place that names the seven widths.
 template <class F>
 void with_segment_width(int probes, F&& f) {
-    switch (body_segment_width(probes)) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        case 8: f(std::integral_constant<int, 8>{}); break;
-        case 16: f(std::integral_constant<int, 16>{}); break;
-        case 32: f(std::integral_constant<int, 32>{}); break;
-        default: f(std::integral_constant<int, 64>{}); break;
-    }
+    (void)with_constant<1, 2, 4, 8, 16, 32, 64>(body_segment_width(probes), f);  // it returns one of the seven
 }
 
 // Workgroups of 256 / w bodies each for `count` bodies.

@@ -41,7 +41,8 @@ __global__ __launch_bounds__(256) void k_surface_grid(DevView v, int tile, int i
     const unsigned by = blockIdx.x / tiles_x, bx = blockIdx.x - by * tiles_x;
     const int i = (int)(bx * TW + threadIdx.x % TW), j = (int)(by * TH + threadIdx.x / TW);
     if (i >= nx || j >= ny) return;
-    const float qx = x0 + (float)i * dx, qz = z0 + (float)j * dz;
+    const float2 q = grid_node(i, j, x0, z0, dx, dz);
+    const float qx = q.x, qz = q.y;
     const size_t k = (size_t)j * nx + i;
     if (MODE == OCEAN_GRID_VERTICES) {
         const WorldSample s = sample_cascades(v, tile, qx, qz, lod);
@@ -61,24 +62,6 @@ __global__ __launch_bounds__(256) void k_surface_grid(DevView v, int tile, int i
     o[1] = rec.nf;
 }
 
-template <int TW>
-void launch_tw(const DevView& v, int tile, int mode, int iterations, float lod, float x0, float z0, float dx,
-               float dz, int nx, int ny, float* out, hipStream_t s) {
-    constexpr int TH = 256 / TW;
-    const unsigned tiles_x = (unsigned)((nx + TW - 1) / TW), tiles_y = (unsigned)((ny + TH - 1) / TH);
-    // nx * ny <= OCEAN_GRID_MAX_NODES = 2^22: at most 2^22 / TH + tiles_y < 2^31 tiles
-    const dim3 g(tiles_x * tiles_y), b(256);
-    if (mode == OCEAN_GRID_VERTICES)
-        launch(k_surface_grid<TW, OCEAN_GRID_VERTICES>, g, b, 0, s, v, tile, iterations, lod, x0, z0, dx, dz, nx, ny,
-               tiles_x, out);
-    else if (mode == OCEAN_GRID_SURFACE)
-        launch(k_surface_grid<TW, OCEAN_GRID_SURFACE>, g, b, 0, s, v, tile, iterations, lod, x0, z0, dx, dz, nx, ny,
-               tiles_x, out);
-    else
-        launch(k_surface_grid<TW, OCEAN_GRID_HEIGHTFIELD>, g, b, 0, s, v, tile, iterations, lod, x0, z0, dx, dz, nx,
-               ny, tiles_x, out);
-}
-
 }  // namespace
 
 bool grid_tile_supported(int tile_w) { return tile_w == 64 || tile_w == 32 || tile_w == 16; }
@@ -88,12 +71,15 @@ hipError_t launch_surface_grid(const DevView& v, int tile, int mode, int iterati
     if (nx <= 0 || ny <= 0) return hipSuccess;
     if (mode < OCEAN_GRID_VERTICES || mode > OCEAN_GRID_HEIGHTFIELD || !grid_tile_supported(tile_w))
         return hipErrorInvalidValue;
-    if (tile_w == 64)
-        launch_tw<64>(v, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out, s);
-    else if (tile_w == 32)
-        launch_tw<32>(v, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out, s);
-    else
-        launch_tw<16>(v, tile, mode, iterations, lod, x0, z0, dx, dz, nx, ny, out, s);
+    (void)with_constant<64, 32, 16>(tile_w, [&](auto tw) {  // both values were checked above: one of each matches
+        (void)with_constant<OCEAN_GRID_VERTICES, OCEAN_GRID_SURFACE, OCEAN_GRID_HEIGHTFIELD>(mode, [&](auto m) {
+            constexpr int TW = decltype(tw)::value, TH = 256 / TW;
+            const unsigned tiles_x = (unsigned)((nx + TW - 1) / TW), tiles_y = (unsigned)((ny + TH - 1) / TH);
+            // nx * ny <= OCEAN_GRID_MAX_NODES = 2^22: at most 2^22 / TH + tiles_y < 2^31 tiles
+            launch(k_surface_grid<TW, decltype(m)::value>, dim3(tiles_x * tiles_y), dim3(256), 0, s, v, tile, iterations,
+                   lod, x0, z0, dx, dz, nx, ny, tiles_x, out);
+        });
+    });
     return hipGetLastError();
 }
 

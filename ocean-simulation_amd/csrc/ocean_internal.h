@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "frame_plan.h"  // pass_*_supported: which sizes each pass family is built for
 #include "ocean/ocean.h"
 
@@ -34,8 +36,15 @@ inline void launch(F kernel, dim3 grid, dim3 block, uint32_t shmem, hipStream_t 
     if (e) e->launched = true;
 }
 
-constexpr int kMaxCascades = 5;  // the consumer shader caps cascades at 5 (Water.shader:139)
+// From a runtime value to a template argument: f(std::integral_constant<int, V>{}) for the V among Vs that equals
+// `value`; false, and no call, when none does.  A launcher states its kernel's argument list once, in a generic
+// lambda, and the kernels instantiated are those of Vs (grid.hip, view.hip, body.hip).
+template <int... Vs, class F>
+inline bool with_constant(int value, F&& f) {
+    return ((value == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
 
+constexpr int kMaxCascades = 5;  // the consumer shader caps cascades at 5 (Water.shader:139)
 
 // Device-side view of one context: every texture of every (tile, cascade) unit.
 // unit u = tile * C + cascade; each texture is [u][y][x] (see include/ocean/ocean.h).
@@ -249,8 +258,9 @@ hipError_t launch_camera_sky(const DevView& v, int tile, int iterations, int ste
 size_t whitecap_scratch_bytes();
 hipError_t launch_whitecaps(const DevView& v, const float4* vel, int tile, float lod, float threshold, float x0, float z0,
                             float dx, float dz, int nx, int ny, int capacity, void* scratch, float* out, hipStream_t s);
-// whitecaps.hip: the scan between a compaction's count and emit launches, one workgroup: counts[0 .. items) become
-// exclusive offsets in place and `out` gets the header record (T, min(T, capacity), third, capacity, 0, 0, 0, 0),
+
+// compact.hip: the scan between a compaction's count and emit launches (compact.h), one workgroup: counts[0 .. items)
+// become exclusive offsets in place and `out` gets the header record (T, min(T, capacity), third, capacity, 0, 0, 0, 0),
 // third = *nodes_dev when that is not null, else nodes.
 hipError_t launch_compact_scan(unsigned* counts, unsigned items, unsigned nodes, const unsigned* nodes_dev,
                                unsigned capacity, float* out, hipStream_t s);

@@ -209,6 +209,13 @@ __device__ __forceinline__ SurfaceRecord surface_record(const WorldSample& s, fl
     return rec;
 }
 
+// Node (i, j) of a regular grid (ocean_surface_grid, ocean_whitecaps): (qx, qz), one fp32 multiply and one fp32
+// add each (ocean.h).  I: int or unsigned, i and j below 2^22, so the conversion is exact either way.
+template <class I>
+__device__ __forceinline__ float2 grid_node(I i, I j, float x0, float z0, float dx, float dz) {
+    return make_float2(x0 + (float)i * dx, z0 + (float)j * dz);
+}
+
 // GetWaterHeight's texel index (WaterBody.cs:195-209), OCEAN_QUERY_REFERENCE: InverseLerp(-N/2, N/2, .) is
 // saturate((v - a) / (b - a)).
 __device__ __forceinline__ int reference_texel(float w, int n) {

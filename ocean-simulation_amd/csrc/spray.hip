@@ -6,20 +6,16 @@
 //
 // Candidates j = 0 .. M - 1, M = n + e known only on the device (the two headers are read there, clamped to the
 // capacities the host passed), so the launch grid follows capacity + emit_capacity and lanes at or beyond M
-// contribute nothing.  The compaction is the whitecaps' (whitecaps.hip): three launches, order-preserving, no
-// atomics, no workgroup that waits for another, so the pool does not depend on the launch grid or on scheduling.
+// contribute nothing.  The compaction is the one compact.h describes, the predicate being `alive`:
 //
-//   step   item = a chunk of 256 consecutive candidates (4 waves x 64 lanes, one candidate per lane).  A lane loads
-//          its candidate (two 16-B loads: a pool record, or an emitter record turned into a fresh particle), takes
-//          up to S substeps, stopping at the first it does not survive, and stores the stepped record to the
-//          context's scratch if it is still alive.  The surface height under a particle is OCEAN_QUERY_SURFACE's,
-//          from surface_fixed_point / sample_disp of sample_filter.h: the bits ocean_query_surface gives for that
-//          point.  The wave's ballot of `alive` goes to masks[j / 64], the chunk's popcount to counts[item] (the
-//          four waves meet in LDS, one barrier per item), and the workgroup of item 0 leaves M beside them.
-//   scan   k_whitecap_scan of whitecaps.hip (launch_compact_scan), the header's third field read from that M.
-//   emit   item = the same chunk.  rank as in k_whitecap_emit; a survivor with rank < capacity copies its record
-//          from scratch to record 1 + rank.  A chunk without a survivor is skipped, and at the first chunk whose
-//          offset reaches the capacity the workgroup is done.
+//   step   the count launch.  A lane loads its candidate (two 16-B loads: a pool record, or an emitter record turned
+//          into a fresh particle), takes up to S substeps, stopping at the first it does not survive, and stores the
+//          stepped record to the context's scratch (the compaction's payload, 32 B per candidate) if it is still
+//          alive.  The surface height under a particle is OCEAN_QUERY_SURFACE's, from surface_fixed_point /
+//          sample_disp of sample_filter.h: the bits ocean_query_surface gives for that point.  The workgroup of item
+//          0 leaves M beside the counts.
+//   scan   the header's third field is read from that M.
+//   emit   a survivor with rank < capacity copies its record from scratch to record 1 + rank.
 //
 // Air skip (ray_march.h has H and its proof): a particle with p'.y > H over a finite (p'.x, p'.z) is above every
 // wave, so the first clause of `alive` is true without a sample (over a NaN or infinite x or z the height is a NaN,
@@ -27,8 +23,9 @@
 // and without the bound; the number of samples is not.  A particle whose age has run out, or whose height is a
 // NaN, is retired by the other clause or by the compare itself, and is not sampled either.
 //
-// step and emit walk their items with launch_items under OCEAN_MAX_GROUPS.  A gather through L1 / L2 / Infinity
-// Cache, K + 1 dependent round trips per substep below H: latency bound, no roofline claimed.  No inline assembly.
+// A gather through L1 / L2 / Infinity Cache, K + 1 dependent round trips per substep below H: latency bound, no
+// roofline claimed.  No inline assembly.
+#include "compact.h"
 #include "ocean_internal.h"
 #include "ray_march.h"
 #include "sample_filter.h"
@@ -36,17 +33,15 @@
 namespace ocean {
 namespace {
 
-constexpr int kThreads = 256, kWaves = kThreads / 64;  // a chunk = one candidate per lane
-
-__global__ __launch_bounds__(kThreads) void k_spray_step(DevView v, int tile, int iterations, int substeps, SprayParams sp,
-                                                         const float* __restrict__ bounds,
-                                                         const float4* __restrict__ pool, unsigned capacity,
-                                                         const float4* __restrict__ emitters, unsigned emit_capacity,
-                                                         unsigned items, float4* __restrict__ stepped,
-                                                         unsigned long long* __restrict__ masks,
-                                                         unsigned* __restrict__ counts, unsigned* __restrict__ total) {
-    __shared__ unsigned part[2][kWaves];  // as k_whitecap_count: two buffers taken in turn, one barrier per item
-    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+__global__ __launch_bounds__(kChunkThreads) void k_spray_step(DevView v, int tile, int iterations, int substeps,
+                                                              SprayParams sp, const float* __restrict__ bounds,
+                                                              const float4* __restrict__ pool, unsigned capacity,
+                                                              const float4* __restrict__ emitters,
+                                                              unsigned emit_capacity, unsigned items,
+                                                              float4* __restrict__ stepped,
+                                                              unsigned long long* __restrict__ masks,
+                                                              unsigned* __restrict__ counts,
+                                                              unsigned* __restrict__ total) {
     // the headers' W fields, clamped: the guard against a header this library did not write
     const unsigned n = min(__float_as_uint(pool[0].y), capacity);
     const unsigned e = emitters ? min(__float_as_uint(emitters[0].y), emit_capacity) : 0u;
@@ -56,8 +51,8 @@ __global__ __launch_bounds__(kThreads) void k_spray_step(DevView v, int tile, in
     const bool skip = bounds != nullptr;
     const float H = skip ? air_height(bounds, v.C) : 0.0f;
     unsigned turn = 0;
-    for (unsigned item = blockIdx.x; item < items; item += gridDim.x, turn ^= 1u) {
-        const unsigned j = item * kThreads + threadIdx.x;
+    for (unsigned item = blockIdx.x; item < items; item += gridDim.x) {
+        const unsigned j = item * kChunkThreads + threadIdx.x;
         bool alive = false;
         if (j < m) {
             float px, py, pz, a, vx, vy, vz, tag;
@@ -90,70 +85,62 @@ __global__ __launch_bounds__(kThreads) void k_spray_step(DevView v, int tile, in
                 stepped[2 * (size_t)j + 1] = make_float4(vx, vy, vz, tag);
             }
         }
-        const unsigned long long mask = __ballot(alive);
-        if (lane == 0) {
-            masks[(size_t)item * kWaves + wave] = mask;  // word j / 64; zero past the last candidate
-            part[turn][wave] = (unsigned)__popcll(mask);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            counts[item] = (part[turn][0] + part[turn][1]) + (part[turn][2] + part[turn][3]);
-            if (item == 0) *total = m;
-        }
+        compact_count(alive, item, turn, masks, counts);
+        if (threadIdx.x == 0 && item == 0) *total = m;
     }
 }
 
-__global__ __launch_bounds__(kThreads) void k_spray_emit(unsigned items, unsigned capacity,
-                                                         const unsigned long long* __restrict__ masks,
-                                                         const unsigned* __restrict__ offsets,
-                                                         const float4* __restrict__ stepped,
-                                                         float4* __restrict__ records) {
-    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+__global__ __launch_bounds__(kChunkThreads) void k_spray_emit(unsigned items, unsigned capacity,
+                                                              const unsigned long long* __restrict__ masks,
+                                                              const unsigned* __restrict__ offsets,
+                                                              const float4* __restrict__ stepped,
+                                                              float4* __restrict__ records) {
     for (unsigned item = blockIdx.x; item < items; item += gridDim.x) {
-        unsigned rank = offsets[item];
-        if (rank >= capacity) break;  // so is every later chunk's
-        const unsigned long long* cm = masks + (size_t)item * kWaves;
-        for (unsigned w = 0; w < wave; ++w) rank += (unsigned)__popcll(cm[w]);
-        const unsigned long long m = cm[wave];
-        if (m == 0 || rank >= capacity) continue;  // wave-uniform
-        rank += (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-        if (!((m >> lane) & 1ull) || rank >= capacity) continue;
-        const size_t j = (size_t)item * kThreads + threadIdx.x;
+        unsigned rank;
+        bool done;
+        if (!compact_rank(item, offsets, masks, capacity, rank, done)) {
+            if (done) break;
+            continue;
+        }
+        const size_t j = (size_t)item * kChunkThreads + threadIdx.x;
         float4* o = records + 2 * (size_t)rank;
         o[0] = stepped[2 * j];
         o[1] = stepped[2 * j + 1];
     }
 }
 
-unsigned spray_items(size_t candidates) { return (unsigned)((candidates + kThreads - 1) / kThreads); }
+// The chunks and the scratch of a call: the stepped records (32 B per candidate), the masks, the counts, M.
+unsigned spray_items(int capacity, int emit_capacity) {
+    return (unsigned)(((size_t)capacity + (size_t)emit_capacity + kChunkThreads - 1) / kChunkThreads);
+}
+CompactScratch spray_scratch(int capacity, int emit_capacity) {
+    return compact_scratch(spray_items(capacity, emit_capacity), 32, true);
+}
 
 }  // namespace
 
-size_t spray_scratch_bytes(int capacity, int emit_capacity) {
-    const size_t items = spray_items((size_t)capacity + (size_t)emit_capacity);
-    // the stepped records, the masks, the counts (to a multiple of 16 B), M
-    return items * kThreads * 32 + items * kWaves * sizeof(unsigned long long) + ((items + 3) & ~(size_t)3) * sizeof(unsigned) + 16;
-}
+size_t spray_scratch_bytes(int capacity, int emit_capacity) { return spray_scratch(capacity, emit_capacity).bytes; }
 
 hipError_t launch_spray_step(const DevView& v, int tile, int iterations, int substeps, const SprayParams& sp,
                              const float* bounds, const float* pool, int capacity, const float* emitters,
                              int emit_capacity, void* scratch, float* out, hipStream_t s) {
     if (capacity <= 0 || emit_capacity < 0 || substeps <= 0 || (emitters == nullptr) != (emit_capacity == 0))
         return hipErrorInvalidValue;
-    const unsigned items = spray_items((size_t)capacity + (size_t)emit_capacity);
-    float4* stepped = static_cast<float4*>(scratch);
-    unsigned long long* masks = reinterpret_cast<unsigned long long*>(stepped + 2 * (size_t)items * kThreads);
-    unsigned* counts = reinterpret_cast<unsigned*>(masks + (size_t)items * kWaves);
-    unsigned* total = counts + ((items + 3) & ~3u);
+    const unsigned items = spray_items(capacity, emit_capacity);
+    const CompactScratch at = spray_scratch(capacity, emit_capacity);
+    float4* stepped = scratch_at<float4>(scratch, at.payload);
+    unsigned long long* masks = scratch_at<unsigned long long>(scratch, at.masks);
+    unsigned* counts = scratch_at<unsigned>(scratch, at.counts);
+    unsigned* total = scratch_at<unsigned>(scratch, at.total);
     const Items it{(int)items, v.max_groups};
-    hipError_t e = launch_items(k_spray_step, kThreads, it, s, v, tile, iterations, substeps, sp, bounds,
+    hipError_t e = launch_items(k_spray_step, kChunkThreads, it, s, v, tile, iterations, substeps, sp, bounds,
                                 reinterpret_cast<const float4*>(pool), (unsigned)capacity,
                                 reinterpret_cast<const float4*>(emitters), (unsigned)emit_capacity, items, stepped, masks,
                                 counts, total);
     if (e != hipSuccess) return e;
     e = launch_compact_scan(counts, items, 0u, total, (unsigned)capacity, out, s);
     if (e != hipSuccess) return e;
-    return launch_items(k_spray_emit, kThreads, it, s, items, (unsigned)capacity, (const unsigned long long*)masks,
+    return launch_items(k_spray_emit, kChunkThreads, it, s, items, (unsigned)capacity, (const unsigned long long*)masks,
                         (const unsigned*)counts, (const float4*)stepped, reinterpret_cast<float4*>(out) + 2);
 }
 

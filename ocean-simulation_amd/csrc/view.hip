@@ -203,15 +203,10 @@ __global__ __launch_bounds__(256) void k_camera_sky(DevView v, int tile, int ite
                                                   sun_size);
 }
 
-template <int MODE>
-void launch_mode(bool tiled, hipStream_t s, const DevView& v, int tile, int iterations, int steps, int refine,
-                 const float* bounds, const CameraRays& cam, const CameraMaterial& mt, int width, int height, float* out) {
-    if (tiled)
-        launch(k_camera<MODE, true>, dim3((width + 15) / 16, (height + 15) / 16), dim3(256), 0, s, v, tile, iterations,
-               steps, refine, bounds, cam, mt, width, height, out);
-    else
-        launch(k_camera<MODE, false>, dim3((unsigned)(((size_t)width * height + 255) / 256)), dim3(256), 0, s, v, tile,
-               iterations, steps, refine, bounds, cam, mt, width, height, out);
+// The launch grid of camera_pixel's two mappings: 16 x 16 pixel tiles, or 256 consecutive pixels per workgroup.
+dim3 camera_groups(int width, int height, bool tiled) {
+    if (tiled) return dim3((width + 15) / 16, (height + 15) / 16);
+    return dim3((unsigned)(((size_t)width * height + 255) / 256));
 }
 
 }  // namespace
@@ -220,20 +215,13 @@ hipError_t launch_camera(const DevView& v, int tile, int mode, int iterations, i
                          const CameraRays& cam, const CameraMaterial& mt, int width, int height, bool tiled, float* out,
                          hipStream_t s) {
     if (width < 1 || height < 1 || (size_t)width * height > (size_t)OCEAN_CAMERA_MAX_PIXELS) return hipErrorInvalidValue;
-    switch (mode) {
-        case OCEAN_CAMERA_HITS:
-            launch_mode<OCEAN_CAMERA_HITS>(tiled, s, v, tile, iterations, steps, refine, bounds, cam, mt, width, height, out);
-            break;
-        case OCEAN_CAMERA_RANGE:
-            launch_mode<OCEAN_CAMERA_RANGE>(tiled, s, v, tile, iterations, steps, refine, bounds, cam, mt, width, height, out);
-            break;
-        case OCEAN_CAMERA_COLOR:
-            launch_mode<OCEAN_CAMERA_COLOR>(tiled, s, v, tile, iterations, steps, refine, bounds, cam, mt, width, height, out);
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool known = with_constant<OCEAN_CAMERA_HITS, OCEAN_CAMERA_RANGE, OCEAN_CAMERA_COLOR>(mode, [&](auto m) {
+        (void)with_constant<0, 1>(tiled, [&](auto t) {  // a bool: one of the two matches
+            launch(k_camera<decltype(m)::value, decltype(t)::value != 0>, camera_groups(width, height, tiled), dim3(256), 0,
+                   s, v, tile, iterations, steps, refine, bounds, cam, mt, width, height, out);
+        });
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_camera_sky(const DevView& v, int tile, int iterations, int steps, int refine, const float* bounds,
@@ -241,12 +229,10 @@ hipError_t launch_camera_sky(const DevView& v, int tile, int iterations, int ste
                              int height, bool tiled, float* out, hipStream_t s) {
     if (width < 1 || height < 1 || (size_t)width * height > (size_t)OCEAN_CAMERA_MAX_PIXELS) return hipErrorInvalidValue;
     if (!sky.texels || sky.w < 2 || sky.h < 2) return hipErrorInvalidValue;
-    if (tiled)
-        launch(k_camera_sky<true>, dim3((width + 15) / 16, (height + 15) / 16), dim3(256), 0, s, v, tile, iterations, steps,
-               refine, bounds, cam, mt, sky, sun_size, width, height, out);
-    else
-        launch(k_camera_sky<false>, dim3((unsigned)(((size_t)width * height + 255) / 256)), dim3(256), 0, s, v, tile,
+    (void)with_constant<0, 1>(tiled, [&](auto t) {  // a bool: one of the two matches
+        launch(k_camera_sky<decltype(t)::value != 0>, camera_groups(width, height, tiled), dim3(256), 0, s, v, tile,
                iterations, steps, refine, bounds, cam, mt, sky, sun_size, width, height, out);
+    });
     return hipGetLastError();
 }
 

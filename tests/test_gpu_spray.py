@@ -185,6 +185,92 @@ def test_spray_placed_classes(C):
     ctx.close()
 
 
+def aged_candidates(ctx, m, e, iterations, tile=0):
+    """M = n + e candidates of the PLACED regime, 1.0 above the queried surface, that only age: the pool's n carry ages
+    on a fixed pattern either side of life - h (every seventh is old, and at M = 769 the whole of wave 4), the e spawned
+    ones are born at age 0.  -> (records float32[n][8], emitters float32[e + 1][8] or None, survives bool[M]), survives
+    being decided here, by the ages alone."""
+    h, life = PLACED[0], PLACED[6]
+    n = m - e
+    rng = np.random.default_rng(100 + m)
+    q = rng.uniform(-60.0, 60.0, (m, 2)).astype(f32)
+    y = ctx.query_surface(q, tile, iterations=iterations)[:, 0] + f32(1.0)
+    j = np.arange(n)
+    old = (j % 7 == 1) | ((m == 769) & (j >= 256) & (j < 320))
+    ages = np.array([step_ulps(f32(life - h), (1 + k % 3) if o else -(1 + k % 3)) for k, o in zip(j, old)], f32).reshape(n)
+    rec = np.zeros((n, 8), f32)
+    rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3] = q[:n, 0], y[:n], q[:n, 1], ages
+    rec[:, 7] = j
+    survives = np.concatenate([(ages + h).astype(f32) < life, np.ones(e, bool)])
+    assert (survives[:n] == ~old).all()
+    emitters = None
+    if e:
+        emitters = np.zeros((e + 1, 8), f32)
+        bits(emitters[0])[:4] = e
+        emitters[1:, 0], emitters[1:, 1], emitters[1:, 2], emitters[1:, 3] = q[n:, 0], y[n:], q[n:, 1], 0.5
+        emitters[1:, 7] = 1000 + np.arange(e)
+    return rec, emitters, survives
+
+
+# (M, e): e = 37 from M = 64 on, so that the seam between the pool and the spawned falls inside a wave; the last case is
+# 769 again with more spawned particles than the pattern retires, which the split of 37 cannot give (below)
+EDGE_CASES = [(1, 0), (63, 0), (64, 37), (65, 37), (255, 37), (256, 37), (257, 37), (769, 37), (769, 300)]
+# the cases whose survivors - 1 still admit the whole pool: the entry clamps a pool to its capacity, so a capacity
+# below n cannot be given all M candidates.  With e = 0 (M = 63) survivors - 1 < n always; at (769, 37) the empty wave
+# alone retires 64 > 37 particles.
+OVERFLOW_CASES = {(64, 37), (65, 37), (255, 37), (256, 37), (257, 37), (769, 300)}
+
+
+@pytest.mark.parametrize("M,e", EDGE_CASES)
+def test_spray_candidate_counts_at_the_wave_and_chunk_edges(M, e):
+    """M = n + e at the edges of a wave (64) and of a chunk (256), 769 being three chunks and one lane, with survivors
+    that are known in advance, neither none nor all, and in the 769 cases a whole wave without one.
+
+    With all M candidates: the capacity that holds all survivors T; the smallest capacity the pool admits, n; and, in
+    OVERFLOW_CASES, T - 1.  The last two overflow there (T > capacity, asserted), over two chunks at M = 257, where the
+    second chunk's offset has reached the capacity n, and over three at (769, 300), where T - 1 cuts inside the last
+    chunk.  At M = 63 and (769, 37) no capacity both admits the pool and overflows, so neither T - 1 nor 1 exists
+    with M candidates; at M = 1 all three capacities are 1.
+
+    A capacity below n (T - 1 outside OVERFLOW_CASES, and 1) is run with the pool it admits, the first `capacity` of
+    the n particles before the same spawned ones: capacity + e candidates, not M, compared like the others."""
+    ctx = make_ctx(N, SCENES[1])
+    K = 2
+    rec, emitters, survives = aged_candidates(ctx, M, e, K)
+    n, T = len(rec), int(survives.sum())
+    assert n + e == M
+    if M >= 2:
+        assert 0 < T < M
+    if M == 769:
+        assert any(not survives[w:w + 64].any() for w in range(0, M, 64))
+    overflows = (M, e) in OVERFLOW_CASES
+    assert (T - 1 >= n) == overflows
+    if (M, e) == (257, 37):
+        assert int(survives[:256].sum()) >= n  # capacity n: the workgroup is done at the second chunk
+    if (M, e) == (769, 300):
+        assert int(survives[:512].sum()) < T - 1  # capacity T - 1: the cut is inside the third chunk
+    whole = {max(n, T): False, n: overflows}
+    if overflows:
+        whole[T - 1] = True
+    for capacity, over in sorted(whole.items(), reverse=True):
+        assert (T > capacity) == over
+        pool = oh.OceanContext.spray_pool(rec, capacity)
+        head, got, died = restate_tagged(ctx, PLACED, pool, emitters, 1, K)
+        msg = f"M {M}, e {e}, capacity {capacity}"
+        assert ((died == 0) == survives).all(), msg
+        assert (head[0], head[1], head[2]) == (T, min(T, capacity), M), msg
+        assert_pool(ctx.spray_step(PLACED, pool, emitters, 1, K), head, got, msg)
+    for capacity in sorted({max(T - 1, 1), 1} - set(range(n, M + 1)), reverse=True):  # below n: the admitted pool
+        pool = oh.OceanContext.spray_pool(rec[:capacity], capacity)
+        want_t = int(survives[:capacity].sum()) + e
+        head, got, died = restate_tagged(ctx, PLACED, pool, emitters, 1, K)
+        msg = f"M {M}, e {e}, capacity {capacity} < n"
+        assert ((died == 0) == np.concatenate([survives[:capacity], survives[n:]])).all(), msg
+        assert (head[0], head[1], head[2]) == (want_t, min(want_t, capacity), capacity + e), msg
+        assert_pool(ctx.spray_step(PLACED, pool, emitters, 1, K), head, got, msg)
+    ctx.close()
+
+
 def random_pool(rng, n, capacity, life):
     rec = np.zeros((n, 8), f32)
     rec[:, 0] = rng.uniform(-50, 50, n)
@@ -343,28 +429,33 @@ def test_spray_header_clamp():
 
 
 def test_spray_does_not_depend_on_the_launch_grid():
-    """OCEAN_MAX_GROUPS=1: one workgroup walks the three chunks in order.  Bit-equal to the default grid's."""
+    """The launch is three chunks (capacity + emit_capacity = 768).  OCEAN_MAX_GROUPS=1: one workgroup walks them in
+    order; 2: one workgroup walks chunks 0 and 2 and the other chunk 1, so the turn of the count's LDS buffers is taken
+    with unequal shares.  Bit-equal to the default grid's."""
     cas = SCENES[3]
-    a, _ = _ctx_with_env({"OCEAN_MAX_GROUPS": "1"}, N, cas, flags=oh.F_VELOCITY)
     b, _ = _ctx_with_env({}, N, cas, flags=oh.F_VELOCITY)
-    for c in (a, b):
-        for t in (0.5, 1.0):
-            c.step(t)
+    for t in (0.5, 1.0):
+        b.step(t)
     rng = np.random.default_rng(4)
-    pool = random_pool(rng, 400, 710, 1.5)
+    pool = random_pool(rng, 400, 468, 1.5)
     emitters = emitter_list(b, 300)
-    for S in (1, 3):
-        oa, ob = device_step(a, PHYSICS, pool, emitters, S, 2), device_step(b, PHYSICS, pool, emitters, S, 2)
-        np.testing.assert_array_equal(bits(oa), bits(ob))
-        head, rec, _ = restate_tagged(b, PHYSICS, pool, emitters, S, 2)
-        assert_pool(oa, head, rec, f"one workgroup, S {S}")
-        assert 0 < head[0] < 700
-    # ... and with a capacity that overflows (the emit kernel's early exit)
-    small = oh.OceanContext.spray_pool(pool[1:61], 60)
-    np.testing.assert_array_equal(bits(device_step(a, HIGH, small, emitters, 2, 2)),
-                                  bits(device_step(b, HIGH, small, emitters, 2, 2)))
-    assert a.kernel_name(2) == b.kernel_name(2) and "k_spray_emit" in a.kernel_name(2)
-    a.close()
+    assert (len(pool) - 1 + len(emitters) - 1 + 255) // 256 == 3
+    for groups in ("1", "2"):
+        a, _ = _ctx_with_env({"OCEAN_MAX_GROUPS": groups}, N, cas, flags=oh.F_VELOCITY)
+        for t in (0.5, 1.0):
+            a.step(t)
+        for S in (1, 3):
+            oa, ob = device_step(a, PHYSICS, pool, emitters, S, 2), device_step(b, PHYSICS, pool, emitters, S, 2)
+            np.testing.assert_array_equal(bits(oa), bits(ob))
+            head, rec, _ = restate_tagged(b, PHYSICS, pool, emitters, S, 2)
+            assert_pool(oa, head, rec, f"{groups} workgroups, S {S}")
+            assert 0 < head[0] < 700
+        # ... and with a capacity that overflows (the emit kernel's early exit)
+        small = oh.OceanContext.spray_pool(pool[1:61], 60)
+        np.testing.assert_array_equal(bits(device_step(a, HIGH, small, emitters, 2, 2)),
+                                      bits(device_step(b, HIGH, small, emitters, 2, 2)))
+        assert a.kernel_name(2) == b.kernel_name(2) and "k_spray_emit" in a.kernel_name(2)
+        a.close()
     b.close()
 
 
