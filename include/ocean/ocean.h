@@ -85,7 +85,9 @@ extern "C" {
  *      ocean_sun_color.
  *      Added later within version 4 in the same way: OCEAN_SPRAY_FLOATS, OCEAN_SPRAY_MAX_PARTICLES,
  *      OCEAN_SPRAY_MAX_STAGED, OCEAN_SPRAY_MAX_SUBSTEPS, ocean_spray_step, ocean_spray_step_device,
- *      ocean_spray_step_async. */
+ *      ocean_spray_step_async.
+ *      Added later within version 4 in the same way: OCEAN_RAY_BODY, OCEAN_BODY_PAINT_FLOATS, ocean_camera_bodies,
+ *      ocean_camera_bodies_device, ocean_camera_bodies_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -1219,10 +1221,80 @@ int ocean_spray_step_async(ocean_ctx *ctx, int tile, int iterations, int substep
                            int capacity, const float *emitters, int emit_capacity, float *out, size_t bytes,
                            ocean_readback **req);
 
+/* Camera views that see the bodies: ocean_camera* with boxes in front of the water.  ocean_body_step_device keeps the
+ * hulls on the device and ocean_camera* makes pictures of the sea, but a lidar's range image shows no other vessel and
+ * a picture of four thousand floating boxes shows water alone: a host that wants them lands the HITS image at 32 B
+ * per pixel and the body states, intersects every pixel's ray with every box on the CPU and shades again.  Here the
+ * kernel tests a pixel's ray against the bodies and against the water and keeps the nearer of the two.
+ *
+ * ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out and bytes, the modes (HITS, RANGE,
+ * COLOR, COLOR | SKY_LUT), the three forms, their ordering and the slot rule of the async form are exactly
+ * ocean_camera*'s.  New:
+ *   box:    float[6] = (lo.x, lo.y, lo.z, hi.x, hi.y, hi.z): one box in the body frame, before the scale, shared by
+ *           all bodies as a hull is.  A host array in every form, passed to the kernel by value.
+ *   paint:  float[OCEAN_BODY_PAINT_FLOATS] = (A.r, A.g, A.b, ka): the bodies' albedo and the weight of the sky's
+ *           light on them.  A host array passed by value; read in the colour modes only, NULL allowed otherwise.
+ *   bodies, stride, count: record b starts at bodies + b * stride floats, and its first ten floats are (c, q, s) of an
+ *           ocean_body_buoyancy `bodies` record; the rest is not read.  stride in [10, 64]: 10 is a `bodies` array, 32
+ *           the `out` or `state` of ocean_body_step*, which the device form takes where it lies.  count in
+ *           [0, OCEAN_BODY_MAX_BODIES] in all forms.  count = 0 is valid in all forms, `bodies` may then be NULL, and
+ *           the image is ocean_camera's, bit for bit.  The device form takes a device pointer, 4-B aligned; the other
+ *           two a host buffer of (count - 1) * stride + 10 floats, staged and consumed before the call returns.
+ *
+ * All arithmetic is fp32, one rounding per operation in the order written (no fused multiply-add); sqrtf and / are
+ * correctly rounded.  Per pixel, o, d, t0, t1 and R_k are ocean_camera's.  Per body, with u = (qx, qy, qz) and rot as
+ * in ocean_body_step:
+ *       w  = o - c (componentwise);   ob = rot(-u, qw, w);   db = rot(-u, qw, d)
+ *       per axis i = x, y, z:   l = s_i * lo_i;  h = s_i * hi_i
+ *           if db_i == 0:  the body is not met unless fminf(l, h) <= ob_i <= fmaxf(l, h);  then n_i = -INFINITY, f_i = +INFINITY
+ *           else:          a = (l - ob_i) / db_i;  e = (h - ob_i) / db_i;  n_i = fminf(a, e);  f_i = fmaxf(a, e)
+ *       tn = fmaxf(fmaxf(n_x, n_y), n_z);   tf = fminf(fminf(f_x, f_y), f_z)
+ *       met  iff  tn <= tf  and  tf >= t0  and  tn <= t1          (with t1 < t0 no body is met)
+ *       te = fmaxf(tn, t0)
+ *       normal: if tn >= t0:  i = the first of x, y, z with n_i == tn;  nb = +0 but nb_i = (db_i > 0 ? -1 : +1);
+ *                             nw = rot(u, qw, nb)
+ *               else (the eye is inside the box):  nw = (-d.x, -d.y, -d.z)
+ * The pixel's body is the met body of smallest te, the lowest b on ties.  The pixel is a body pixel iff a body is met
+ * and R_k's status is MISS, or HIT with te < t* (t* = R_k[0]).  Water wins ties, and a SUBMERGED pixel stays
+ * SUBMERGED.  Every other pixel is exactly ocean_camera's.  A body pixel is
+ *   HITS:   (te, 0, 0, (float)OCEAN_RAY_BODY, nw.x, nw.y, nw.z, (float)b)
+ *   RANGE:  te
+ *   COLOR:  (A_c * (ka * amb_c + LC_c * fmaxf(dot(nw, L), 0)), (float)OCEAN_RAY_BODY), c = r, g, b, with
+ *           amb_c = sky(nw.y)_c of the two-colour sky, or SKY(nw)_c with OCEAN_CAMERA_SKY_LUT; dot, L and LC are the
+ *           camera's.
+ * Limits of the feature: bodies are not reflected in the water, cast no shadow and are not fogged under the water;
+ * the library does not inspect records, so a non-unit quaternion distorts the box as the formulas say, and non-finite
+ * values give unspecified numbers (never an access outside the textures or the records).
+ * Cull and early stop.  The kernel does not test every body per pixel: per 16 x 16-pixel tile it drops the bodies
+ * whose bounding sphere lies off a cone around the tile's rays or outside [t0, t1], with a derived margin, and it
+ * ends a pixel's march at the first node at or behind te that is above the water, where any t* exceeds te.  Every
+ * result bit is as defined above; only the time differs.  OCEAN_CAMERA_CULL=0 in the environment (read by
+ * ocean_create) makes every body a survivor of the cull; the air skip, the bounds launches and OCEAN_RAY_BOUNDS=0 are
+ * ocean_camera's.
+ *
+ * All three: OCEAN_E_INVALID_ARG, checked before any device call, for everything ocean_camera* refuses, a null `box`,
+ * a null `paint` in a colour mode, a `box` value or a value of a `paint` that is passed that is not finite, stride
+ * outside [10, 64], count outside [0, OCEAN_BODY_MAX_BODIES], a null `bodies` with count > 0 or a misaligned device
+ * `bodies`; then OCEAN_E_STATE and OCEAN_E_UNSUPPORTED as for the camera.  The launch counts as kind 2 of
+ * ocean_kernel_stats / ocean_kernel_name. */
+#define OCEAN_RAY_BODY 3
+#define OCEAN_BODY_PAINT_FLOATS 4
+int ocean_camera_bodies(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine, const float *camera,
+                        const float *material, int width, int height, const float *box, const float *paint,
+                        const float *bodies, int stride, int count, float *out, size_t bytes);
+int ocean_camera_bodies_device(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine,
+                               const float *camera, const float *material, int width, int height, const float *box,
+                               const float *paint, const float *bodies, int stride, int count, float *out, size_t bytes);
+int ocean_camera_bodies_async(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine,
+                              const float *camera, const float *material, int width, int height, const float *box,
+                              const float *paint, const float *bodies, int stride, int count, float *out, size_t bytes,
+                              ocean_readback **req);
+
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
  * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async /
  * ocean_body_buoyancy_async / ocean_query_velocity_async / ocean_raycast_async / ocean_body_dynamics_async /
- * ocean_whitecaps_async / ocean_camera_async / ocean_body_step_async / ocean_spray_step_async request records HIP
+ * ocean_whitecaps_async / ocean_camera_async / ocean_body_step_async / ocean_spray_step_async /
+ * ocean_camera_bodies_async request records HIP
  * timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it is off record only untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 

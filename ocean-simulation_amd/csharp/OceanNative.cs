@@ -223,6 +223,18 @@ namespace OceanHip
         public static extern OceanStatus ocean_camera_device(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, IntPtr output, UIntPtr bytes);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_camera_async(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, IntPtr dst, UIntPtr bytes, out IntPtr request);
+        // Camera views that see the bodies (added within ABI 4 in the same way): ocean_camera with boxes in front of the
+        // water.  box = 6 floats (lo, hi) in the body frame before the scale, shared by all bodies; paint = 4 floats (r, g, b,
+        // ka), null outside the colour modes; record b starts at bodies + b * stride floats, its first ten floats (c, q, s),
+        // stride in [10, 64] (32: the records of ocean_body_step), count in [0, BodyMaxBodies].  A body pixel has the
+        // status RayBody.
+        public const int RayBody = 3, BodyPaintFloats = 4;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_camera_bodies(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, [In] float[] box, [In] float[] paint, [In] float[] bodies, int stride, int count, [Out] float[] output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_camera_bodies_device(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, [In] float[] box, [In] float[] paint, IntPtr bodies, int stride, int count, IntPtr output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_camera_bodies_async(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, [In] float[] box, [In] float[] paint, [In] float[] bodies, int stride, int count, IntPtr dst, UIntPtr bytes, out IntPtr request);
         // The atmosphere (added within ABI 4 in the same way; ocean.h "The atmosphere"): the three look-up tables of
         // AtmosphereController.cs, owned by the context.  `parameters` = 32 floats (ocean.h names them); the six sizes all 0
         // select the reference's.  ocean_sky_update is the per-frame call; CameraColor | CameraSkyLut then shades the

@@ -340,6 +340,24 @@ namespace OceanHip
             return output;
         }
 
+        // Camera with the boxes of `bodies` in the picture (ocean.h ocean_camera_bodies): `bodies` holds records `stride`
+        // floats apart whose first ten floats are (c, q, s), the `bodies` of Buoyancy or the records StepBodies returns
+        // (stride 32); `box` = (lo, hi) of the one box they share, `paint` = (r, g, b, ka), null outside the colour modes.
+        // A body pixel has the status OceanNative.RayBody: its distance, its normal and the body's index in CameraHits.
+        public float[] CameraBodies(float[] camera, int width, int height, float[] box, float[] paint, float[] bodies,
+                                    int stride = 10, int mode = OceanNative.CameraColor, float[] material = null,
+                                    int iterations = 4, int steps = 64, int refine = 8)
+        {
+            int per = mode == OceanNative.CameraHits ? 8 : mode == OceanNative.CameraRange ? 1 : 4;
+            bool valid = width >= 1 && height >= 1 && (long)width * height <= OceanNative.CameraMaxPixels;
+            var output = new float[valid ? width * height * per : 0];
+            int count = bodies == null || stride < 10 ? 0 : (bodies.Length + stride - 10) / stride;
+            OceanNative.Check(OceanNative.ocean_camera_bodies(ctx, 0, mode, iterations, steps, refine, camera, material, width,
+                                                              height, box, paint, bodies, stride, count, output,
+                                                              (UIntPtr)(ulong)(output.Length * 4)), "ocean_camera_bodies");
+            return output;
+        }
+
         // The atmosphere of AtmosphereController.cs (ocean.h "The atmosphere"): Awake's two tables, with `parameters` =
         // 32 floats (null: the reference's defaults) at the reference's sizes.
         public static readonly float[] DefaultAtmosphere = {

@@ -1,6 +1,6 @@
 // C-ABI layer of liboceanhip.so, the point consumers (ocean.h): surface and velocity queries, surface grids,
-// buoyant bodies, body dynamics, body steps, ray casts, whitecap emitters, spray particles and camera views, each in a
-// _device, a blocking host
+// buoyant bodies, body dynamics, body steps, ray casts, whitecap emitters, spray particles and camera views (with and
+// without the bodies), each in a _device, a blocking host
 // and an _async form; and world sampling and the surface bounds, which keep bodies of their own.
 //
 // A consumer is stated once, as a struct built from its entry's arguments (a "family"), and its three entries
@@ -468,7 +468,9 @@ struct Camera {
 
     static constexpr int kSkyMode = OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT;
     static size_t pixel_bytes(int mode) { return mode == OCEAN_CAMERA_HITS ? 32 : mode == OCEAN_CAMERA_RANGE ? 4 : 16; }
-    int check(Form form) const {
+    int check(Form form) const { return check_as(form, state().entry, inputs()); }
+    // entry, in: the family's own name and inputs (the camera with bodies runs these tests too)
+    int check_as(Form form, const char* entry, const StagedInputs& in) const {
         if (!camera || !out) return fail(OCEAN_E_INVALID_ARG, "null camera or output");
         if (mode == (OCEAN_CAMERA_HITS | OCEAN_CAMERA_SKY_LUT) || mode == (OCEAN_CAMERA_RANGE | OCEAN_CAMERA_SKY_LUT))
             return fail(OCEAN_E_INVALID_ARG, "camera mode: OCEAN_CAMERA_SKY_LUT combines with OCEAN_CAMERA_COLOR only");
@@ -496,13 +498,13 @@ struct Camera {
             return fail(OCEAN_E_INVALID_ARG, "byte count " + std::to_string(bytes) + " != width * height * " +
                                                  std::to_string(pixel_bytes(mode)) + " = " + std::to_string(want));
         if (form == Form::Device)
-            if (int r = check_aligned(state().entry, inputs(), out)) return r;
+            if (int r = check_aligned(entry, in, out)) return r;
         if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
         if (int r = check_tile(ctx, tile)) return r;
         // the async form's result is written into a readback slot
         if (form == Form::Async && bytes > stage_slot_bytes(ctx))
-            return fail(OCEAN_E_INVALID_ARG, "ocean_camera_async: " + std::to_string(bytes) + " B exceed a readback slot of " +
-                                                 std::to_string(stage_slot_bytes(ctx)) + " B");
+            return fail(OCEAN_E_INVALID_ARG, std::string(entry) + "_async: " + std::to_string(bytes) +
+                                                 " B exceed a readback slot of " + std::to_string(stage_slot_bytes(ctx)) + " B");
         return OCEAN_OK;
     }
     StateRule state() const { return {"ocean_camera", "camera view of", Needs::Nothing, mode == kSkyMode}; }
@@ -529,6 +531,63 @@ struct Camera {
                      "camera");
     }
 };
+
+// Camera views with bodies: the camera, with the box's six and the paint's four floats by value beside its own and
+// the body records as its one staged input, (count - 1) * stride + 10 floats (none when count is 0).  Its own arguments
+// first, none of which needs the context, then everything the camera refuses.  The async form's records can outgrow
+// both a slot's room behind the image and its pinned copy (2 MiB at the limits), so they go through the slot's own
+// block pair, as the spray's inputs do.
+struct CameraBodies : Camera {
+    const float* box;
+    const float* paint;
+    const float* bodies;
+    int stride, count;
+
+    int check(Form form) const {
+        if (!box) return fail(OCEAN_E_INVALID_ARG, "null box");
+        if ((mode == OCEAN_CAMERA_COLOR || mode == kSkyMode) && !paint)
+            return fail(OCEAN_E_INVALID_ARG, "the colour modes need a paint");
+        for (int k = 0; k < 6; ++k)
+            if (!std::isfinite(box[k])) return fail(OCEAN_E_INVALID_ARG, "box[" + std::to_string(k) + "] is not finite");
+        for (int k = 0; paint && k < OCEAN_BODY_PAINT_FLOATS; ++k)
+            if (!std::isfinite(paint[k])) return fail(OCEAN_E_INVALID_ARG, "paint[" + std::to_string(k) + "] is not finite");
+        if (stride < 10 || stride > 64) return fail(OCEAN_E_INVALID_ARG, "stride = " + std::to_string(stride) + " outside [10, 64]");
+        if (count < 0 || count > OCEAN_BODY_MAX_BODIES)
+            return fail(OCEAN_E_INVALID_ARG, "body count " + std::to_string(count) + " outside [0, OCEAN_BODY_MAX_BODIES]");
+        if (count > 0 && !bodies) return fail(OCEAN_E_INVALID_ARG, "null bodies with count > 0");
+        return check_as(form, state().entry, inputs());
+    }
+    StateRule state() const { return {"ocean_camera_bodies", "camera view of", Needs::Nothing, mode == kSkyMode}; }
+    StagedInputs inputs() const {
+        const size_t floats = count > 0 ? ((size_t)count - 1) * stride + 10 : 0;
+        return {"bodies", count > 0 ? 1 : 0, {{bodies, floats * 4}}, 0, true};
+    }
+    int launch(const float* const* in, float* d_out) const {
+        const float* bounds;
+        if (int r = air_skip_bounds(ctx, tile, &bounds)) return r;
+        ocean::CameraRays cam;
+        ocean::CameraMaterial mat = {};
+        ocean::BodyBox bx;
+        ocean::BodyPaint pt = {};
+        std::copy(camera, camera + OCEAN_CAMERA_FLOATS, cam.c);
+        if (material) std::copy(material, material + OCEAN_CAMERA_MATERIAL_FLOATS, mat.m);
+        std::copy(box, box + 6, bx.b);
+        if (paint) std::copy(paint, paint + OCEAN_BODY_PAINT_FLOATS, pt.p);
+        const bool sky = mode == kSkyMode;
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] {
+                         return ocean::launch_camera_bodies(v, tile, mode, iterations, steps, refine, bounds, cam, mat,
+                                                            sky ? ctx->atm.view(OCEAN_LUT_SKYVIEW) : ocean::LutView{},
+                                                            sky ? ctx->atm.params.p[26] : 0.0f, bx, pt,
+                                                            count > 0 ? in[0] : nullptr, stride, count,
+                                                            ctx->opt.camera_cull != 0, width, height, d_out, ctx->stream);
+                     },
+                     "camera_bodies");
+    }
+};
+static_assert(((size_t)OCEAN_BODY_MAX_BODIES * 64) * sizeof(float) <= kSprayInputBytes,
+              "a slot's own block pair holds every camera request's bodies");
 
 // Spray particles: the pool, (capacity + 1) records of 32 B, and the emitter list or none -> the stepped pool, with
 // the sixteen `spray` floats by value.  As for the whitecaps, what does not need the context is checked first, the
@@ -740,6 +799,28 @@ int ocean_camera(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, 
 int ocean_camera_async(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, int refine, const float* camera,
                        const float* material, int width, int height, float* out, size_t bytes, ocean_readback** req) {
     return async_form(Camera{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes}, req);
+}
+
+int ocean_camera_bodies_device(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, int refine, const float* camera,
+                               const float* material, int width, int height, const float* box, const float* paint,
+                               const float* bodies, int stride, int count, float* out, size_t bytes) {
+    return device_form(CameraBodies{{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes},
+                                    box, paint, bodies, stride, count});
+}
+
+int ocean_camera_bodies(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, int refine, const float* camera,
+                        const float* material, int width, int height, const float* box, const float* paint,
+                        const float* bodies, int stride, int count, float* out, size_t bytes) {
+    return host_form(CameraBodies{{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes},
+                                  box, paint, bodies, stride, count});
+}
+
+int ocean_camera_bodies_async(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, int refine, const float* camera,
+                              const float* material, int width, int height, const float* box, const float* paint,
+                              const float* bodies, int stride, int count, float* out, size_t bytes, ocean_readback** req) {
+    return async_form(CameraBodies{{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes},
+                                   box, paint, bodies, stride, count},
+                      req);
 }
 
 int ocean_spray_step_device(ocean_ctx* ctx, int tile, int iterations, int substeps, const float* spray, const float* pool,

@@ -119,7 +119,8 @@ static_assert(kSprayInputBytes == 4096 * 1024, "the arithmetic above");
 struct StageSlot {
     void* mem = nullptr;
     void* pts_host = nullptr;    // pinned, kStageInputBytes: the inputs of the request holding the slot
-    void* big_host = nullptr;    // pinned, kSprayInputBytes, and its device twin: a spray request's inputs
+    void* big_host = nullptr;    // pinned, kSprayInputBytes, and its device twin: a spray request's inputs, or the
+                                 // bodies of a camera request
     void* big_dev = nullptr;
     hipEvent_t after = nullptr;  // the snapshot is in the slot (the copy stream waits for it)
     hipEvent_t done = nullptr;   // the host copy has landed (untimed requests)
@@ -144,6 +145,7 @@ struct ocean_options {
     int prune = 1;          // OCEAN_PRUNE=0: passes AQ / BQ run every row of a band-limited cascade (dense schedule)
     int ray_bounds = 1;     // OCEAN_RAY_BOUNDS=0: the ray kernel samples every node (no air skip, no bounds launches)
     int camera_tile = 1;    // OCEAN_CAMERA_TILE=0: the camera kernel maps pixels to lanes row-linearly, not in 8 x 8 tiles (A/B)
+    int camera_cull = 1;    // OCEAN_CAMERA_CULL=0: ocean_camera_bodies* hands every body to every tile's slab tests (no cull; A/B)
     int max_groups = 0;     // OCEAN_MAX_GROUPS: at most this many workgroups per persistent launch (the transform passes
                             // of fftq / fft3 / fft4k / fft2.hip), so that their item loops iterate at small shapes; 0: no cap
 
@@ -161,6 +163,7 @@ struct ocean_options {
         if (const char* e = std::getenv("OCEAN_PRUNE")) o.prune = std::atoi(e);
         if (const char* e = std::getenv("OCEAN_RAY_BOUNDS")) o.ray_bounds = std::atoi(e);
         if (const char* e = std::getenv("OCEAN_CAMERA_TILE")) o.camera_tile = std::atoi(e);
+        if (const char* e = std::getenv("OCEAN_CAMERA_CULL")) o.camera_cull = std::atoi(e);
         if (const char* e = std::getenv("OCEAN_MAX_GROUPS")) o.max_groups = std::max(0, std::atoi(e));
         return o;
     }
@@ -400,7 +403,8 @@ struct StagedInputs {
     int n;
     HostInput v[kMaxInputs];
     size_t slot_offset = kQueryPointsOffset;  // where an async request puts them in its slot (StageSlot)
-    bool own_block = false;  // an async request stages them in the slot's big_host / big_dev pair instead (spray)
+    bool own_block = false;  // an async request stages them in the slot's big_host / big_dev pair instead (spray, and
+                             // the camera's bodies)
 };
 
 // Bytes of a readback slot of this context: the largest slice (float4 textures), or a full surface query's

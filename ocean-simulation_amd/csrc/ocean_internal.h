@@ -250,6 +250,21 @@ hipError_t launch_skyview(const AtmosphereParams& a, const LutView& tr, const Lu
 hipError_t launch_camera_sky(const DevView& v, int tile, int iterations, int steps, int refine, const float* bounds,
                              const CameraRays& cam, const CameraMaterial& mt, const LutView& sky, float sun_size, int width,
                              int height, bool tiled, float* out, hipStream_t s);
+// view.hip: camera views with bodies (ocean_camera_bodies*): launch_camera's image, or launch_camera_sky's in the mode
+// OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT (`sky` and sun_size are read in that mode only), with the boxes of `bodies`
+// in front of the water: record b at bodies + b * stride floats, device pointer, may be null when count is 0.  The box's
+// 6 and the paint's 4 floats of ocean.h travel as kernel arguments.  Always the tiled mapping.  cull: the per-tile
+// bounding-sphere cull (false: every body reaches every pixel's slab test; the same image).
+struct BodyBox {
+    float b[6];
+};
+struct BodyPaint {
+    float p[OCEAN_BODY_PAINT_FLOATS];
+};
+hipError_t launch_camera_bodies(const DevView& v, int tile, int mode, int iterations, int steps, int refine,
+                                const float* bounds, const CameraRays& cam, const CameraMaterial& mt, const LutView& sky,
+                                float sun_size, const BodyBox& box, const BodyPaint& paint, const float* bodies, int stride,
+                                int count, bool cull, int width, int height, float* out, hipStream_t s);
 
 // whitecaps.hip: whitecap emitters (ocean_whitecaps*), device pointers: out = (capacity + 1) records of 32 B, the
 // header then the selected nodes of the grid in ascending node order, 16-B aligned; vel = the context's VEL or null

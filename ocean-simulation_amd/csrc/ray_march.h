@@ -28,6 +28,15 @@
 // gradual underflow, f = pos.y - height > 0: the branch the sampled f would have taken.  The result does not
 // depend on the bound, only the number of samples does.  (NaN texels or rays: unspecified numbers, as ocean.h
 // says; bil() wraps every index whatever its input, and nothing here indexes by t.)
+//
+// Stop at a body (STOP, the camera views with bodies).  A caller that already knows an opaque thing on the ray at
+// t_stop needs the water only in front of it.  A node t_j >= t_stop that is above the water, with no crossing
+// before it, ends the march: a later crossing would be bracketed by a = t_(j'-1) >= t_j and b = t_j' > a, the
+// bisection keeps a < b (a midpoint equal to a is above, as a is, and moves a, never b), so t* = b > t_stop, and a
+// MISS has no t* at all; in both cases the thing at t_stop is what the ray meets first.  The march then reports
+// OCEAN_RAY_BODY and no t*.  A node at or behind t_stop that is under the water bisects as usual, and the caller
+// compares t* with t_stop.  HIT, MISS and SUBMERGED results are those of the full march, bit for bit; only the
+// number of samples differs.  t_stop = NaN never stops (every compare with it is false).
 #pragma once
 
 #include "ocean_internal.h"
@@ -53,9 +62,10 @@ struct RayMeet {
     int status;
 };
 
-__device__ __forceinline__ RayMeet ray_march(const DevView& v, int tile, int iterations, int steps, int refine,
-                                             const float* __restrict__ bounds, float ox, float oy, float oz, float dx,
-                                             float dy, float dz, float t0, float t1) {
+template <bool STOP>
+__device__ __forceinline__ RayMeet ray_march_until(const DevView& v, int tile, int iterations, int steps, int refine,
+                                                   const float* __restrict__ bounds, float ox, float oy, float oz,
+                                                   float dx, float dy, float dz, float t0, float t1, float t_stop) {
     const bool skip = bounds != nullptr;
     const float H = skip ? air_height(bounds, v.C) : 0.0f;
     const float dt = (t1 - t0) / (float)steps;
@@ -73,6 +83,10 @@ __device__ __forceinline__ RayMeet ray_march(const DevView& v, int tile, int ite
         }
         if (!refining) {
             if (above) {
+                if (STOP && t >= t_stop) {
+                    status = OCEAN_RAY_BODY;
+                    break;
+                }
                 if (j == steps) {
                     status = OCEAN_RAY_MISS;
                     break;
@@ -106,6 +120,13 @@ __device__ __forceinline__ RayMeet ray_march(const DevView& v, int tile, int ite
     m.t = t;
     m.status = status;
     return m;
+}
+
+// The full march: ocean_raycast's and ocean_camera's.
+__device__ __forceinline__ RayMeet ray_march(const DevView& v, int tile, int iterations, int steps, int refine,
+                                             const float* __restrict__ bounds, float ox, float oy, float oz, float dx,
+                                             float dy, float dz, float t0, float t1) {
+    return ray_march_until<false>(v, tile, iterations, steps, refine, bounds, ox, oy, oz, dx, dy, dz, t0, t1, 0.0f);
 }
 
 }  // namespace ocean

@@ -116,36 +116,26 @@ __device__ __forceinline__ float3 shade_hit(const CameraMaterial& mt, float dx, 
     return make_float3(out[0], out[1], out[2]);
 }
 
-// Pixel (i, j) -> element k = j * width + i of `out`.  TILED: a workgroup is a 16 x 16 pixel tile, wave w its
-// 8 x 8 quadrant (w & 1, w >> 1), lane l the pixel (l & 7, l >> 3) of it; else 256 consecutive k per workgroup.
-// SKY (colour mode only): the sky and the sun's disc of OCEAN_CAMERA_SKY_LUT over `sk`.
-template <int MODE, bool TILED, bool SKY>
-__device__ __forceinline__ void camera_pixel(const DevView& v, int tile, int iterations, int steps, int refine,
-                                             const float* __restrict__ bounds, const CameraRays& cam,
-                                             const CameraMaterial& mt, int width, int height, float* __restrict__ out,
-                                             const LutView& sk, float sun_size) {
-    int i, j;
-    if (TILED) {
-        const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-        i = blockIdx.x * 16 + (w & 1) * 8 + (l & 7);
-        j = blockIdx.y * 16 + (w >> 1) * 8 + (l >> 3);
-    } else {
-        const int lin = blockIdx.x * 256 + threadIdx.x;  // < 2^22 + 256
-        i = lin % width;
-        j = lin / width;
-    }
-    if (i >= width || j >= height) return;
-    const size_t k = (size_t)j * width + i;
-
-    const float fi = (float)i, fj = (float)j;
+// d of ocean.h for the pixel at (fi, fj): the camera's direction through it, normalised.
+struct Vec3 {
+    float x, y, z;
+};
+__device__ __forceinline__ Vec3 pixel_direction(const CameraRays& cam, float fi, float fj) {
     const float rx = (cam.c[3] + fi * cam.c[6]) + fj * cam.c[9];
     const float ry = (cam.c[4] + fi * cam.c[7]) + fj * cam.c[10];
     const float rz = (cam.c[5] + fi * cam.c[8]) + fj * cam.c[11];
     const float len = sqrtf((rx * rx + ry * ry) + rz * rz);
-    const float dx = rx / len, dy = ry / len, dz = rz / len;
-    const float ox = cam.c[0], oy = cam.c[1], oz = cam.c[2];
+    Vec3 d;
+    d.x = rx / len, d.y = ry / len, d.z = rz / len;
+    return d;
+}
 
-    const RayMeet m = ray_march(v, tile, iterations, steps, refine, bounds, ox, oy, oz, dx, dy, dz, cam.c[12], cam.c[13]);
+// Element k of `out` for a pixel whose ray (o, d) met the water as `m` says (HIT, MISS or SUBMERGED): ocean_camera's
+// pixel in MODE.  SKY (colour mode only): the sky and the sun's disc of OCEAN_CAMERA_SKY_LUT over `sk`.
+template <int MODE, bool SKY>
+__device__ __forceinline__ void water_pixel(const DevView& v, int tile, int iterations, const CameraMaterial& mt, float ox,
+                                            float oy, float oz, float dx, float dy, float dz, const RayMeet& m, size_t k,
+                                            float* __restrict__ out, const LutView& sk, float sun_size) {
     const float t = m.t;
     if (MODE == OCEAN_CAMERA_RANGE) {
         out[k] = m.status == OCEAN_RAY_MISS ? __builtin_inff() : t;
@@ -187,6 +177,31 @@ __device__ __forceinline__ void camera_pixel(const DevView& v, int tile, int ite
     }
 }
 
+// Pixel (i, j) -> element k = j * width + i of `out`.  TILED: a workgroup is a 16 x 16 pixel tile, wave w its
+// 8 x 8 quadrant (w & 1, w >> 1), lane l the pixel (l & 7, l >> 3) of it; else 256 consecutive k per workgroup.
+template <int MODE, bool TILED, bool SKY>
+__device__ __forceinline__ void camera_pixel(const DevView& v, int tile, int iterations, int steps, int refine,
+                                             const float* __restrict__ bounds, const CameraRays& cam,
+                                             const CameraMaterial& mt, int width, int height, float* __restrict__ out,
+                                             const LutView& sk, float sun_size) {
+    int i, j;
+    if (TILED) {
+        const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+        i = blockIdx.x * 16 + (w & 1) * 8 + (l & 7);
+        j = blockIdx.y * 16 + (w >> 1) * 8 + (l >> 3);
+    } else {
+        const int lin = blockIdx.x * 256 + threadIdx.x;  // < 2^22 + 256
+        i = lin % width;
+        j = lin / width;
+    }
+    if (i >= width || j >= height) return;
+    const size_t k = (size_t)j * width + i;
+    const Vec3 d = pixel_direction(cam, (float)i, (float)j);
+    const float ox = cam.c[0], oy = cam.c[1], oz = cam.c[2];
+    const RayMeet m = ray_march(v, tile, iterations, steps, refine, bounds, ox, oy, oz, d.x, d.y, d.z, cam.c[12], cam.c[13]);
+    water_pixel<MODE, SKY>(v, tile, iterations, mt, ox, oy, oz, d.x, d.y, d.z, m, k, out, sk, sun_size);
+}
+
 template <int MODE, bool TILED>
 __global__ __launch_bounds__(256) void k_camera(DevView v, int tile, int iterations, int steps, int refine,
                                                 const float* __restrict__ bounds, CameraRays cam, CameraMaterial mt,
@@ -201,6 +216,210 @@ __global__ __launch_bounds__(256) void k_camera_sky(DevView v, int tile, int ite
                                                     float* __restrict__ out) {
     camera_pixel<OCEAN_CAMERA_COLOR, TILED, true>(v, tile, iterations, steps, refine, bounds, cam, mt, width, height, out, sk,
                                                   sun_size);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Camera views that see the bodies (ocean_camera_bodies*).  include/ocean/ocean.h has the definition: per pixel the
+// slab test of the ray against every body's box, the nearest body met, and the nearer of that body and the water.
+// The definition is a loop over all bodies per pixel; the kernel gets the same bits from fewer tests and samples.
+//
+// Cull per workgroup.  A workgroup is a 16 x 16 pixel tile (always the tiled mapping).  The bodies go by in chunks
+// of 256; lane l of the workgroup forms what the slab test needs of body base + l that does not depend on the
+// pixel (ob, l, h: the statements of ocean.h, so the same bits for every pixel) and tests the body's bounding
+// sphere against a cone around the tile's rays and against [t0, t1].  The survivors are compacted into LDS in
+// ascending b (a ballot per wave, then a prefix over the four waves' counts), and after a barrier every lane runs
+// the slab test over them.  Survivors in ascending b and a strict `te <` keep the lowest b on ties, as the
+// definition does.  OCEAN_CAMERA_CULL=0 makes every body a survivor.
+//
+// The cull is conservative: a body it drops is met by no ray of the tile.  In exact arithmetic:
+//   - the cone.  The raw directions of a tile's pixels are affine in (i, j): they lie in the parallelogram of the
+//     four corner pixels' raw directions.  The directions within an angle theta < 90 degrees of an axis form a convex
+//     cone, so if the corners are within theta of the axis, every pixel is.  The axis a is the direction through the
+//     tile's centre; sin(theta) is the largest |corner x a| and cos(theta) the smallest dot(corner, a) (a partial
+//     tile uses the full tile's corners: a superset).  A tile with cos(theta) < 1/2 is not culled at all;
+//   - the sphere.  With q near unit the slab test's box is c + A B, B the scaled box, A = P + Q / sigma, where P
+//     projects on u, Q turns the plane across u and sigma^2 = 1 + 4 |u|^2 e, e = |q|^2 - 1; rot(u, qw, .) is
+//     P + sigma Q.  For |e| <= 2^-10: 1 / sigma <= 1 + 2^-8 and |1 / sigma - sigma| <= 2^-7, so every point of the
+//     box lies within hd (1 + 2^-8) + 2^-7 |bc| of ctr = c + rot(u, qw, bc), bc the scaled box's centre and hd half
+//     its diagonal.  A body whose |q|^2 is further from 1 is a survivor: its box may be anything;
+//   - the test.  With v = ctr - o, x = dot(v, a), y = |v x a|, a point at distance y cos(theta) - x sin(theta) or
+//     more from every point of the solid cone (behind the apex the true distance, |v|, is larger still), so a body
+//     with y cos(theta) - x sin(theta) > rad is off every ray, and one with |v| - rad > t1 or |v| + rad < t0 is
+//     met outside [t0, t1] only.
+// In fp32, with u = 2^-24, every length below is at most S = |v|_1 + |bc|_1 + hd (1-norms: larger than the 2-norms):
+//   - the slab test itself reports `met` only for a ray that passes within 64 u S of the exact box: ob and db carry
+//     at most 16 u |w| and 16 u from rot's four levels of operations, l and h one rounding each, n_i and f_i two;
+//     one axis has |db_i| >= 1 / 2, which bounds tn and tf by 2 S, so the overlap tn <= tf can be wrong by 8 u S of
+//     ray length, and the perturbed ob and db move the ray by 16 u |w| + 32 u S;
+//   - the pixels' fp32 directions are within 8 u of the exact ones, and of unit length within 4 u: 12 u |v| across
+//     and along the ray;
+//   - v, a, the two products x and y (a cross product, not a difference of squares), cos and sin each carry at most
+//     24 u S, 4 u, 24 u S, 8 u: the left side is off by at most 80 u S.
+// Together less than 160 u S; the margin is 2^-16 S = 256 u S, added to rad.  Every compare is written so that a
+// NaN makes a survivor.
+//
+// Stop the march at the body.  The body loop comes first, and the march runs with t_stop = te of the pixel's body
+// (ray_march.h, STOP): a ray that reaches the body's distance above the water ends there.
+struct alignas(16) BodySurvivor {  // 64 B: what the slab test reads of a body, and its index
+    float obx, oby, obz, ux, uy, uz, qw, lx, ly, lz, hx, hy, hz;
+    int b;
+};
+static_assert(sizeof(BodySurvivor) == 64, "four float4 per survivor");
+
+// a rotated by the quaternion (u, w) (ocean.h, rot): t = 2 (u x a), (a + w t) + (u x t).
+__device__ __forceinline__ Vec3 rotate(float ux, float uy, float uz, float w, float ax, float ay, float az) {
+    const float tx = 2.0f * (uy * az - uz * ay), ty = 2.0f * (uz * ax - ux * az), tz = 2.0f * (ux * ay - uy * ax);
+    Vec3 r;
+    r.x = (ax + w * tx) + (uy * tz - uz * ty);
+    r.y = (ay + w * ty) + (uz * tx - ux * tz);
+    r.z = (az + w * tz) + (ux * ty - uy * tx);
+    return r;
+}
+
+// One axis of the slab test: n_i and f_i, or false where the ray runs beside the slab.
+__device__ __forceinline__ bool slab(float l, float h, float ob, float db, float& n, float& f) {
+    if (db == 0.0f) {
+        n = -__builtin_inff(), f = __builtin_inff();
+        return fminf(l, h) <= ob && ob <= fmaxf(l, h);
+    }
+    const float a = (l - ob) / db, e = (h - ob) / db;
+    n = fminf(a, e), f = fmaxf(a, e);
+    return true;
+}
+
+constexpr float kCullMargin = 0x1p-16f;   // of S, above
+constexpr float kUnitQuat = 0x1p-10f;     // |q|^2 within this of 1, above
+
+template <int MODE, bool SKY>
+__global__ __launch_bounds__(256) void k_camera_bodies(DevView v, int tile, int iterations, int steps, int refine,
+                                                       const float* __restrict__ bounds, CameraRays cam, CameraMaterial mt,
+                                                       LutView sk, float sun_size, BodyBox box, BodyPaint paint,
+                                                       const float* __restrict__ bodies, int stride, int count, int cull,
+                                                       int width, int height, float* __restrict__ out) {
+    __shared__ BodySurvivor s_body[256];
+    __shared__ int s_count[4];
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int i0 = blockIdx.x * 16, j0 = blockIdx.y * 16;
+    const int i = i0 + (w & 1) * 8 + (l & 7), j = j0 + (w >> 1) * 8 + (l >> 3);
+    const Vec3 d = pixel_direction(cam, (float)i, (float)j);
+    const float ox = cam.c[0], oy = cam.c[1], oz = cam.c[2], t0 = cam.c[12], t1 = cam.c[13];
+
+    // the tile's cone: axis, cos and sin of its half angle
+    const Vec3 ax = pixel_direction(cam, (float)i0 + 7.5f, (float)j0 + 7.5f);
+    float ct = 1.0f, st = 0.0f;
+    for (int c = 0; c < 4; ++c) {
+        const Vec3 e = pixel_direction(cam, (float)(i0 + 15 * (c & 1)), (float)(j0 + 15 * (c >> 1)));
+        const float cx = e.y * ax.z - e.z * ax.y, cy = e.z * ax.x - e.x * ax.z, cz = e.x * ax.y - e.y * ax.x;
+        ct = fminf(ct, dot3(e.x, e.y, e.z, ax.x, ax.y, ax.z));
+        st = fmaxf(st, sqrtf((cx * cx + cy * cy) + cz * cz));
+    }
+    const bool culling = cull != 0 && ct >= 0.5f;
+
+    // the pixel's body: the met body of smallest te, the lowest b on ties
+    float best_te = __builtin_inff(), nwx = 0.0f, nwy = 0.0f, nwz = 0.0f;
+    int best_b = -1;
+    if (!(t1 < t0)) {  // else no body is met
+        for (int base = 0; base < count; base += 256) {
+            const int b = base + (int)threadIdx.x;
+            bool keep = false;
+            BodySurvivor sv = {};
+            if (b < count) {
+                const float* B = bodies + (size_t)b * stride;
+                const float cx = B[0], cy = B[1], cz = B[2], sx = B[7], sy = B[8], sz = B[9];
+                sv.ux = B[3], sv.uy = B[4], sv.uz = B[5], sv.qw = B[6];
+                const Vec3 ob = rotate(-sv.ux, -sv.uy, -sv.uz, sv.qw, ox - cx, oy - cy, oz - cz);
+                sv.obx = ob.x, sv.oby = ob.y, sv.obz = ob.z;
+                sv.lx = sx * box.b[0], sv.ly = sy * box.b[1], sv.lz = sz * box.b[2];
+                sv.hx = sx * box.b[3], sv.hy = sy * box.b[4], sv.hz = sz * box.b[5];
+                sv.b = b;
+                keep = true;
+                if (culling) {
+                    const float bx = 0.5f * (sv.lx + sv.hx), by = 0.5f * (sv.ly + sv.hy), bz = 0.5f * (sv.lz + sv.hz);
+                    const float ex = 0.5f * (sv.hx - sv.lx), ey = 0.5f * (sv.hy - sv.ly), ez = 0.5f * (sv.hz - sv.lz);
+                    const float hd = sqrtf((ex * ex + ey * ey) + ez * ez);
+                    const float bc1 = (fabsf(bx) + fabsf(by)) + fabsf(bz);
+                    const Vec3 r = rotate(sv.ux, sv.uy, sv.uz, sv.qw, bx, by, bz);
+                    const float vx = (cx - ox) + r.x, vy = (cy - oy) + r.y, vz = (cz - oz) + r.z;
+                    const float S = (((fabsf(vx) + fabsf(vy)) + fabsf(vz)) + bc1) + hd;
+                    const float rad = (hd * (1.0f + 0x1p-8f) + bc1 * 0x1p-7f) + kCullMargin * S;
+                    const float x = dot3(vx, vy, vz, ax.x, ax.y, ax.z);
+                    const float px = vy * ax.z - vz * ax.y, py = vz * ax.x - vx * ax.z, pz = vx * ax.y - vy * ax.x;
+                    const float y = sqrtf((px * px + py * py) + pz * pz);
+                    const float dist = sqrtf((vx * vx + vy * vy) + vz * vz);
+                    const float qq = ((sv.ux * sv.ux + sv.uy * sv.uy) + sv.uz * sv.uz) + sv.qw * sv.qw;
+                    const bool off = y * ct - x * st > rad || dist - rad > t1 || dist + rad < t0;
+                    keep = !(off && fabsf(qq - 1.0f) <= kUnitQuat);
+                }
+            }
+            const unsigned long long mask = __ballot(keep);
+            if (l == 0) s_count[w] = __popcll(mask);
+            __syncthreads();  // the counts are there; every lane is done with the chunk before
+            int first = 0, total = 0;
+            for (int k = 0; k < 4; ++k) {
+                const int n = s_count[k];
+                first += k < w ? n : 0;
+                total += n;
+            }
+            if (keep) s_body[first + __popcll(mask & ((1ull << l) - 1ull))] = sv;
+            __syncthreads();  // the survivors are there
+
+            for (int s = 0; s < total; ++s) {
+                const BodySurvivor& q = s_body[s];  // one address for the wave: a broadcast
+                const Vec3 db = rotate(-q.ux, -q.uy, -q.uz, q.qw, d.x, d.y, d.z);
+                float nx, ny, nz, fx, fy, fz;
+                bool met = slab(q.lx, q.hx, q.obx, db.x, nx, fx);
+                met = slab(q.ly, q.hy, q.oby, db.y, ny, fy) && met;
+                met = slab(q.lz, q.hz, q.obz, db.z, nz, fz) && met;
+                const float tn = fmaxf(fmaxf(nx, ny), nz), tf = fminf(fminf(fx, fy), fz);
+                met = met && tn <= tf && tf >= t0 && tn <= t1;
+                const float te = fmaxf(tn, t0);
+                if (met && te < best_te) {
+                    best_te = te;
+                    best_b = q.b;
+                    if (tn >= t0) {
+                        const bool on_x = nx == tn, on_y = !on_x && ny == tn;
+                        const float dbi = on_x ? db.x : on_y ? db.y : db.z;
+                        const float sign = dbi > 0.0f ? -1.0f : 1.0f;
+                        const Vec3 nw = rotate(q.ux, q.uy, q.uz, q.qw, on_x ? sign : 0.0f, on_y ? sign : 0.0f,
+                                               on_x || on_y ? 0.0f : sign);
+                        nwx = nw.x, nwy = nw.y, nwz = nw.z;
+                    } else {  // the eye is inside the box
+                        nwx = -d.x, nwy = -d.y, nwz = -d.z;
+                    }
+                }
+            }
+        }
+    }
+    if (i >= width || j >= height) return;  // behind the last barrier
+    const size_t k = (size_t)j * width + i;
+
+    const RayMeet m = ray_march_until<true>(v, tile, iterations, steps, refine, bounds, ox, oy, oz, d.x, d.y, d.z, t0, t1,
+                                            best_b >= 0 ? best_te : __builtin_nanf(""));
+    const bool body = best_b >= 0 && (m.status == OCEAN_RAY_BODY || m.status == OCEAN_RAY_MISS ||
+                                      (m.status == OCEAN_RAY_HIT && best_te < m.t));
+    if (!body) {
+        water_pixel<MODE, SKY>(v, tile, iterations, mt, ox, oy, oz, d.x, d.y, d.z, m, k, out, sk, sun_size);
+        return;
+    }
+    if (MODE == OCEAN_CAMERA_RANGE) {
+        out[k] = best_te;
+    } else if (MODE == OCEAN_CAMERA_HITS) {
+        float4* o = reinterpret_cast<float4*>(out) + 2 * k;
+        o[0] = make_float4(best_te, 0.0f, 0.0f, (float)OCEAN_RAY_BODY);
+        o[1] = make_float4(nwx, nwy, nwz, (float)best_b);
+    } else {
+        float amb[3];
+        if (SKY) {
+            const float3 e = sky_lut(sk, nwx, nwy, nwz);
+            amb[0] = e.x, amb[1] = e.y, amb[2] = e.z;
+        } else {
+            for (int c = 0; c < 3; ++c) amb[c] = sky(mt.m[26 + c], mt.m[29 + c], nwy);
+        }
+        const float lit = fmaxf(dot3(nwx, nwy, nwz, mt.m[20], mt.m[21], mt.m[22]), 0.0f);
+        float rgb[3];
+        for (int c = 0; c < 3; ++c) rgb[c] = paint.p[c] * (paint.p[3] * amb[c] + mt.m[23 + c] * lit);
+        reinterpret_cast<float4*>(out)[k] = make_float4(rgb[0], rgb[1], rgb[2], (float)OCEAN_RAY_BODY);
+    }
 }
 
 // The launch grid of camera_pixel's two mappings: 16 x 16 pixel tiles, or 256 consecutive pixels per workgroup.
@@ -234,6 +453,23 @@ hipError_t launch_camera_sky(const DevView& v, int tile, int iterations, int ste
                iterations, steps, refine, bounds, cam, mt, sky, sun_size, width, height, out);
     });
     return hipGetLastError();
+}
+
+hipError_t launch_camera_bodies(const DevView& v, int tile, int mode, int iterations, int steps, int refine,
+                                const float* bounds, const CameraRays& cam, const CameraMaterial& mt, const LutView& sky,
+                                float sun_size, const BodyBox& box, const BodyPaint& paint, const float* bodies, int stride,
+                                int count, bool cull, int width, int height, float* out, hipStream_t s) {
+    if (width < 1 || height < 1 || (size_t)width * height > (size_t)OCEAN_CAMERA_MAX_PIXELS) return hipErrorInvalidValue;
+    if (stride < 10 || count < 0 || (count > 0 && !bodies)) return hipErrorInvalidValue;
+    constexpr int kSky = OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT;
+    if (mode == kSky && (!sky.texels || sky.w < 2 || sky.h < 2)) return hipErrorInvalidValue;
+    const bool known = with_constant<OCEAN_CAMERA_HITS, OCEAN_CAMERA_RANGE, OCEAN_CAMERA_COLOR, kSky>(mode, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        launch(k_camera_bodies<M & ~OCEAN_CAMERA_SKY_LUT, M == kSky>, camera_groups(width, height, true), dim3(256), 0, s, v,
+               tile, iterations, steps, refine, bounds, cam, mt, sky, sun_size, box, paint, bodies, stride, count,
+               cull ? 1 : 0, width, height, out);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace ocean

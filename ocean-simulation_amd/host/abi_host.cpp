@@ -4,7 +4,7 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|sky|step|spray]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|camera_bodies|sky|step|spray]
 //
 // With step the host plays F frames on a velocity context and, behind each, advances a fleet of six boxes of 4 x 3
 // probes by 4 substeps of 1/240 s through one WaterBody::StepBodies in its async form (surface mode, 4 steps,
@@ -16,6 +16,10 @@
 // 45 x 37 pixels (2 fixed-point steps, 32 march steps, 6 bisections): the shaded picture under a fixed material; it
 // writes camera.bin (float32 [14]), material.bin (float32 [32]) and color.bin (float32 [37][45][4]); the summary line
 // carries the number of pixels of each status; tests/test_gpu_camera_host.py checks them.
+// With camera_bodies it runs F steps, then one WaterBody::CameraBodies in OCEAN_CAMERA_HITS mode for the camera mode's
+// camera and five boxes in its view, records 16 floats apart: one in the air, three afloat, one sunk; it writes camera.bin,
+// box.bin (float32 [6]), bodies.bin (float32 [5][16]) and body_hits.bin (float32 [37][45][8]); the summary line carries
+// the number of pixels of each status; tests/test_gpu_camera_bodies_host.py checks them.
 // With sky it does the same behind the atmosphere: WaterBody::Atmosphere at the sizes 12 x 20, 3 x 5 and 20 x 12, one
 // SkyUpdate, and the camera in OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT mode under the light colour SkyUpdate returned;
 // it writes transmittance.bin, multiscatter.bin, skyview.bin (float32 [h][w][4] each), sun.bin (float32 [3]),
@@ -76,14 +80,14 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|sky|step|spray]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|camera_bodies|sky|step|spray]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
     if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity" &&
-        mode != "rays" && mode != "dynamics" && mode != "whitecaps" && mode != "camera" && mode != "sky" && mode != "step" &&
-        mode != "spray") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps, camera, sky, step or spray\n");
+        mode != "rays" && mode != "dynamics" && mode != "whitecaps" && mode != "camera" && mode != "camera_bodies" &&
+        mode != "sky" && mode != "step" && mode != "spray") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps, camera, camera_bodies, sky, step or spray\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -277,6 +281,34 @@ int main(int argc, char** argv) {
             std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"width\": %d, \"height\": %d, \"miss\": %d, "
                         "\"hit\": %d, \"submerged\": %d}\n", F, n, (int)wb.cascades.size(), width, height, status[0], status[1],
                         status[2]);
+            wb.OnDisable();
+            return 0;
+        }
+        if (mode == "camera_bodies") {
+            const int width = 45, height = 37, stride = 16;
+            const std::vector<float> camera = {3.0f, 30.0f, -4.0f, -0.45f, 0.21f, 0.85f, 0.02f, 0.0f, 0.01f,
+                                               0.0f,  -0.02f, 0.0f,  0.0f,   600.0f};
+            const std::vector<float> box = {-0.5f, -0.25f, -0.5f, 0.5f, 0.75f, 0.5f};
+            // origin, quaternion (x, y, z, w), scale; the six floats behind them are not read
+            const std::vector<float> bodies = {
+                2.0f,   16.0f, 95.0f,  0.0f,  0.0f,  0.0f,  1.0f,  8.0f,  6.0f,  8.0f,  9.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f,
+                -25.0f, 0.5f,  160.0f, 0.0f,  0.6f,  0.0f,  0.8f,  30.0f, 12.0f, 14.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f,
+                30.0f,  1.0f,  210.0f, 0.28f, 0.0f,  0.0f,  0.96f, 25.0f, 20.0f, 25.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f,
+                -5.0f,  -1.0f, 300.0f, 0.5f,  0.5f,  0.5f,  0.5f,  40.0f, 40.0f, 20.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f,
+                10.0f,  -30.0f, 120.0f, 0.0f, 0.0f,  0.0f,  1.0f,  30.0f, 10.0f, 30.0f};
+            wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
+            wb.Awake();
+            for (int f = 0; f < F; ++f) wb.Update((float)f / 60.0f);
+            const std::vector<float> hits = wb.CameraBodies(camera, width, height, box, {}, bodies, stride, OCEAN_CAMERA_HITS, {}, 2, 32, 6);
+            write_bin(out + "/camera.bin", camera.data(), camera.size());
+            write_bin(out + "/box.bin", box.data(), box.size());
+            write_bin(out + "/bodies.bin", bodies.data(), bodies.size());
+            write_bin(out + "/body_hits.bin", hits.data(), hits.size());
+            int status[4] = {0, 0, 0, 0};
+            for (int k = 0; k < width * height; ++k) ++status[(int)hits[8 * k + 3]];
+            std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"width\": %d, \"height\": %d, \"miss\": %d, "
+                        "\"hit\": %d, \"submerged\": %d, \"body\": %d}\n", F, n, (int)wb.cascades.size(), width, height,
+                        status[0], status[1], status[2], status[3]);
             wb.OnDisable();
             return 0;
         }

@@ -305,6 +305,31 @@ public:
         return out;
     }
 
+    // Camera with the boxes of `bodies` in the picture (ocean.h ocean_camera_bodies): `bodies` holds records `stride`
+    // floats apart whose first ten floats are (c, q, s), the `bodies` of Buoyancy (stride 10) or the records StepBodies
+    // returns (stride 32); `box` = 6 floats (lo, hi) of the one box they share, `paint` = 4 floats (r, g, b, ka), empty
+    // outside the colour modes.  A body pixel has the status OCEAN_RAY_BODY; OCEAN_CAMERA_HITS carries its distance,
+    // its normal and the body's index.
+    std::vector<float> CameraBodies(const std::vector<float>& camera, int width, int height, const std::vector<float>& box,
+                                    const std::vector<float>& paint, const std::vector<float>& bodies, int stride = 10,
+                                    int mode = OCEAN_CAMERA_COLOR, const std::vector<float>& material = {},
+                                    int iterations = 4, int steps = 64, int refine = 8) const {
+        if (camera.size() != OCEAN_CAMERA_FLOATS || (!material.empty() && material.size() != OCEAN_CAMERA_MATERIAL_FLOATS))
+            throw std::runtime_error("CameraBodies: camera is 14 floats, material 32 or none");
+        if (box.size() != 6 || (!paint.empty() && paint.size() != OCEAN_BODY_PAINT_FLOATS) || stride < 10)
+            throw std::runtime_error("CameraBodies: box is 6 floats, paint 4 or none, stride at least 10");
+        const size_t per = mode == OCEAN_CAMERA_HITS ? 8 : mode == OCEAN_CAMERA_RANGE ? 1 : 4;
+        const bool valid = width >= 1 && height >= 1 && (long long)width * height <= OCEAN_CAMERA_MAX_PIXELS;
+        std::vector<float> out(valid ? (size_t)width * height * per : 0);
+        const int count = bodies.empty() ? 0 : (int)((bodies.size() + (size_t)stride - 10) / (size_t)stride);
+        check(ocean_camera_bodies(ctx_, 0, mode, iterations, steps, refine, camera.data(),
+                                  material.empty() ? nullptr : material.data(), width, height, box.data(),
+                                  paint.empty() ? nullptr : paint.data(), bodies.empty() ? nullptr : bodies.data(), stride,
+                                  count, out.data(), out.size() * sizeof(float)),
+              "ocean_camera_bodies");
+        return out;
+    }
+
     // The atmosphere of AtmosphereController.cs (ocean.h "The atmosphere"): its Awake, the transmittance and the
     // multiscatter table from the 32 floats of `params` (ocean.h names them; DefaultAtmosphere() has the reference's),
     // at the reference's sizes when `dims` is empty, else (Tw, Th, Mw, Mh, Sw, Sh).  Needs no spectrum.

@@ -77,6 +77,7 @@ EXPORTED_SYMBOLS = (
     "ocean_body_step", "ocean_body_step_device", "ocean_body_step_async",
     "ocean_atmosphere", "ocean_sky_update", "ocean_atmosphere_read", "ocean_atmosphere_lut", "ocean_sun_color",
     "ocean_spray_step", "ocean_spray_step_device", "ocean_spray_step_async",
+    "ocean_camera_bodies", "ocean_camera_bodies_device", "ocean_camera_bodies_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -121,6 +122,11 @@ SPRAY_FLOATS = 16
 SPRAY_MAX_PARTICLES = (1 << 20) - 1
 SPRAY_MAX_STAGED = 65535
 SPRAY_MAX_SUBSTEPS = 64
+# ocean_camera_bodies*: the status of a body pixel, the paint's size and the limits of a record's stride (ocean.h); the
+# modes and limits are the camera's, the body limit the bodies'
+RAY_BODY = 3
+BODY_PAINT_FLOATS = 4
+BODY_STRIDE_MIN, BODY_STRIDE_MAX = 10, 64
 
 
 class OceanError(RuntimeError):
@@ -229,6 +235,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_spray_step": ([P, i, i, i, P, P, i, P, i, P, sz], i),
         "ocean_spray_step_device": ([P, i, i, i, P, P, i, P, i, P, sz], i),
         "ocean_spray_step_async": ([P, i, i, i, P, P, i, P, i, P, sz, ctypes.POINTER(P)], i),
+        "ocean_camera_bodies": ([P, i, i, i, i, i, P, P, i, i, P, P, P, i, i, P, sz], i),
+        "ocean_camera_bodies_device": ([P, i, i, i, i, i, P, P, i, i, P, P, P, i, i, P, sz], i),
+        "ocean_camera_bodies_async": ([P, i, i, i, i, i, P, P, i, i, P, P, P, i, i, P, sz, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -637,6 +646,70 @@ class OceanContext:
         _check(self.lib.ocean_camera_device(self._h, tile, mode, iterations, steps, refine, cam.ctypes.data,
                                             mat.ctypes.data if mat is not None else None, width, height,
                                             ctypes.c_void_p(out_ptr), nbytes), "ocean_camera_device")
+
+    @staticmethod
+    def _body_view_args(box, paint, bodies):
+        """(box float32[6], paint float32[4] or None, records float32[count][stride] or None, stride, count)."""
+        bx = np.ascontiguousarray(box, np.float32).reshape(-1)
+        if bx.shape[0] != 6:
+            raise ValueError(f"box must be float32[6] = (lo, hi), got {bx.shape}")
+        pt = None
+        if paint is not None:
+            pt = np.ascontiguousarray(paint, np.float32).reshape(-1)
+            if pt.shape[0] != BODY_PAINT_FLOATS:
+                raise ValueError(f"paint must be float32[{BODY_PAINT_FLOATS}] = (r, g, b, ka), got {pt.shape}")
+        if bodies is None or len(bodies) == 0:
+            return bx, pt, None, BODY_STRIDE_MIN, 0
+        rec = np.ascontiguousarray(bodies, np.float32)
+        if rec.ndim != 2 or rec.shape[1] < BODY_STRIDE_MIN:
+            raise ValueError(f"bodies must be float32[count][stride >= 10] = (c, q, s, ...), got {rec.shape}")
+        return bx, pt, rec, rec.shape[1], rec.shape[0]
+
+    def camera_bodies(self, camera, width: int, height: int, bodies, box=(-0.5, -0.5, -0.5, 0.5, 0.5, 0.5),
+                      paint=(0.8, 0.8, 0.8, 1.0), mode: int = CAMERA_COLOR, material=None, tile: int = 0,
+                      iterations: int = 4, steps: int = 64, refine: int = 8) -> np.ndarray:
+        """camera() with the boxes of `bodies` in front of the water (ocean.h ocean_camera_bodies), blocking.  bodies:
+        float32[count][stride], stride in [10, 64], a record's first ten floats (c, q, s) as body_buoyancy takes them
+        (the state or the result of body_step serves as it is), or None; box: (lo, hi) of the one box all bodies share,
+        in the body frame before the scale; paint: (r, g, b, ka), read in the colour modes.  A body pixel has the
+        status RAY_BODY: HITS (te, 0, 0, 3, normal, index), RANGE te, COLOR the painted box under the sky and the sun."""
+        cam, mat, shape, nbytes = self._camera_args(camera, material, mode, width, height)
+        bx, pt, rec, stride, count = self._body_view_args(box, paint, bodies)
+        out = np.empty(shape, np.float32)
+        _check(self.lib.ocean_camera_bodies(self._h, tile, mode, iterations, steps, refine, cam.ctypes.data,
+                                            mat.ctypes.data if mat is not None else None, width, height, bx.ctypes.data,
+                                            pt.ctypes.data if pt is not None else None,
+                                            rec.ctypes.data if rec is not None else None, stride, count,
+                                            out.ctypes.data, nbytes), "ocean_camera_bodies")
+        return out
+
+    def camera_bodies_async(self, camera, width: int, height: int, bodies, box=(-0.5, -0.5, -0.5, 0.5, 0.5, 0.5),
+                            paint=(0.8, 0.8, 0.8, 1.0), mode: int = CAMERA_COLOR, material=None, tile: int = 0,
+                            iterations: int = 4, steps: int = 64, refine: int = 8, buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_camera_bodies_async), as camera_async: `bodies` is consumed by the call."""
+        cam, mat, shape, nbytes = self._camera_args(camera, material, mode, width, height)
+        bx, pt, rec, stride, count = self._body_view_args(box, paint, bodies)
+        return Readback(self, shape, nbytes, "ocean_camera_bodies_async",
+                        lambda dst, req: self.lib.ocean_camera_bodies_async(
+                            self._h, tile, mode, iterations, steps, refine, cam.ctypes.data,
+                            mat.ctypes.data if mat is not None else None, width, height, bx.ctypes.data,
+                            pt.ctypes.data if pt is not None else None, rec.ctypes.data if rec is not None else None,
+                            stride, count, dst, nbytes, req), buf)
+
+    def camera_bodies_device(self, out_ptr: int, camera, width: int, height: int, bodies_ptr: int, count: int,
+                             stride: int = 32, box=(-0.5, -0.5, -0.5, 0.5, 0.5, 0.5), paint=(0.8, 0.8, 0.8, 1.0),
+                             mode: int = CAMERA_COLOR, material=None, tile: int = 0, iterations: int = 4,
+                             steps: int = 64, refine: int = 8) -> None:
+        """The device-pointer form (ocean_camera_bodies_device): `bodies_ptr` holds `count` records `stride` floats
+        apart on this context's device (32: where body_step_device left them), `out_ptr` is 16-B aligned; async on the
+        context's stream, after the queued steps.  camera, material, box and paint are host arrays."""
+        cam, mat, _, nbytes = self._camera_args(camera, material, mode, width, height)
+        bx, pt, _, _, _ = self._body_view_args(box, paint, None)
+        _check(self.lib.ocean_camera_bodies_device(self._h, tile, mode, iterations, steps, refine, cam.ctypes.data,
+                                                   mat.ctypes.data if mat is not None else None, width, height,
+                                                   bx.ctypes.data, pt.ctypes.data if pt is not None else None,
+                                                   ctypes.c_void_p(bodies_ptr) if bodies_ptr else None, stride, count,
+                                                   ctypes.c_void_p(out_ptr), nbytes), "ocean_camera_bodies_device")
 
     @staticmethod
     def grid_points(x0: float, z0: float, dx: float, dz: float, nx: int, ny: int) -> np.ndarray:
@@ -1475,6 +1548,17 @@ class WaterBody:
             material = _material()
         cam = look_at_camera(eye, target, up, fov_y, width, height, 0.0, max_distance)
         return self.ctx.camera(cam, width, height, mode, material, tile, iterations, steps, refine)
+
+    def camera_bodies(self, eye, target, width: int, height: int, bodies, box=(-0.5, -0.5, -0.5, 0.5, 0.5, 0.5),
+                      paint=(0.8, 0.8, 0.8, 1.0), fov_y: float = 1.0, max_distance: float = 2000.0,
+                      mode: int = CAMERA_COLOR, material=None, up=(0.0, 1.0, 0.0), iterations: int = 4, steps: int = 64,
+                      refine: int = 8, tile: int = 0) -> np.ndarray:
+        """Camera() with the boxes of `bodies` in the picture (OceanContext.camera_bodies over look_at_camera): what a
+        vessel's camera or lidar sees of the sea and of the hulls StepBodies moves."""
+        if material is None and mode in (CAMERA_COLOR, CAMERA_COLOR | CAMERA_SKY_LUT):
+            material = _material()
+        cam = look_at_camera(eye, target, up, fov_y, width, height, 0.0, max_distance)
+        return self.ctx.camera_bodies(cam, width, height, bodies, box, paint, mode, material, tile, iterations, steps, refine)
 
     def Whitecaps(self, threshold: float, x0: float, z0: float, dx: float, dz: float, nx: int, ny: int,
                   capacity: int = 4096, lod: float = 0.0, tile: int = 0):
