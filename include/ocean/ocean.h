@@ -87,7 +87,9 @@ extern "C" {
  *      OCEAN_SPRAY_MAX_STAGED, OCEAN_SPRAY_MAX_SUBSTEPS, ocean_spray_step, ocean_spray_step_device,
  *      ocean_spray_step_async.
  *      Added later within version 4 in the same way: OCEAN_RAY_BODY, OCEAN_BODY_PAINT_FLOATS, ocean_camera_bodies,
- *      ocean_camera_bodies_device, ocean_camera_bodies_async. */
+ *      ocean_camera_bodies_device, ocean_camera_bodies_async.
+ *      Added later within version 4 in the same way: OCEAN_CAMERA_LINKS, OCEAN_SCENE_OPTICS_FLOATS, ocean_camera_scene,
+ *      ocean_camera_scene_device, ocean_camera_scene_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -1262,7 +1264,8 @@ int ocean_spray_step_async(ocean_ctx *ctx, int tile, int iterations, int substep
  *   COLOR:  (A_c * (ka * amb_c + LC_c * fmaxf(dot(nw, L), 0)), (float)OCEAN_RAY_BODY), c = r, g, b, with
  *           amb_c = sky(nw.y)_c of the two-colour sky, or SKY(nw)_c with OCEAN_CAMERA_SKY_LUT; dot, L and LC are the
  *           camera's.
- * Limits of the feature: bodies are not reflected in the water, cast no shadow and are not fogged under the water;
+ * Limits of the feature: bodies are not reflected in the water, cast no shadow and are not fogged under the water
+ * (ocean_camera_scene* below adds the three);
  * the library does not inspect records, so a non-unit quaternion distorts the box as the formulas say, and non-finite
  * values give unspecified numbers (never an access outside the textures or the records).
  * Cull and early stop.  The kernel does not test every body per pixel: per 16 x 16-pixel tile it drops the bodies
@@ -1290,11 +1293,87 @@ int ocean_camera_bodies_async(ocean_ctx *ctx, int tile, int mode, int iterations
                               const float *paint, const float *bodies, int stride, int count, float *out, size_t bytes,
                               ocean_readback **req);
 
+/* Camera views in which the water sees the bodies: shadows on it, reflections in it, hulls through it.
+ * ocean_camera_bodies* puts the hulls in front of the sea, but the sea does not know they are there: nothing shows
+ * where a hull meets the water.  The fragment stage of Water.shader reads scene geometry in three places, which
+ * ocean_camera* had to define away: shadowFactor (:357, used at :368 and :370, with _ShadowsColor and
+ * _ShadowsIntensity), UnderwaterView (:143-172, with _WaterFogDensity) and EnvironmentReflections (:181-188).  Here the
+ * geometry is the bodies', and the three are evaluated at every water pixel.
+ *
+ * Every argument but `optics` and `mode`, the three forms, their ordering and staging, the slot rule of the async form,
+ * the alignment rules, the state rules and the kernel-stats kind are exactly ocean_camera_bodies*'s.  New:
+ *   optics: float[OCEAN_SCENE_OPTICS_FLOATS] = (SH.r, SH.g, SH.b, SI, WF, reach): [_ShadowsColor], [_ShadowsIntensity],
+ *           [_WaterFogDensity], and the length searched by the two secondary rays.  A host array in every form, passed
+ *           to the kernel by value and read in every mode: never NULL.
+ *   mode:   OCEAN_CAMERA_COLOR, OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT or OCEAN_CAMERA_LINKS (valid here only).
+ *           `material` is required in all three (LINKS takes L and the normal's lod from it), `paint` in the two
+ *           colour modes; in LINKS mode it may be NULL.
+ *   bytes:  width * height * 16 in every mode.
+ *
+ * All arithmetic is fp32, one rounding per operation in the order written (no fused multiply-add); sqrtf and / are
+ * correctly rounded.  meet(p, r, s0, s1) is the body test of ocean_camera_bodies with o := p, d := r, t0 := s0,
+ * t1 := s1: the met body of smallest te, the lowest b on ties, its te and its nw (r is used as it is, whatever its
+ * length); it also serves as "any body met".  paintc(nw)_c = A_c * (ka * amb(nw)_c + LC_c * fmaxf(dot(nw, L), 0)) is
+ * the body pixel's colour, amb following the sky mode.  Per pixel, o, d, t0, t1, R_k and t* are the camera's, and
+ * (b1, te1, nw1) = meet(o, d, t0, t1) is ocean_camera_bodies' own test.  A body pixel, a MISS pixel and a SUBMERGED
+ * pixel are exactly ocean_camera_bodies' in the colour modes.  A water HIT pixel (HIT and not a body pixel) has
+ *       q = (o.x + t* * d.x, o.y + t* * d.y, o.z + t* * d.z)
+ * and n, foam, eta, V, ndv, F, g, ry and the rest of the camera's "Colour of a hit".  Then
+ *   through the water (UnderwaterView without the screen-space offset: the ray goes straight on):
+ *       if b1 >= 0 (so te1 >= t*):  depth = te1 - t*;  fog = exp2f(-(WF * depth));
+ *                                   base_c = C_c + fog * (paintc(nw1)_c - C_c)
+ *       else:                       base_c = C_c
+ *       refraction_c = base_c + (g * SS_c) * LC_c
+ *   shadow:
+ *       sf = 0 if L.y > 0 and meet(q, L, 0, reach) meets any body, else sf = 1
+ *   reflection:
+ *       rd = ((2 * ndv) * n.x - V.x, ry, (2 * ndv) * n.z - V.z);   (b2, te2, nw2) = meet(q, rd, 0, reach)
+ *       src_c = paintc(nw2)_c if a body is met, else the camera's sky term: sky(ry)_c, or SKY(rd)_c
+ *       env_c = (src_c * pi) * ke
+ *   composition:
+ *       sf == 1:  reflections_c and e_c are the camera's expressions, unchanged
+ *       sf == 0:  reflections_c = env_c;   m_c = refraction_c + F * (reflections_c - refraction_c);
+ *                 e_c = m_c + SI * (SH_c - m_c)                                                    (:370)
+ *       then the foam lerp (:371) as for the camera; the fourth channel is the status.
+ * A water pixel with sf == 1, b1 < 0 and b2 < 0 is therefore ocean_camera_bodies' pixel bit for bit, and so is the whole
+ * image when count == 0.
+ *   OCEAN_CAMERA_LINKS: out[4k + 0..3] = (sf, (float)b1t, (float)b2, (float)status) for a water HIT pixel, b1t = b1 if
+ *       a body shows through the water, else -1, and b2 = -1 if no body is reflected; a body pixel is
+ *       (1, (float)b, -1, (float)OCEAN_RAY_BODY); MISS and SUBMERGED pixels are (1, -1, -1, (float)status).  Every
+ *       discrete decision of the colour image, and a label image: which hull a pixel's shadow and reflection belong to.
+ * Limits of the feature: shadows are hard (a point sun); bodies do not shadow or reflect each other; the colours seen
+ * through the water or in it are unshadowed; a hull behind a wave crest is fogged by its distance behind the surface,
+ * as the shader's depth difference does; `reach` bounds both secondary rays; exp2f is a third operation, beside powf
+ * and the sky table's atan2f and asinf, whose last bits belong to the device's math library.
+ * Culls.  The primary cull and the early stop are ocean_camera_bodies'.  For the secondary rays the kernel drops, per
+ * 16 x 16-pixel tile, the bodies whose bounding sphere is further than `reach` from the bounding box of the tile's
+ * points q, with a derived margin.  Every result bit is as defined above; only the time differs, and it grows with
+ * `reach`.  OCEAN_CAMERA_CULL=0 makes every body a survivor of both culls.
+ *
+ * All three: OCEAN_E_INVALID_ARG, checked before any device call, for a null `optics`, an `optics` value that is not
+ * finite, reach < 0, the modes OCEAN_CAMERA_HITS and OCEAN_CAMERA_RANGE (ocean_camera_bodies* serves them) and every
+ * other mode not named above, a null `material`, a null `paint` in a colour mode, and everything
+ * ocean_camera_bodies* refuses; then OCEAN_E_STATE and OCEAN_E_UNSUPPORTED as for the camera.  The launch counts as
+ * kind 2 of ocean_kernel_stats / ocean_kernel_name. */
+#define OCEAN_CAMERA_LINKS 3 /* valid only in ocean_camera_scene* */
+#define OCEAN_SCENE_OPTICS_FLOATS 6
+int ocean_camera_scene(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine, const float *camera,
+                       const float *material, int width, int height, const float *box, const float *paint,
+                       const float *optics, const float *bodies, int stride, int count, float *out, size_t bytes);
+int ocean_camera_scene_device(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine,
+                              const float *camera, const float *material, int width, int height, const float *box,
+                              const float *paint, const float *optics, const float *bodies, int stride, int count,
+                              float *out, size_t bytes);
+int ocean_camera_scene_async(ocean_ctx *ctx, int tile, int mode, int iterations, int steps, int refine,
+                             const float *camera, const float *material, int width, int height, const float *box,
+                             const float *paint, const float *optics, const float *bodies, int stride, int count,
+                             float *out, size_t bytes, ocean_readback **req);
+
 /* Readback timing (off after ocean_create): while on, each new ocean_read_async /
  * ocean_read_height_async / ocean_query_surface_async / ocean_surface_grid_async /
  * ocean_body_buoyancy_async / ocean_query_velocity_async / ocean_raycast_async / ocean_body_dynamics_async /
  * ocean_whitecaps_async / ocean_camera_async / ocean_body_step_async / ocean_spray_step_async /
- * ocean_camera_bodies_async request records HIP
+ * ocean_camera_bodies_async / ocean_camera_scene_async request records HIP
  * timing events around its device-to-host copy, for ocean_readback_copy_ms.  Requests made while it is off record only untimed events. */
 int ocean_set_readback_timing(ocean_ctx *ctx, int enable);
 

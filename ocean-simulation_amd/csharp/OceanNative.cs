@@ -235,6 +235,18 @@ namespace OceanHip
         public static extern OceanStatus ocean_camera_bodies_device(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, [In] float[] box, [In] float[] paint, IntPtr bodies, int stride, int count, IntPtr output, UIntPtr bytes);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_camera_bodies_async(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, [In] float[] box, [In] float[] paint, [In] float[] bodies, int stride, int count, IntPtr dst, UIntPtr bytes, out IntPtr request);
+        // Camera views in which the water sees the bodies (added within ABI 4 in the same way): ocean_camera_bodies with the
+        // bodies' shadows on the water, their reflections in it and their submerged parts through it.  optics = 6 floats
+        // (shadow colour r, g, b, shadow intensity, water fog density, reach of the secondary rays); mode CameraColor,
+        // CameraColor | CameraSkyLut or CameraLinks (valid here only: per pixel lit or not, the body seen through the water,
+        // the body reflected, the status); 16 bytes per pixel in every mode; material required, paint in the colour modes.
+        public const int CameraLinks = 3, SceneOpticsFloats = 6;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_camera_scene(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, [In] float[] box, [In] float[] paint, [In] float[] optics, [In] float[] bodies, int stride, int count, [Out] float[] output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_camera_scene_device(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, [In] float[] box, [In] float[] paint, [In] float[] optics, IntPtr bodies, int stride, int count, IntPtr output, UIntPtr bytes);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_camera_scene_async(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, [In] float[] box, [In] float[] paint, [In] float[] optics, [In] float[] bodies, int stride, int count, IntPtr dst, UIntPtr bytes, out IntPtr request);
         // The atmosphere (added within ABI 4 in the same way; ocean.h "The atmosphere"): the three look-up tables of
         // AtmosphereController.cs, owned by the context.  `parameters` = 32 floats (ocean.h names them); the six sizes all 0
         // select the reference's.  ocean_sky_update is the per-frame call; CameraColor | CameraSkyLut then shades the

@@ -358,6 +358,23 @@ namespace OceanHip
             return output;
         }
 
+        // CameraBodies with the water seeing the bodies (ocean.h ocean_camera_scene): their shadows on it, their reflections
+        // in it and their submerged parts through it.  `optics` = (shadow r, g, b, shadow intensity, water fog density, reach
+        // of the secondary rays in metres); mode CameraColor, CameraColor | CameraSkyLut or CameraLinks (per pixel: lit or
+        // not, the body seen through the water, the body reflected, the status).  Four floats per pixel in every mode.
+        public float[] CameraScene(float[] camera, int width, int height, float[] box, float[] paint, float[] optics,
+                                   float[] bodies, float[] material, int stride = 10, int mode = OceanNative.CameraColor,
+                                   int iterations = 4, int steps = 64, int refine = 8)
+        {
+            bool valid = width >= 1 && height >= 1 && (long)width * height <= OceanNative.CameraMaxPixels;
+            var output = new float[valid ? width * height * 4 : 0];
+            int count = bodies == null || stride < 10 ? 0 : (bodies.Length + stride - 10) / stride;
+            OceanNative.Check(OceanNative.ocean_camera_scene(ctx, 0, mode, iterations, steps, refine, camera, material, width,
+                                                             height, box, paint, optics, bodies, stride, count, output,
+                                                             (UIntPtr)(ulong)(output.Length * 4)), "ocean_camera_scene");
+            return output;
+        }
+
         // The atmosphere of AtmosphereController.cs (ocean.h "The atmosphere"): Awake's two tables, with `parameters` =
         // 32 floats (null: the reference's defaults) at the reference's sizes.
         public static readonly float[] DefaultAtmosphere = {

@@ -1,6 +1,6 @@
 // C-ABI layer of liboceanhip.so, the point consumers (ocean.h): surface and velocity queries, surface grids,
-// buoyant bodies, body dynamics, body steps, ray casts, whitecap emitters, spray particles and camera views (with and
-// without the bodies), each in a _device, a blocking host
+// buoyant bodies, body dynamics, body steps, ray casts, whitecap emitters, spray particles and camera views (without
+// the bodies, with them, and with the water seeing them), each in a _device, a blocking host
 // and an _async form; and world sampling and the surface bounds, which keep bodies of their own.
 //
 // A consumer is stated once, as a struct built from its entry's arguments (a "family"), and its three entries
@@ -543,7 +543,9 @@ struct CameraBodies : Camera {
     const float* bodies;
     int stride, count;
 
-    int check(Form form) const {
+    int check(Form form) const { return check_bodies_as(form, state().entry); }
+    // entry: the family's own name (the camera of the scene runs these tests too)
+    int check_bodies_as(Form form, const char* entry) const {
         if (!box) return fail(OCEAN_E_INVALID_ARG, "null box");
         if ((mode == OCEAN_CAMERA_COLOR || mode == kSkyMode) && !paint)
             return fail(OCEAN_E_INVALID_ARG, "the colour modes need a paint");
@@ -555,7 +557,7 @@ struct CameraBodies : Camera {
         if (count < 0 || count > OCEAN_BODY_MAX_BODIES)
             return fail(OCEAN_E_INVALID_ARG, "body count " + std::to_string(count) + " outside [0, OCEAN_BODY_MAX_BODIES]");
         if (count > 0 && !bodies) return fail(OCEAN_E_INVALID_ARG, "null bodies with count > 0");
-        return check_as(form, state().entry, inputs());
+        return check_as(form, entry, inputs());
     }
     StateRule state() const { return {"ocean_camera_bodies", "camera view of", Needs::Nothing, mode == kSkyMode}; }
     StagedInputs inputs() const {
@@ -588,6 +590,60 @@ struct CameraBodies : Camera {
 };
 static_assert(((size_t)OCEAN_BODY_MAX_BODIES * 64) * sizeof(float) <= kSprayInputBytes,
               "a slot's own block pair holds every camera request's bodies");
+
+// Camera views in which the water sees the bodies: the camera with bodies, with the six `optics` floats by value
+// beside the rest.  Its own arguments first (the optics, and its own set of modes), then everything the camera with
+// bodies refuses: OCEAN_CAMERA_LINKS is 16 B per pixel and needs a material, as OCEAN_CAMERA_COLOR does, so those
+// tests run with that mode in its place, but without a paint's being required.
+struct CameraScene : CameraBodies {
+    const float* optics;
+
+    int check(Form form) const {
+        if (!optics) return fail(OCEAN_E_INVALID_ARG, "null optics");
+        for (int k = 0; k < OCEAN_SCENE_OPTICS_FLOATS; ++k)
+            if (!std::isfinite(optics[k])) return fail(OCEAN_E_INVALID_ARG, "optics[" + std::to_string(k) + "] is not finite");
+        if (optics[5] < 0.0f) return fail(OCEAN_E_INVALID_ARG, "optics[5] (reach) is negative");
+        if (mode == OCEAN_CAMERA_HITS || mode == OCEAN_CAMERA_RANGE)
+            return fail(OCEAN_E_INVALID_ARG, "scene mode: OCEAN_CAMERA_HITS and OCEAN_CAMERA_RANGE are ocean_camera_bodies*'s");
+        if (mode != OCEAN_CAMERA_COLOR && mode != kSkyMode && mode != OCEAN_CAMERA_LINKS)
+            return fail(OCEAN_E_INVALID_ARG, "unknown scene mode");
+        if (mode != OCEAN_CAMERA_LINKS) return check_bodies_as(form, state().entry);
+        if (!material) return fail(OCEAN_E_INVALID_ARG, "OCEAN_CAMERA_LINKS needs a material");
+        CameraBodies as = *this;
+        as.mode = OCEAN_CAMERA_COLOR;
+        if (!paint) {  // not required, and not read: any finite paint passes in its place
+            static const float kNoPaint[OCEAN_BODY_PAINT_FLOATS] = {};
+            as.paint = kNoPaint;
+        }
+        return as.check_bodies_as(form, state().entry);
+    }
+    StateRule state() const { return {"ocean_camera_scene", "camera view of", Needs::Nothing, mode == kSkyMode}; }
+    int launch(const float* const* in, float* d_out) const {
+        const float* bounds;
+        if (int r = air_skip_bounds(ctx, tile, &bounds)) return r;
+        ocean::CameraRays cam;
+        ocean::CameraMaterial mat;
+        ocean::BodyBox bx;
+        ocean::BodyPaint pt = {};
+        ocean::SceneOptics op;
+        std::copy(camera, camera + OCEAN_CAMERA_FLOATS, cam.c);
+        std::copy(material, material + OCEAN_CAMERA_MATERIAL_FLOATS, mat.m);
+        std::copy(box, box + 6, bx.b);
+        if (paint) std::copy(paint, paint + OCEAN_BODY_PAINT_FLOATS, pt.p);
+        std::copy(optics, optics + OCEAN_SCENE_OPTICS_FLOATS, op.o);
+        const bool sky = mode == kSkyMode;
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] {
+                         return ocean::launch_camera_scene(v, tile, mode, iterations, steps, refine, bounds, cam, mat,
+                                                           sky ? ctx->atm.view(OCEAN_LUT_SKYVIEW) : ocean::LutView{},
+                                                           sky ? ctx->atm.params.p[26] : 0.0f, bx, pt, op,
+                                                           count > 0 ? in[0] : nullptr, stride, count,
+                                                           ctx->opt.camera_cull != 0, width, height, d_out, ctx->stream);
+                     },
+                     "camera_scene");
+    }
+};
 
 // Spray particles: the pool, (capacity + 1) records of 32 B, and the emitter list or none -> the stepped pool, with
 // the sixteen `spray` floats by value.  As for the whitecaps, what does not need the context is checked first, the
@@ -820,6 +876,32 @@ int ocean_camera_bodies_async(ocean_ctx* ctx, int tile, int mode, int iterations
                               const float* bodies, int stride, int count, float* out, size_t bytes, ocean_readback** req) {
     return async_form(CameraBodies{{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes},
                                    box, paint, bodies, stride, count},
+                      req);
+}
+
+int ocean_camera_scene_device(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, int refine, const float* camera,
+                              const float* material, int width, int height, const float* box, const float* paint,
+                              const float* optics, const float* bodies, int stride, int count, float* out, size_t bytes) {
+    return device_form(CameraScene{{{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes},
+                                    box, paint, bodies, stride, count},
+                                   optics});
+}
+
+int ocean_camera_scene(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, int refine, const float* camera,
+                       const float* material, int width, int height, const float* box, const float* paint,
+                       const float* optics, const float* bodies, int stride, int count, float* out, size_t bytes) {
+    return host_form(CameraScene{{{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes},
+                                  box, paint, bodies, stride, count},
+                                 optics});
+}
+
+int ocean_camera_scene_async(ocean_ctx* ctx, int tile, int mode, int iterations, int steps, int refine, const float* camera,
+                             const float* material, int width, int height, const float* box, const float* paint,
+                             const float* optics, const float* bodies, int stride, int count, float* out, size_t bytes,
+                             ocean_readback** req) {
+    return async_form(CameraScene{{{ctx, tile, mode, iterations, steps, refine, camera, material, width, height, out, bytes},
+                                   box, paint, bodies, stride, count},
+                                  optics},
                       req);
 }
 

@@ -145,7 +145,7 @@ struct ocean_options {
     int prune = 1;          // OCEAN_PRUNE=0: passes AQ / BQ run every row of a band-limited cascade (dense schedule)
     int ray_bounds = 1;     // OCEAN_RAY_BOUNDS=0: the ray kernel samples every node (no air skip, no bounds launches)
     int camera_tile = 1;    // OCEAN_CAMERA_TILE=0: the camera kernel maps pixels to lanes row-linearly, not in 8 x 8 tiles (A/B)
-    int camera_cull = 1;    // OCEAN_CAMERA_CULL=0: ocean_camera_bodies* hands every body to every tile's slab tests (no cull; A/B)
+    int camera_cull = 1;    // OCEAN_CAMERA_CULL=0: ocean_camera_bodies* and ocean_camera_scene* hand every body to every tile's slab tests (no cull; A/B)
     int max_groups = 0;     // OCEAN_MAX_GROUPS: at most this many workgroups per persistent launch (the transform passes
                             // of fftq / fft3 / fft4k / fft2.hip), so that their item loops iterate at small shapes; 0: no cap
 

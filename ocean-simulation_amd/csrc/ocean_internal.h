@@ -265,6 +265,19 @@ hipError_t launch_camera_bodies(const DevView& v, int tile, int mode, int iterat
                                 const float* bounds, const CameraRays& cam, const CameraMaterial& mt, const LutView& sky,
                                 float sun_size, const BodyBox& box, const BodyPaint& paint, const float* bodies, int stride,
                                 int count, bool cull, int width, int height, float* out, hipStream_t s);
+// view.hip: camera views in which the water sees the bodies (ocean_camera_scene*): launch_camera_bodies' colour image
+// with the bodies' shadows, reflections and fogged submerged parts at the water pixels, or the OCEAN_CAMERA_LINKS
+// record of those decisions; mode is OCEAN_CAMERA_COLOR, OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT or
+// OCEAN_CAMERA_LINKS, 16 B per pixel in each.  The six `optics` floats of ocean.h travel as a kernel argument.
+// cull: both culls (false: every body reaches every ray's slab test; the same image).
+struct SceneOptics {
+    float o[OCEAN_SCENE_OPTICS_FLOATS];
+};
+hipError_t launch_camera_scene(const DevView& v, int tile, int mode, int iterations, int steps, int refine,
+                               const float* bounds, const CameraRays& cam, const CameraMaterial& mt, const LutView& sky,
+                               float sun_size, const BodyBox& box, const BodyPaint& paint, const SceneOptics& optics,
+                               const float* bodies, int stride, int count, bool cull, int width, int height, float* out,
+                               hipStream_t s);
 
 // whitecaps.hip: whitecap emitters (ocean_whitecaps*), device pointers: out = (capacity + 1) records of 32 B, the
 // header then the selected nodes of the grid in ascending node order, 16-B aligned; vel = the context's VEL or null

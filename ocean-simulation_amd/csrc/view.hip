@@ -51,12 +51,23 @@ __device__ __forceinline__ float3 sky_lut(const LutView& sk, float rx, float ry,
     return make_float3(2.0f * t.x, 2.0f * t.y, 2.0f * t.z);
 }
 
+// What the bodies add to the colour of a water pixel (ocean.h, ocean_camera_scene): the body seen through the water
+// and its fog, the body in the mirror, the shadow.
+struct SceneTerms {
+    bool through, mirrored, shadowed;
+    float fog;
+    float seen[3], mirror[3];  // paintc of the body seen through the water, and of the reflected one
+    float sh[3], si;           // _ShadowsColor, _ShadowsIntensity
+};
+
 // The colour of a hit pixel (ocean.h, "Colour of a hit"): the ray direction d, the normal n, the wave height and
 // the foam at the point met.  has_foam: the context has DERIV and TURB (not DISPLACEMENT_ONLY).
 // SKY: the sky is sky_lut over `sk`, else the two-colour sky of the material.
-template <bool SKY>
+// SCENE: with the terms of `sc` (ocean_camera_scene); without, every statement is ocean_camera's.
+template <bool SKY, bool SCENE = false>
 __device__ __forceinline__ float3 shade_hit(const CameraMaterial& mt, float dx, float dy, float dz, float nx, float ny,
-                                            float nz, float height, float foam, bool has_foam, const LutView& sk) {
+                                            float nz, float height, float foam, bool has_foam, const LutView& sk,
+                                            const SceneTerms& sc = SceneTerms{}) {
     const float* m = mt.m;
     const float r0 = m[3], rough = m[6];
     const float lx = m[20], ly = m[21], lz = m[22];
@@ -78,7 +89,7 @@ __device__ __forceinline__ float3 shade_hit(const CameraMaterial& mt, float dx, 
     // the sky at -reflect(V, n) = 2 dot(n, V) n - V: only its y is needed
     const float ry = (2.0f * ndv) * ny - vy;
     float env_sky[3] = {0.0f, 0.0f, 0.0f};
-    if (SKY) {  // all of -reflect(V, n)
+    if (SKY && !(SCENE && sc.mirrored)) {  // all of -reflect(V, n)
         const float3 e = sky_lut(sk, (2.0f * ndv) * nx - vx, ry, (2.0f * ndv) * nz - vz);
         env_sky[0] = e.x, env_sky[1] = e.y, env_sky[2] = e.z;
     }
@@ -104,12 +115,17 @@ __device__ __forceinline__ float3 shade_hit(const CameraMaterial& mt, float dx, 
     float out[3];
     for (int c = 0; c < 3; ++c) {
         const float light = m[23 + c];
-        const float refr = m[c] + (coeff * m[12 + c]) * light;
-        const float env = ((SKY ? env_sky[c] : sky(m[26 + c], m[29 + c], ry)) * kPi) * m[10];
+        float base = m[c];
+        if (SCENE && sc.through) base = m[c] + sc.fog * (sc.seen[c] - m[c]);
+        const float refr = base + (coeff * m[12 + c]) * light;
+        float src = SKY ? env_sky[c] : sky(m[26 + c], m[29 + c], ry);
+        if (SCENE && sc.mirrored) src = sc.mirror[c];
+        const float env = (src * kPi) * m[10];
         const float cook = sun_up ? ((light * dist) * geom) / ctden : 0.0f;
         const float ashk = sun_up ? light * as : 0.0f;
-        const float refl = env + (cook + ashk * sndv) * m[11];
+        const float refl = SCENE && sc.shadowed ? env : env + (cook + ashk * sndv) * m[11];
         float e = refr + fresnel * (refl - refr);
+        if (SCENE && sc.shadowed) e = e + sc.si * (sc.sh[c] - e);
         if (foamy) e = e + m[19] * (m[16 + c] - e);
         out[c] = e;
     }
@@ -290,18 +306,131 @@ __device__ __forceinline__ bool slab(float l, float h, float ob, float db, float
 constexpr float kCullMargin = 0x1p-16f;   // of S, above
 constexpr float kUnitQuat = 0x1p-10f;     // |q|^2 within this of 1, above
 
-template <int MODE, bool SKY>
-__global__ __launch_bounds__(256) void k_camera_bodies(DevView v, int tile, int iterations, int steps, int refine,
-                                                       const float* __restrict__ bounds, CameraRays cam, CameraMaterial mt,
-                                                       LutView sk, float sun_size, BodyBox box, BodyPaint paint,
-                                                       const float* __restrict__ bodies, int stride, int count, int cull,
-                                                       int width, int height, float* __restrict__ out) {
-    __shared__ BodySurvivor s_body[256];
-    __shared__ int s_count[4];
+// Record b of `bodies` as a survivor, but for ob: what the slab test reads of the body that does not depend on where
+// the ray starts (l, h: the statements of ocean.h), and the body's origin c.
+__device__ __forceinline__ BodySurvivor body_record(const float* __restrict__ bodies, int stride, int b, const BodyBox& box,
+                                                    Vec3& c) {
+    const float* B = bodies + (size_t)b * stride;
+    const float sx = B[7], sy = B[8], sz = B[9];
+    c.x = B[0], c.y = B[1], c.z = B[2];
+    BodySurvivor sv = {};
+    sv.ux = B[3], sv.uy = B[4], sv.uz = B[5], sv.qw = B[6];
+    sv.lx = sx * box.b[0], sv.ly = sy * box.b[1], sv.lz = sz * box.b[2];
+    sv.hx = sx * box.b[3], sv.hy = sy * box.b[4], sv.hz = sz * box.b[5];
+    sv.b = b;
+    return sv;
+}
+
+// The body's bounding sphere ("the sphere", above): r = ctr - c, its radius before the margin, |bc|_1 + hd for S, and
+// whether |q|^2 is within kUnitQuat of 1 (false for a NaN: such a body is a survivor of every cull).
+struct BodySphere {
+    Vec3 r;
+    float rad, size;
+    bool unit;
+};
+__device__ __forceinline__ BodySphere body_sphere(const BodySurvivor& sv) {
+    const float bx = 0.5f * (sv.lx + sv.hx), by = 0.5f * (sv.ly + sv.hy), bz = 0.5f * (sv.lz + sv.hz);
+    const float ex = 0.5f * (sv.hx - sv.lx), ey = 0.5f * (sv.hy - sv.ly), ez = 0.5f * (sv.hz - sv.lz);
+    const float hd = sqrtf((ex * ex + ey * ey) + ez * ez);
+    const float bc1 = (fabsf(bx) + fabsf(by)) + fabsf(bz);
+    const float qq = ((sv.ux * sv.ux + sv.uy * sv.uy) + sv.uz * sv.uz) + sv.qw * sv.qw;
+    BodySphere sp;
+    sp.r = rotate(sv.ux, sv.uy, sv.uz, sv.qw, bx, by, bz);
+    sp.rad = hd * (1.0f + 0x1p-8f) + bc1 * 0x1p-7f;
+    sp.size = bc1 + hd;
+    sp.unit = fabsf(qq - 1.0f) <= kUnitQuat;
+    return sp;
+}
+
+// The kept records of one chunk into s_body in ascending lane order, so in ascending b; their number.  Two barriers:
+// every lane of the workgroup comes here, with w its wave and l its lane.
+__device__ __forceinline__ int compact_survivors(bool keep, const BodySurvivor& sv, BodySurvivor* s_body, int* s_count,
+                                                 int w, int l) {
+    const unsigned long long mask = __ballot(keep);
+    if (l == 0) s_count[w] = __popcll(mask);
+    __syncthreads();  // the counts are there; every lane is done with the chunk before
+    int first = 0, total = 0;
+    for (int k = 0; k < 4; ++k) {
+        const int n = s_count[k];
+        first += k < w ? n : 0;
+        total += n;
+    }
+    if (keep) s_body[first + __popcll(mask & ((1ull << l) - 1ull))] = sv;
+    __syncthreads();  // the survivors are there
+    return total;
+}
+
+// The slab test of ocean.h for one body: the ray from ob (in the body frame) along d (in the world's), met within
+// [t0, t1] or not, and what the normal needs.
+struct SlabMeet {
+    bool met;
+    float tn, nx, ny;
+    Vec3 db;
+};
+__device__ __forceinline__ SlabMeet meet_box(const BodySurvivor& q, float obx, float oby, float obz, const Vec3& d,
+                                             float t0, float t1) {
+    SlabMeet m;
+    m.db = rotate(-q.ux, -q.uy, -q.uz, q.qw, d.x, d.y, d.z);
+    float nz, fx, fy, fz;
+    bool met = slab(q.lx, q.hx, obx, m.db.x, m.nx, fx);
+    met = slab(q.ly, q.hy, oby, m.db.y, m.ny, fy) && met;
+    met = slab(q.lz, q.hz, obz, m.db.z, nz, fz) && met;
+    m.tn = fmaxf(fmaxf(m.nx, m.ny), nz);
+    const float tf = fminf(fminf(fx, fy), fz);
+    m.met = met && m.tn <= tf && tf >= t0 && m.tn <= t1;
+    return m;
+}
+
+// The nearest body met so far (ocean.h: the met body of smallest te, the lowest b on ties): b = -1 for none.
+struct BodyMeet {
+    int b;
+    float te;
+    Vec3 nw;
+};
+__device__ __forceinline__ BodyMeet no_body() { return BodyMeet{-1, __builtin_inff(), Vec3{0.0f, 0.0f, 0.0f}}; }
+
+// Body q, tested as m says, against the nearest so far; the bodies come in ascending b, so the strict `te <` keeps
+// the lowest b on ties.  The normal is formed for a new nearest body only.
+__device__ __forceinline__ void keep_nearer(const BodySurvivor& q, const SlabMeet& m, const Vec3& d, float t0,
+                                            BodyMeet& best) {
+    const float te = fmaxf(m.tn, t0);
+    if (m.met && te < best.te) {
+        best.te = te;
+        best.b = q.b;
+        if (m.tn >= t0) {
+            const bool on_x = m.nx == m.tn, on_y = !on_x && m.ny == m.tn;
+            const float dbx = m.db.x, dby = m.db.y, dbz = m.db.z;  // values: a select of members is one of addresses
+            const float dbi = on_x ? dbx : on_y ? dby : dbz;
+            const float sign = dbi > 0.0f ? -1.0f : 1.0f;
+            best.nw = rotate(q.ux, q.uy, q.uz, q.qw, on_x ? sign : 0.0f, on_y ? sign : 0.0f, on_x || on_y ? 0.0f : sign);
+        } else {  // the ray starts inside the box
+            best.nw.x = -d.x, best.nw.y = -d.y, best.nw.z = -d.z;
+        }
+    }
+}
+
+// paintc(nw) of ocean.h, the colour of a body's face with the world normal nw:
+// A_c * (ka * amb(nw)_c + LC_c * fmaxf(dot(nw, L), 0)), amb the two-colour sky at nw.y or, with SKY, the table at nw.
+template <bool SKY>
+__device__ __forceinline__ void paint_colour(const CameraMaterial& mt, const BodyPaint& paint, const LutView& sk,
+                                             const Vec3& nw, float* rgb) {
+    float amb[3];
+    if (SKY) {
+        const float3 e = sky_lut(sk, nw.x, nw.y, nw.z);
+        amb[0] = e.x, amb[1] = e.y, amb[2] = e.z;
+    } else {
+        for (int c = 0; c < 3; ++c) amb[c] = sky(mt.m[26 + c], mt.m[29 + c], nw.y);
+    }
+    const float lit = fmaxf(dot3(nw.x, nw.y, nw.z, mt.m[20], mt.m[21], mt.m[22]), 0.0f);
+    for (int c = 0; c < 3; ++c) rgb[c] = paint.p[c] * (paint.p[3] * amb[c] + mt.m[23 + c] * lit);
+}
+
+// The body of the pixel whose ray from the eye runs along d, in the 16 x 16 tile at (i0, j0): the cull per chunk, the
+// compaction and the slab tests of the comment above.  Every lane of the workgroup comes here (barriers inside).
+__device__ __forceinline__ BodyMeet primary_body(const CameraRays& cam, const BodyBox& box,
+                                                 const float* __restrict__ bodies, int stride, int count, int cull, int i0,
+                                                 int j0, const Vec3& d, BodySurvivor* s_body, int* s_count) {
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    const int i0 = blockIdx.x * 16, j0 = blockIdx.y * 16;
-    const int i = i0 + (w & 1) * 8 + (l & 7), j = j0 + (w >> 1) * 8 + (l >> 3);
-    const Vec3 d = pixel_direction(cam, (float)i, (float)j);
     const float ox = cam.c[0], oy = cam.c[1], oz = cam.c[2], t0 = cam.c[12], t1 = cam.c[13];
 
     // the tile's cone: axis, cos and sin of its half angle
@@ -316,110 +445,251 @@ __global__ __launch_bounds__(256) void k_camera_bodies(DevView v, int tile, int 
     const bool culling = cull != 0 && ct >= 0.5f;
 
     // the pixel's body: the met body of smallest te, the lowest b on ties
-    float best_te = __builtin_inff(), nwx = 0.0f, nwy = 0.0f, nwz = 0.0f;
-    int best_b = -1;
-    if (!(t1 < t0)) {  // else no body is met
-        for (int base = 0; base < count; base += 256) {
-            const int b = base + (int)threadIdx.x;
-            bool keep = false;
-            BodySurvivor sv = {};
-            if (b < count) {
-                const float* B = bodies + (size_t)b * stride;
-                const float cx = B[0], cy = B[1], cz = B[2], sx = B[7], sy = B[8], sz = B[9];
-                sv.ux = B[3], sv.uy = B[4], sv.uz = B[5], sv.qw = B[6];
-                const Vec3 ob = rotate(-sv.ux, -sv.uy, -sv.uz, sv.qw, ox - cx, oy - cy, oz - cz);
-                sv.obx = ob.x, sv.oby = ob.y, sv.obz = ob.z;
-                sv.lx = sx * box.b[0], sv.ly = sy * box.b[1], sv.lz = sz * box.b[2];
-                sv.hx = sx * box.b[3], sv.hy = sy * box.b[4], sv.hz = sz * box.b[5];
-                sv.b = b;
-                keep = true;
-                if (culling) {
-                    const float bx = 0.5f * (sv.lx + sv.hx), by = 0.5f * (sv.ly + sv.hy), bz = 0.5f * (sv.lz + sv.hz);
-                    const float ex = 0.5f * (sv.hx - sv.lx), ey = 0.5f * (sv.hy - sv.ly), ez = 0.5f * (sv.hz - sv.lz);
-                    const float hd = sqrtf((ex * ex + ey * ey) + ez * ez);
-                    const float bc1 = (fabsf(bx) + fabsf(by)) + fabsf(bz);
-                    const Vec3 r = rotate(sv.ux, sv.uy, sv.uz, sv.qw, bx, by, bz);
-                    const float vx = (cx - ox) + r.x, vy = (cy - oy) + r.y, vz = (cz - oz) + r.z;
-                    const float S = (((fabsf(vx) + fabsf(vy)) + fabsf(vz)) + bc1) + hd;
-                    const float rad = (hd * (1.0f + 0x1p-8f) + bc1 * 0x1p-7f) + kCullMargin * S;
-                    const float x = dot3(vx, vy, vz, ax.x, ax.y, ax.z);
-                    const float px = vy * ax.z - vz * ax.y, py = vz * ax.x - vx * ax.z, pz = vx * ax.y - vy * ax.x;
-                    const float y = sqrtf((px * px + py * py) + pz * pz);
-                    const float dist = sqrtf((vx * vx + vy * vy) + vz * vz);
-                    const float qq = ((sv.ux * sv.ux + sv.uy * sv.uy) + sv.uz * sv.uz) + sv.qw * sv.qw;
-                    const bool off = y * ct - x * st > rad || dist - rad > t1 || dist + rad < t0;
-                    keep = !(off && fabsf(qq - 1.0f) <= kUnitQuat);
-                }
-            }
-            const unsigned long long mask = __ballot(keep);
-            if (l == 0) s_count[w] = __popcll(mask);
-            __syncthreads();  // the counts are there; every lane is done with the chunk before
-            int first = 0, total = 0;
-            for (int k = 0; k < 4; ++k) {
-                const int n = s_count[k];
-                first += k < w ? n : 0;
-                total += n;
-            }
-            if (keep) s_body[first + __popcll(mask & ((1ull << l) - 1ull))] = sv;
-            __syncthreads();  // the survivors are there
-
-            for (int s = 0; s < total; ++s) {
-                const BodySurvivor& q = s_body[s];  // one address for the wave: a broadcast
-                const Vec3 db = rotate(-q.ux, -q.uy, -q.uz, q.qw, d.x, d.y, d.z);
-                float nx, ny, nz, fx, fy, fz;
-                bool met = slab(q.lx, q.hx, q.obx, db.x, nx, fx);
-                met = slab(q.ly, q.hy, q.oby, db.y, ny, fy) && met;
-                met = slab(q.lz, q.hz, q.obz, db.z, nz, fz) && met;
-                const float tn = fmaxf(fmaxf(nx, ny), nz), tf = fminf(fminf(fx, fy), fz);
-                met = met && tn <= tf && tf >= t0 && tn <= t1;
-                const float te = fmaxf(tn, t0);
-                if (met && te < best_te) {
-                    best_te = te;
-                    best_b = q.b;
-                    if (tn >= t0) {
-                        const bool on_x = nx == tn, on_y = !on_x && ny == tn;
-                        const float dbi = on_x ? db.x : on_y ? db.y : db.z;
-                        const float sign = dbi > 0.0f ? -1.0f : 1.0f;
-                        const Vec3 nw = rotate(q.ux, q.uy, q.uz, q.qw, on_x ? sign : 0.0f, on_y ? sign : 0.0f,
-                                               on_x || on_y ? 0.0f : sign);
-                        nwx = nw.x, nwy = nw.y, nwz = nw.z;
-                    } else {  // the eye is inside the box
-                        nwx = -d.x, nwy = -d.y, nwz = -d.z;
-                    }
-                }
+    BodyMeet best = no_body();
+    if (t1 < t0) return best;  // no body is met (uniform: before any barrier)
+    for (int base = 0; base < count; base += 256) {
+        const int b = base + (int)threadIdx.x;
+        bool keep = false;
+        BodySurvivor sv = {};
+        if (b < count) {
+            Vec3 c;
+            sv = body_record(bodies, stride, b, box, c);
+            const Vec3 ob = rotate(-sv.ux, -sv.uy, -sv.uz, sv.qw, ox - c.x, oy - c.y, oz - c.z);
+            sv.obx = ob.x, sv.oby = ob.y, sv.obz = ob.z;
+            keep = true;
+            if (culling) {
+                const BodySphere sp = body_sphere(sv);
+                const float vx = (c.x - ox) + sp.r.x, vy = (c.y - oy) + sp.r.y, vz = (c.z - oz) + sp.r.z;
+                const float S = ((fabsf(vx) + fabsf(vy)) + fabsf(vz)) + sp.size;
+                const float rad = sp.rad + kCullMargin * S;
+                const float x = dot3(vx, vy, vz, ax.x, ax.y, ax.z);
+                const float px = vy * ax.z - vz * ax.y, py = vz * ax.x - vx * ax.z, pz = vx * ax.y - vy * ax.x;
+                const float y = sqrtf((px * px + py * py) + pz * pz);
+                const float dist = sqrtf((vx * vx + vy * vy) + vz * vz);
+                const bool off = y * ct - x * st > rad || dist - rad > t1 || dist + rad < t0;
+                keep = !(off && sp.unit);
             }
         }
+        const int total = compact_survivors(keep, sv, s_body, s_count, w, l);
+        for (int s = 0; s < total; ++s) {
+            const BodySurvivor& q = s_body[s];  // one address for the wave: a broadcast
+            keep_nearer(q, meet_box(q, q.obx, q.oby, q.obz, d, t0, t1), d, t0, best);
+        }
     }
+    return best;
+}
+
+// A body pixel of ocean_camera_bodies in MODE (element k of `out`).
+template <int MODE, bool SKY>
+__device__ __forceinline__ void body_pixel(const CameraMaterial& mt, const BodyPaint& paint, const LutView& sk,
+                                           const BodyMeet& bm, size_t k, float* __restrict__ out) {
+    if (MODE == OCEAN_CAMERA_RANGE) {
+        out[k] = bm.te;
+    } else if (MODE == OCEAN_CAMERA_HITS) {
+        float4* o = reinterpret_cast<float4*>(out) + 2 * k;
+        o[0] = make_float4(bm.te, 0.0f, 0.0f, (float)OCEAN_RAY_BODY);
+        o[1] = make_float4(bm.nw.x, bm.nw.y, bm.nw.z, (float)bm.b);
+    } else {
+        float rgb[3];
+        paint_colour<SKY>(mt, paint, sk, bm.nw, rgb);
+        reinterpret_cast<float4*>(out)[k] = make_float4(rgb[0], rgb[1], rgb[2], (float)OCEAN_RAY_BODY);
+    }
+}
+
+// Whether the pixel whose ray met the water as `m` says and the body `bm` is a body pixel (ocean.h: a body is met and
+// the water is missed or met behind it; water wins ties, SUBMERGED stays).
+__device__ __forceinline__ bool body_in_front(const BodyMeet& bm, const RayMeet& m) {
+    return bm.b >= 0 && (m.status == OCEAN_RAY_BODY || m.status == OCEAN_RAY_MISS ||
+                         (m.status == OCEAN_RAY_HIT && bm.te < m.t));
+}
+
+template <int MODE, bool SKY>
+__global__ __launch_bounds__(256) void k_camera_bodies(DevView v, int tile, int iterations, int steps, int refine,
+                                                       const float* __restrict__ bounds, CameraRays cam, CameraMaterial mt,
+                                                       LutView sk, float sun_size, BodyBox box, BodyPaint paint,
+                                                       const float* __restrict__ bodies, int stride, int count, int cull,
+                                                       int width, int height, float* __restrict__ out) {
+    __shared__ BodySurvivor s_body[256];
+    __shared__ int s_count[4];
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int i0 = blockIdx.x * 16, j0 = blockIdx.y * 16;
+    const int i = i0 + (w & 1) * 8 + (l & 7), j = j0 + (w >> 1) * 8 + (l >> 3);
+    const Vec3 d = pixel_direction(cam, (float)i, (float)j);
+    const float ox = cam.c[0], oy = cam.c[1], oz = cam.c[2], t0 = cam.c[12], t1 = cam.c[13];
+    const BodyMeet bm = primary_body(cam, box, bodies, stride, count, cull, i0, j0, d, s_body, s_count);
     if (i >= width || j >= height) return;  // behind the last barrier
     const size_t k = (size_t)j * width + i;
 
     const RayMeet m = ray_march_until<true>(v, tile, iterations, steps, refine, bounds, ox, oy, oz, d.x, d.y, d.z, t0, t1,
-                                            best_b >= 0 ? best_te : __builtin_nanf(""));
-    const bool body = best_b >= 0 && (m.status == OCEAN_RAY_BODY || m.status == OCEAN_RAY_MISS ||
-                                      (m.status == OCEAN_RAY_HIT && best_te < m.t));
-    if (!body) {
+                                            bm.b >= 0 ? bm.te : __builtin_nanf(""));
+    if (body_in_front(bm, m))
+        body_pixel<MODE, SKY>(mt, paint, sk, bm, k, out);
+    else
         water_pixel<MODE, SKY>(v, tile, iterations, mt, ox, oy, oz, d.x, d.y, d.z, m, k, out, sk, sun_size);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Camera views in which the water sees the bodies (ocean_camera_scene*).  include/ocean/ocean.h has the definition:
+// ocean_camera_bodies' image, and at a water pixel the three places where the fragment stage of Water.shader reads
+// scene geometry: the body behind the surface, fogged by its distance behind it; the shadow ray from the point met
+// towards the sun; the mirror ray.  Again the definition tries every body for every ray, and the kernel gets the same
+// bits from fewer tests.
+//
+// Order.  The primary body loop and the stopped march are k_camera_bodies'.  Then the pixel's fixed point and sample,
+// which the mirror ray needs for n.  Body, MISS and SUBMERGED pixels are stored there, and their lanes, like those
+// outside the image, stay alive to every barrier behind.  Then the second cull, the secondary rays, the shading.
+//
+// The second cull.  The secondary rays do not start at the eye, so the cone does not serve.  They start at the q of
+// the workgroup's water pixels: the workgroup reduces the bounding box of those q (a butterfly per wave, then LDS
+// across the four waves; a tile without a water pixel skips the stage uniformly), and with pc the box's centre, pr
+// half its diagonal and rl the longest secondary ray, a body with |ctr - pc| > rad + pr + rl is further than rad from
+// every point of every secondary ray of the tile.  ctr, rad and the unit-quaternion rule are those of the cull above.
+// In exact arithmetic a ray's points are q + s r, s in [0, reach], so rl = reach max(|L|, |rd|); |rd|^2 = |V|^2 +
+// 4 ndv^2 (|n|^2 - 1) is within 2^-20 of 1 for the fp32 unit vectors n and V, and rl = reach max(|L|, 1) (1 + 2^-10)
+// covers both.  In fp32, with u = 2^-24 and every length at most S = |ctr - pc|_1 + |bc|_1 + hd + pr + rl:
+//   - the slab test reports `met` only for a ray that passes within 64 u S of the exact box, and only for a part of
+//     it within 8 u S of [0, reach] (the derivation above, with w = q - c, |w| <= |ctr - pc| + pr + |bc| (1 + 2^-7));
+//   - the box is reduced from the very q the rays start at (fminf and fmaxf are exact); pc carries one rounding, and
+//     the half extents are formed from the rounded pc as fmaxf(hi - pc, pc - lo), so that [pc - e, pc + e] holds the
+//     box to one rounding of e; pr carries four more: 6 u S;
+//   - ctr - pc is (c - pc) + r: 2 u S and rot's 16 u |bc|; its length 3 u S; the right side's sums 4 u S, rl's
+//     products 3 u S.
+// Together less than 110 u S; the margin is the 2^-16 S = 256 u S of the cull above.  Every compare is written so
+// that a NaN makes a survivor.  The survivors' records carry c where the primary ones carry ob: a lane forms ob
+// from its own q (the statements of ocean.h: w = q - c, ob = rot(-u, qw, w)), once for both rays.
+//
+// Registers and LDS: 73 VGPRs in LINKS mode and 95 in the two colour modes, no scratch; 16 KiB of survivors, 16 B of
+// counts and 96 B of boxes.  At 95 VGPRs five waves per SIMD are resident, five workgroups per CU, and their 81 KiB
+// of LDS fit the CU's 160 KiB: as for k_camera_bodies, the registers bound the occupancy, not the LDS.
+template <int MODE, bool SKY>
+__global__ __launch_bounds__(256) void k_camera_scene(DevView v, int tile, int iterations, int steps, int refine,
+                                                      const float* __restrict__ bounds, CameraRays cam, CameraMaterial mt,
+                                                      LutView sk, float sun_size, BodyBox box, BodyPaint paint,
+                                                      SceneOptics op, const float* __restrict__ bodies, int stride,
+                                                      int count, int cull, int width, int height,
+                                                      float* __restrict__ out) {
+    __shared__ BodySurvivor s_body[256];
+    __shared__ int s_count[4];
+    __shared__ float s_box[4][6];
+    constexpr bool kLinks = MODE == OCEAN_CAMERA_LINKS;
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int i0 = blockIdx.x * 16, j0 = blockIdx.y * 16;
+    const int i = i0 + (w & 1) * 8 + (l & 7), j = j0 + (w >> 1) * 8 + (l >> 3);
+    const Vec3 d = pixel_direction(cam, (float)i, (float)j);
+    const float ox = cam.c[0], oy = cam.c[1], oz = cam.c[2], t0 = cam.c[12], t1 = cam.c[13];
+    const BodyMeet b1 = primary_body(cam, box, bodies, stride, count, cull, i0, j0, d, s_body, s_count);
+    const bool inside = i < width && j < height;
+    const size_t k = (size_t)j * width + i;  // used by the lanes inside only
+
+    // the water on the ray, and every pixel that is not a water HIT pixel
+    bool water = false;
+    float tstar = 0.0f;
+    if (inside) {
+        const RayMeet m = ray_march_until<true>(v, tile, iterations, steps, refine, bounds, ox, oy, oz, d.x, d.y, d.z, t0,
+                                                t1, b1.b >= 0 ? b1.te : __builtin_nanf(""));
+        const bool body = body_in_front(b1, m);
+        water = !body && m.status == OCEAN_RAY_HIT;
+        tstar = m.t;
+        if (kLinks) {
+            if (!water)
+                reinterpret_cast<float4*>(out)[k] = make_float4(1.0f, body ? (float)b1.b : -1.0f, -1.0f,
+                                                                (float)(body ? OCEAN_RAY_BODY : m.status));
+        } else if (body) {
+            body_pixel<OCEAN_CAMERA_COLOR, SKY>(mt, paint, sk, b1, k, out);
+        } else if (!water) {
+            water_pixel<OCEAN_CAMERA_COLOR, SKY>(v, tile, iterations, mt, ox, oy, oz, d.x, d.y, d.z, m, k, out, sk, sun_size);
+        }
+    }
+
+    // the point met, its normal, wave height and foam: the statements of water_pixel's colour mode
+    float qx = 0.0f, qy = 0.0f, qz = 0.0f, nx = 0.0f, ny = 1.0f, nz = 0.0f, eta = 0.0f, foam = 0.0f;
+    Vec3 rd = {0.0f, 1.0f, 0.0f};
+    if (water) {
+        qx = ox + tstar * d.x, qy = oy + tstar * d.y, qz = oz + tstar * d.z;
+        const float2 p = surface_fixed_point(v, tile, qx, qz, iterations);
+        const WorldSample s = sample_cascades(v, tile, p.x, p.y, tstar * mt.m[7]);
+        const float4 n = normal_from_deriv(s.deriv.x, s.deriv.y, s.deriv.z, s.deriv.w);  // (0, 1, 0) without DERIV
+        nx = n.x, ny = n.y, nz = n.z, eta = s.disp.y, foam = s.turb;
+        const float vx = -d.x, vy = -d.y, vz = -d.z;
+        const float ndv = dot3(nx, ny, nz, vx, vy, vz);
+        rd.x = (2.0f * ndv) * nx - vx, rd.y = (2.0f * ndv) * ny - vy, rd.z = (2.0f * ndv) * nz - vz;
+    }
+
+    // the secondary rays: the shadow ray any-hit, the mirror ray nearest-hit
+    const float reach = op.o[5];
+    const Vec3 L = {mt.m[20], mt.m[21], mt.m[22]};
+    const bool sun_up = L.y > 0.0f;
+    bool shadowed = false;
+    BodyMeet b2 = no_body();
+    if (count > 0) {
+        // the box of the workgroup's q: lanes that are no water pixel contribute nothing
+        const float inf = __builtin_inff();
+        float bb[6] = {water ? qx : inf, water ? qy : inf, water ? qz : inf, water ? qx : -inf, water ? qy : -inf,
+                       water ? qz : -inf};
+        for (int step = 1; step < 64; step <<= 1)
+            for (int c = 0; c < 3; ++c) {
+                bb[c] = fminf(bb[c], __shfl_xor(bb[c], step));
+                bb[3 + c] = fmaxf(bb[3 + c], __shfl_xor(bb[3 + c], step));
+            }
+        if (l == 0)
+            for (int c = 0; c < 6; ++c) s_box[w][c] = bb[c];
+        __syncthreads();
+        for (int c = 0; c < 3; ++c) {
+            bb[c] = fminf(fminf(s_box[0][c], s_box[1][c]), fminf(s_box[2][c], s_box[3][c]));
+            bb[3 + c] = fmaxf(fmaxf(s_box[0][3 + c], s_box[1][3 + c]), fmaxf(s_box[2][3 + c], s_box[3][3 + c]));
+        }
+        if (bb[0] <= bb[3]) {  // uniform: some lane is a water pixel
+            const float pcx = 0.5f * (bb[0] + bb[3]), pcy = 0.5f * (bb[1] + bb[4]), pcz = 0.5f * (bb[2] + bb[5]);
+            const float ex = fmaxf(bb[3] - pcx, pcx - bb[0]), ey = fmaxf(bb[4] - pcy, pcy - bb[1]);
+            const float ez = fmaxf(bb[5] - pcz, pcz - bb[2]);
+            const float pr = sqrtf((ex * ex + ey * ey) + ez * ez);
+            const float rl = (reach * fmaxf(sqrtf((L.x * L.x + L.y * L.y) + L.z * L.z), 1.0f)) * (1.0f + 0x1p-10f);
+            for (int base = 0; base < count; base += 256) {
+                const int b = base + (int)threadIdx.x;
+                bool keep = false;
+                BodySurvivor sv = {};
+                if (b < count) {
+                    Vec3 c;
+                    sv = body_record(bodies, stride, b, box, c);
+                    sv.obx = c.x, sv.oby = c.y, sv.obz = c.z;  // c in ob's place: ob depends on the lane's q
+                    keep = true;
+                    if (cull != 0) {
+                        const BodySphere sp = body_sphere(sv);
+                        const float vx = (c.x - pcx) + sp.r.x, vy = (c.y - pcy) + sp.r.y, vz = (c.z - pcz) + sp.r.z;
+                        const float S = ((((fabsf(vx) + fabsf(vy)) + fabsf(vz)) + sp.size) + pr) + rl;
+                        const float dist = sqrtf((vx * vx + vy * vy) + vz * vz);
+                        const bool off = dist > ((sp.rad + pr) + rl) + kCullMargin * S;
+                        keep = !(off && sp.unit);
+                    }
+                }
+                const int total = compact_survivors(keep, sv, s_body, s_count, w, l);
+                if (water)
+                    for (int s = 0; s < total; ++s) {
+                        const BodySurvivor& q = s_body[s];  // one address for the wave: a broadcast
+                        const Vec3 ob = rotate(-q.ux, -q.uy, -q.uz, q.qw, qx - q.obx, qy - q.oby, qz - q.obz);
+                        if (sun_up && !shadowed) shadowed = meet_box(q, ob.x, ob.y, ob.z, L, 0.0f, reach).met;
+                        keep_nearer(q, meet_box(q, ob.x, ob.y, ob.z, rd, 0.0f, reach), rd, 0.0f, b2);
+                    }
+            }
+        }
+    }
+    if (!water) return;  // behind the last barrier
+
+    if (kLinks) {
+        reinterpret_cast<float4*>(out)[k] =
+            make_float4(shadowed ? 0.0f : 1.0f, (float)b1.b, (float)b2.b, (float)OCEAN_RAY_HIT);
         return;
     }
-    if (MODE == OCEAN_CAMERA_RANGE) {
-        out[k] = best_te;
-    } else if (MODE == OCEAN_CAMERA_HITS) {
-        float4* o = reinterpret_cast<float4*>(out) + 2 * k;
-        o[0] = make_float4(best_te, 0.0f, 0.0f, (float)OCEAN_RAY_BODY);
-        o[1] = make_float4(nwx, nwy, nwz, (float)best_b);
-    } else {
-        float amb[3];
-        if (SKY) {
-            const float3 e = sky_lut(sk, nwx, nwy, nwz);
-            amb[0] = e.x, amb[1] = e.y, amb[2] = e.z;
-        } else {
-            for (int c = 0; c < 3; ++c) amb[c] = sky(mt.m[26 + c], mt.m[29 + c], nwy);
-        }
-        const float lit = fmaxf(dot3(nwx, nwy, nwz, mt.m[20], mt.m[21], mt.m[22]), 0.0f);
-        float rgb[3];
-        for (int c = 0; c < 3; ++c) rgb[c] = paint.p[c] * (paint.p[3] * amb[c] + mt.m[23 + c] * lit);
-        reinterpret_cast<float4*>(out)[k] = make_float4(rgb[0], rgb[1], rgb[2], (float)OCEAN_RAY_BODY);
+    SceneTerms sc = {};
+    sc.through = b1.b >= 0, sc.mirrored = b2.b >= 0, sc.shadowed = shadowed;
+    if (sc.through) {
+        sc.fog = exp2f(-(op.o[4] * (b1.te - tstar)));
+        paint_colour<SKY>(mt, paint, sk, b1.nw, sc.seen);
     }
+    if (sc.mirrored) paint_colour<SKY>(mt, paint, sk, b2.nw, sc.mirror);
+    sc.sh[0] = op.o[0], sc.sh[1] = op.o[1], sc.sh[2] = op.o[2], sc.si = op.o[3];
+    const float3 c = shade_hit<SKY, true>(mt, d.x, d.y, d.z, nx, ny, nz, eta, foam, v.deriv != nullptr, sk, sc);
+    reinterpret_cast<float4*>(out)[k] = make_float4(c.x, c.y, c.z, (float)OCEAN_RAY_HIT);
 }
 
 // The launch grid of camera_pixel's two mappings: 16 x 16 pixel tiles, or 256 consecutive pixels per workgroup.
@@ -467,6 +737,24 @@ hipError_t launch_camera_bodies(const DevView& v, int tile, int mode, int iterat
         constexpr int M = decltype(m)::value;
         launch(k_camera_bodies<M & ~OCEAN_CAMERA_SKY_LUT, M == kSky>, camera_groups(width, height, true), dim3(256), 0, s, v,
                tile, iterations, steps, refine, bounds, cam, mt, sky, sun_size, box, paint, bodies, stride, count,
+               cull ? 1 : 0, width, height, out);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+hipError_t launch_camera_scene(const DevView& v, int tile, int mode, int iterations, int steps, int refine,
+                               const float* bounds, const CameraRays& cam, const CameraMaterial& mt, const LutView& sky,
+                               float sun_size, const BodyBox& box, const BodyPaint& paint, const SceneOptics& optics,
+                               const float* bodies, int stride, int count, bool cull, int width, int height, float* out,
+                               hipStream_t s) {
+    if (width < 1 || height < 1 || (size_t)width * height > (size_t)OCEAN_CAMERA_MAX_PIXELS) return hipErrorInvalidValue;
+    if (stride < 10 || count < 0 || (count > 0 && !bodies)) return hipErrorInvalidValue;
+    constexpr int kSky = OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT;
+    if (mode == kSky && (!sky.texels || sky.w < 2 || sky.h < 2)) return hipErrorInvalidValue;
+    const bool known = with_constant<OCEAN_CAMERA_COLOR, kSky, OCEAN_CAMERA_LINKS>(mode, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        launch(k_camera_scene<M & ~OCEAN_CAMERA_SKY_LUT, M == kSky>, camera_groups(width, height, true), dim3(256), 0, s, v,
+               tile, iterations, steps, refine, bounds, cam, mt, sky, sun_size, box, paint, optics, bodies, stride, count,
                cull ? 1 : 0, width, height, out);
     });
     return known ? hipGetLastError() : hipErrorInvalidValue;

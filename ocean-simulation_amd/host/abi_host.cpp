@@ -4,7 +4,7 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|camera_bodies|sky|step|spray]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|camera_bodies|camera_scene|sky|step|spray]
 //
 // With step the host plays F frames on a velocity context and, behind each, advances a fleet of six boxes of 4 x 3
 // probes by 4 substeps of 1/240 s through one WaterBody::StepBodies in its async form (surface mode, 4 steps,
@@ -20,6 +20,11 @@
 // camera and five boxes in its view, records 16 floats apart: one in the air, three afloat, one sunk; it writes camera.bin,
 // box.bin (float32 [6]), bodies.bin (float32 [5][16]) and body_hits.bin (float32 [37][45][8]); the summary line carries
 // the number of pixels of each status; tests/test_gpu_camera_bodies_host.py checks them.
+// With camera_scene it runs F steps, then two WaterBody::CameraScene calls for the same camera and boxes as camera_bodies
+// (records 16 floats apart) under the camera mode's material, in OCEAN_CAMERA_LINKS and in OCEAN_CAMERA_COLOR mode; it
+// writes camera.bin, material.bin, box.bin, paint.bin (float32 [4]), optics.bin (float32 [6]), bodies.bin, scene_links.bin
+// and scene_color.bin (float32 [37][45][4] each); the summary line carries the number of water pixels that are shadowed,
+// that show a body through the water and that reflect one; tests/test_gpu_camera_scene_host.py checks them.
 // With sky it does the same behind the atmosphere: WaterBody::Atmosphere at the sizes 12 x 20, 3 x 5 and 20 x 12, one
 // SkyUpdate, and the camera in OCEAN_CAMERA_COLOR | OCEAN_CAMERA_SKY_LUT mode under the light colour SkyUpdate returned;
 // it writes transmittance.bin, multiscatter.bin, skyview.bin (float32 [h][w][4] each), sun.bin (float32 [3]),
@@ -80,14 +85,14 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|camera_bodies|sky|step|spray]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|camera_bodies|camera_scene|sky|step|spray]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
     if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity" &&
         mode != "rays" && mode != "dynamics" && mode != "whitecaps" && mode != "camera" && mode != "camera_bodies" &&
-        mode != "sky" && mode != "step" && mode != "spray") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps, camera, camera_bodies, sky, step or spray\n");
+        mode != "camera_scene" && mode != "sky" && mode != "step" && mode != "spray") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps, camera, camera_bodies, camera_scene, sky, step or spray\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -309,6 +314,54 @@ int main(int argc, char** argv) {
             std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"width\": %d, \"height\": %d, \"miss\": %d, "
                         "\"hit\": %d, \"submerged\": %d, \"body\": %d}\n", F, n, (int)wb.cascades.size(), width, height,
                         status[0], status[1], status[2], status[3]);
+            wb.OnDisable();
+            return 0;
+        }
+        if (mode == "camera_scene") {
+            const int width = 45, height = 37, stride = 16;
+            const std::vector<float> camera = {3.0f, 30.0f, -4.0f, -0.45f, 0.21f, 0.85f, 0.02f, 0.0f, 0.01f,
+                                               0.0f,  -0.02f, 0.0f,  0.0f,   600.0f};
+            // the camera mode's material, but for a lower sun from the left: (-0.6, 0.35, 0.72) normalised
+            const std::vector<float> material = {0.02f,  0.1f,  0.16f,  0.0203731f, 2.2308f, 4.72995f, 0.3f, 0.004f,
+                                                 0.25f,  0.25f, 1.0f,   1.0f,       0.0f,    0.3f,     0.25f, 0.25f,
+                                                 1.0f,   1.0f,  1.0f,   0.5f,       -0.599730f, 0.349843f, 0.719676f, 1.0f,
+                                                 0.96f,  0.9f,  0.75f,  0.82f,      0.9f,    0.2f,     0.4f,  0.8f};
+            const std::vector<float> box = {-0.5f, -0.25f, -0.5f, 0.5f, 0.75f, 0.5f};
+            const std::vector<float> paint = {0.85f, 0.35f, 0.15f, 0.6f};
+            // shadow colour and intensity, water fog density, reach of the secondary rays
+            const std::vector<float> optics = {0.02f, 0.03f, 0.08f, 0.6f, 0.05f, 200.0f};
+            const std::vector<float> bodies = {
+                2.0f,   16.0f, 95.0f,  0.0f,  0.0f,  0.0f,  1.0f,  8.0f,  6.0f,  8.0f,  9.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f,
+                -25.0f, 0.5f,  160.0f, 0.0f,  0.6f,  0.0f,  0.8f,  30.0f, 12.0f, 14.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f,
+                30.0f,  1.0f,  210.0f, 0.28f, 0.0f,  0.0f,  0.96f, 25.0f, 20.0f, 25.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f,
+                -5.0f,  -1.0f, 300.0f, 0.5f,  0.5f,  0.5f,  0.5f,  40.0f, 40.0f, 20.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f, 9.0f,
+                10.0f,  -30.0f, 120.0f, 0.0f, 0.0f,  0.0f,  1.0f,  30.0f, 10.0f, 30.0f};
+            wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
+            wb.Awake();
+            for (int f = 0; f < F; ++f) wb.Update((float)f / 60.0f);
+            const std::vector<float> links = wb.CameraScene(camera, width, height, box, {}, optics, bodies, stride,
+                                                            OCEAN_CAMERA_LINKS, material, 2, 32, 6);
+            const std::vector<float> color = wb.CameraScene(camera, width, height, box, paint, optics, bodies, stride,
+                                                            OCEAN_CAMERA_COLOR, material, 2, 32, 6);
+            write_bin(out + "/camera.bin", camera.data(), camera.size());
+            write_bin(out + "/material.bin", material.data(), material.size());
+            write_bin(out + "/box.bin", box.data(), box.size());
+            write_bin(out + "/paint.bin", paint.data(), paint.size());
+            write_bin(out + "/optics.bin", optics.data(), optics.size());
+            write_bin(out + "/bodies.bin", bodies.data(), bodies.size());
+            write_bin(out + "/scene_links.bin", links.data(), links.size());
+            write_bin(out + "/scene_color.bin", color.data(), color.size());
+            int shadowed = 0, through = 0, mirrored = 0, water = 0;
+            for (int k = 0; k < width * height; ++k) {
+                if ((int)links[4 * k + 3] != OCEAN_RAY_HIT) continue;
+                ++water;
+                shadowed += links[4 * k] == 0.0f;
+                through += links[4 * k + 1] >= 0.0f;
+                mirrored += links[4 * k + 2] >= 0.0f;
+            }
+            std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"width\": %d, \"height\": %d, \"water\": %d, "
+                        "\"shadowed\": %d, \"through\": %d, \"mirrored\": %d}\n", F, n, (int)wb.cascades.size(), width,
+                        height, water, shadowed, through, mirrored);
             wb.OnDisable();
             return 0;
         }

@@ -330,6 +330,31 @@ public:
         return out;
     }
 
+    // CameraBodies with the water seeing the bodies (ocean.h ocean_camera_scene): their shadows on it, their reflections
+    // in it and their submerged parts through it.  `optics` = 6 floats (shadow colour r, g, b, shadow intensity, water
+    // fog density, reach of the secondary rays in metres); mode OCEAN_CAMERA_COLOR, OCEAN_CAMERA_COLOR |
+    // OCEAN_CAMERA_SKY_LUT or OCEAN_CAMERA_LINKS (per pixel: lit or not, the body seen through the water, the body
+    // reflected, the status), 4 floats per pixel in each; the material is required, the paint in the colour modes.
+    std::vector<float> CameraScene(const std::vector<float>& camera, int width, int height, const std::vector<float>& box,
+                                   const std::vector<float>& paint, const std::vector<float>& optics,
+                                   const std::vector<float>& bodies, int stride, int mode, const std::vector<float>& material,
+                                   int iterations = 4, int steps = 64, int refine = 8) const {
+        if (camera.size() != OCEAN_CAMERA_FLOATS || material.size() != OCEAN_CAMERA_MATERIAL_FLOATS)
+            throw std::runtime_error("CameraScene: camera is 14 floats, material 32");
+        if (box.size() != 6 || (!paint.empty() && paint.size() != OCEAN_BODY_PAINT_FLOATS) ||
+            optics.size() != OCEAN_SCENE_OPTICS_FLOATS || stride < 10)
+            throw std::runtime_error("CameraScene: box is 6 floats, paint 4 or none, optics 6, stride at least 10");
+        const bool valid = width >= 1 && height >= 1 && (long long)width * height <= OCEAN_CAMERA_MAX_PIXELS;
+        std::vector<float> out(valid ? (size_t)width * height * 4 : 0);
+        const int count = bodies.empty() ? 0 : (int)((bodies.size() + (size_t)stride - 10) / (size_t)stride);
+        check(ocean_camera_scene(ctx_, 0, mode, iterations, steps, refine, camera.data(), material.data(), width, height,
+                                 box.data(), paint.empty() ? nullptr : paint.data(), optics.data(),
+                                 bodies.empty() ? nullptr : bodies.data(), stride, count, out.data(),
+                                 out.size() * sizeof(float)),
+              "ocean_camera_scene");
+        return out;
+    }
+
     // The atmosphere of AtmosphereController.cs (ocean.h "The atmosphere"): its Awake, the transmittance and the
     // multiscatter table from the 32 floats of `params` (ocean.h names them; DefaultAtmosphere() has the reference's),
     // at the reference's sizes when `dims` is empty, else (Tw, Th, Mw, Mh, Sw, Sh).  Needs no spectrum.

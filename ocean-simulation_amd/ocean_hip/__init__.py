@@ -78,6 +78,7 @@ EXPORTED_SYMBOLS = (
     "ocean_atmosphere", "ocean_sky_update", "ocean_atmosphere_read", "ocean_atmosphere_lut", "ocean_sun_color",
     "ocean_spray_step", "ocean_spray_step_device", "ocean_spray_step_async",
     "ocean_camera_bodies", "ocean_camera_bodies_device", "ocean_camera_bodies_async",
+    "ocean_camera_scene", "ocean_camera_scene_device", "ocean_camera_scene_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -127,6 +128,10 @@ SPRAY_MAX_SUBSTEPS = 64
 RAY_BODY = 3
 BODY_PAINT_FLOATS = 4
 BODY_STRIDE_MIN, BODY_STRIDE_MAX = 10, 64
+# ocean_camera_scene*: its own mode (the record of every pixel's shadow, through-water and reflection links) and the
+# size of its optics array (ocean.h)
+CAMERA_LINKS = 3
+SCENE_OPTICS_FLOATS = 6
 
 
 class OceanError(RuntimeError):
@@ -238,6 +243,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_camera_bodies": ([P, i, i, i, i, i, P, P, i, i, P, P, P, i, i, P, sz], i),
         "ocean_camera_bodies_device": ([P, i, i, i, i, i, P, P, i, i, P, P, P, i, i, P, sz], i),
         "ocean_camera_bodies_async": ([P, i, i, i, i, i, P, P, i, i, P, P, P, i, i, P, sz, ctypes.POINTER(P)], i),
+        "ocean_camera_scene": ([P, i, i, i, i, i, P, P, i, i, P, P, P, P, i, i, P, sz], i),
+        "ocean_camera_scene_device": ([P, i, i, i, i, i, P, P, i, i, P, P, P, P, i, i, P, sz], i),
+        "ocean_camera_scene_async": ([P, i, i, i, i, i, P, P, i, i, P, P, P, P, i, i, P, sz, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -316,6 +324,14 @@ def atmosphere_params(planet_radius: float = 6360000.0, atmosphere_radius: float
     p[9:12], p[12:15], p[15], p[16] = mie_scattering, mie_absorption, mie_scale_height, g
     p[17:20], p[20:23], p[23:26], p[26] = ozone_scattering, ozone_absorption, ground_albedo, sun_size
     return p.astype(np.float32)
+
+
+def optics(shadow_color=(0.0, 0.0, 0.0), shadow_intensity: float = 0.5, fog_density: float = 0.2,
+           reach: float = 100.0) -> np.ndarray:
+    """The float32[6] `optics` of ocean_camera_scene (ocean.h) = (SH.r, SH.g, SH.b, SI, WF, reach): Water.shader's
+    _ShadowsColor, _ShadowsIntensity and _WaterFogDensity, and the length in metres that the shadow ray and the mirror
+    ray search for a body.  Rounded once."""
+    return np.array([*shadow_color, shadow_intensity, fog_density, reach], np.float32)
 
 
 def step_params(h: float, g: float = 9.81, buoyancy: Optional[float] = None, drag: float = 0.0, drag_torque: float = 0.0,
@@ -710,6 +726,64 @@ class OceanContext:
                                                    bx.ctypes.data, pt.ctypes.data if pt is not None else None,
                                                    ctypes.c_void_p(bodies_ptr) if bodies_ptr else None, stride, count,
                                                    ctypes.c_void_p(out_ptr), nbytes), "ocean_camera_bodies_device")
+
+    @staticmethod
+    def _scene_args(camera, material, optics, width, height):
+        """(camera, material, optics float32[6], result shape, bytes): 16 B per pixel in every mode of the scene."""
+        cam, mat, shape, nbytes = OceanContext._camera_args(camera, material, CAMERA_COLOR, width, height)
+        op = np.ascontiguousarray(optics, np.float32).reshape(-1)
+        if op.shape[0] != SCENE_OPTICS_FLOATS:
+            raise ValueError(f"optics must be float32[{SCENE_OPTICS_FLOATS}] (optics()), got {op.shape}")
+        return cam, mat, op, shape, nbytes
+
+    def camera_scene(self, camera, width: int, height: int, bodies, box=(-0.5, -0.5, -0.5, 0.5, 0.5, 0.5),
+                     paint=(0.8, 0.8, 0.8, 1.0), optics=(0.0, 0.0, 0.0, 0.5, 0.2, 100.0), mode: int = CAMERA_COLOR,
+                     material=None, tile: int = 0, iterations: int = 4, steps: int = 64, refine: int = 8) -> np.ndarray:
+        """camera_bodies() with the water seeing the bodies (ocean.h ocean_camera_scene), blocking: at a water pixel
+        the body behind the surface shows through, fogged by its distance behind it; a body between the point met and
+        the sun shadows it; a body on the mirror ray is reflected instead of the sky.  optics: optics().  mode:
+        CAMERA_COLOR, CAMERA_COLOR | CAMERA_SKY_LUT, or CAMERA_LINKS: float32[height][width][4] = (sf, the body seen
+        through the water or -1, the body reflected or -1, status), a body pixel (1, its body, -1, RAY_BODY).  The
+        material is required in every mode, the paint in the colour modes."""
+        cam, mat, op, shape, nbytes = self._scene_args(camera, material, optics, width, height)
+        bx, pt, rec, stride, count = self._body_view_args(box, paint, bodies)
+        out = np.empty(shape, np.float32)
+        _check(self.lib.ocean_camera_scene(self._h, tile, mode, iterations, steps, refine, cam.ctypes.data,
+                                           mat.ctypes.data if mat is not None else None, width, height, bx.ctypes.data,
+                                           pt.ctypes.data if pt is not None else None, op.ctypes.data,
+                                           rec.ctypes.data if rec is not None else None, stride, count,
+                                           out.ctypes.data, nbytes), "ocean_camera_scene")
+        return out
+
+    def camera_scene_async(self, camera, width: int, height: int, bodies, box=(-0.5, -0.5, -0.5, 0.5, 0.5, 0.5),
+                           paint=(0.8, 0.8, 0.8, 1.0), optics=(0.0, 0.0, 0.0, 0.5, 0.2, 100.0), mode: int = CAMERA_COLOR,
+                           material=None, tile: int = 0, iterations: int = 4, steps: int = 64, refine: int = 8,
+                           buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_camera_scene_async), as camera_bodies_async: `bodies` is consumed by the call."""
+        cam, mat, op, shape, nbytes = self._scene_args(camera, material, optics, width, height)
+        bx, pt, rec, stride, count = self._body_view_args(box, paint, bodies)
+        return Readback(self, shape, nbytes, "ocean_camera_scene_async",
+                        lambda dst, req: self.lib.ocean_camera_scene_async(
+                            self._h, tile, mode, iterations, steps, refine, cam.ctypes.data,
+                            mat.ctypes.data if mat is not None else None, width, height, bx.ctypes.data,
+                            pt.ctypes.data if pt is not None else None, op.ctypes.data,
+                            rec.ctypes.data if rec is not None else None, stride, count, dst, nbytes, req), buf)
+
+    def camera_scene_device(self, out_ptr: int, camera, width: int, height: int, bodies_ptr: int, count: int,
+                            stride: int = 32, box=(-0.5, -0.5, -0.5, 0.5, 0.5, 0.5), paint=(0.8, 0.8, 0.8, 1.0),
+                            optics=(0.0, 0.0, 0.0, 0.5, 0.2, 100.0), mode: int = CAMERA_COLOR, material=None,
+                            tile: int = 0, iterations: int = 4, steps: int = 64, refine: int = 8) -> None:
+        """The device-pointer form (ocean_camera_scene_device), as camera_bodies_device: `bodies_ptr` holds `count`
+        records `stride` floats apart on this context's device (32: where body_step_device left them), `out_ptr` is
+        16-B aligned; async on the context's stream.  camera, material, box, paint and optics are host arrays."""
+        cam, mat, op, _, nbytes = self._scene_args(camera, material, optics, width, height)
+        bx, pt, _, _, _ = self._body_view_args(box, paint, None)
+        _check(self.lib.ocean_camera_scene_device(self._h, tile, mode, iterations, steps, refine, cam.ctypes.data,
+                                                  mat.ctypes.data if mat is not None else None, width, height,
+                                                  bx.ctypes.data, pt.ctypes.data if pt is not None else None,
+                                                  op.ctypes.data, ctypes.c_void_p(bodies_ptr) if bodies_ptr else None,
+                                                  stride, count, ctypes.c_void_p(out_ptr), nbytes),
+               "ocean_camera_scene_device")
 
     @staticmethod
     def grid_points(x0: float, z0: float, dx: float, dz: float, nx: int, ny: int) -> np.ndarray:
@@ -1559,6 +1633,18 @@ class WaterBody:
             material = _material()
         cam = look_at_camera(eye, target, up, fov_y, width, height, 0.0, max_distance)
         return self.ctx.camera_bodies(cam, width, height, bodies, box, paint, mode, material, tile, iterations, steps, refine)
+
+    def camera_scene(self, eye, target, width: int, height: int, bodies, box=(-0.5, -0.5, -0.5, 0.5, 0.5, 0.5),
+                     paint=(0.8, 0.8, 0.8, 1.0), optics=(0.0, 0.0, 0.0, 0.5, 0.2, 100.0), fov_y: float = 1.0,
+                     max_distance: float = 2000.0, mode: int = CAMERA_COLOR, material=None, up=(0.0, 1.0, 0.0),
+                     iterations: int = 4, steps: int = 64, refine: int = 8, tile: int = 0) -> np.ndarray:
+        """camera_bodies() with the hulls' shadows on the water, their reflections in it and their submerged parts
+        through it (OceanContext.camera_scene over look_at_camera)."""
+        if material is None:
+            material = _material()
+        cam = look_at_camera(eye, target, up, fov_y, width, height, 0.0, max_distance)
+        return self.ctx.camera_scene(cam, width, height, bodies, box, paint, optics, mode, material, tile, iterations,
+                                     steps, refine)
 
     def Whitecaps(self, threshold: float, x0: float, z0: float, dx: float, dz: float, nx: int, ny: int,
                   capacity: int = 4096, lod: float = 0.0, tile: int = 0):
