@@ -89,7 +89,10 @@ extern "C" {
  *      Added later within version 4 in the same way: OCEAN_RAY_BODY, OCEAN_BODY_PAINT_FLOATS, ocean_camera_bodies,
  *      ocean_camera_bodies_device, ocean_camera_bodies_async.
  *      Added later within version 4 in the same way: OCEAN_CAMERA_LINKS, OCEAN_SCENE_OPTICS_FLOATS, ocean_camera_scene,
- *      ocean_camera_scene_device, ocean_camera_scene_async. */
+ *      ocean_camera_scene_device, ocean_camera_scene_async.
+ *      Added later within version 4 in the same way: OCEAN_HULL_MAX_VERTICES, OCEAN_HULL_MAX_TRIANGLES,
+ *      OCEAN_HULL_RECORD_FLOATS, ocean_body_hydrostatics, ocean_body_hydrostatics_device,
+ *      ocean_body_hydrostatics_async. */
 #define OCEAN_ABI_VERSION 4
 
 /* status codes */
@@ -987,6 +990,99 @@ int ocean_body_step_device(ocean_ctx *ctx, int tile, int mode, int iterations, i
 int ocean_body_step_async(ocean_ctx *ctx, int tile, int mode, int iterations, int law, int substeps, const float *step,
                           const float *hull, int probes, const float *props, const float *state, int count, float *out,
                           ocean_readback **req);
+
+/* Mesh hulls: the hydrostatic pressure integrated over the wetted part of a triangle mesh, for M rigid bodies that
+ * share the mesh, reduced on the device to 64 B per body whatever the mesh's size.  A probe of ocean_body_buoyancy is a
+ * vertical column: it has no side, so it cannot place the waterline on a sloped plate; its horizontal force is zero, so
+ * a hull never feels the slope of the wave it sits on (the Froude-Krylov surge and sway); it has neither wetted nor
+ * waterplane area; and its accuracy is that of the host's voxelisation.  Here the water is sampled over the mesh's
+ * vertices, every triangle is clipped at the waterline and the pressure, taken as linear over a clipped piece, is
+ * integrated exactly.  With the entries above a host would query M x V points, read M x V x 32 B back and clip itself.
+ *
+ *   vertices:  vertex i is float[3] = (rx, ry, rz) in the body frame.  V = nverts in [1, OCEAN_HULL_MAX_VERTICES].
+ *   triangles: triangle k is int[3] = (i0, i1, i2), indices into `vertices`, counter-clockwise seen from outside (the
+ *              normal (P1 - P0) x (P2 - P0) points out of the hull).  T = ntris in [1, OCEAN_HULL_MAX_TRIANGLES].
+ *              Declared `const void *` so that every binding marshals it as a plain address; it is an int array.
+ *   bodies:    float[M][10], exactly as ocean_body_buoyancy takes it.
+ *   out:       record b is float[OCEAN_HULL_RECORD_FLOATS] = float[16].
+ * The surface lookup is always OCEAN_QUERY_SURFACE with K = `iterations` in [0, 16]; there is no mode argument, because
+ * a texel pick has no waterline.
+ *
+ * All arithmetic is fp32, each line one rounding per operation in the order written (no fused multiply-add); sqrtf and /
+ * are correctly rounded.  (a x b) = (a.y * b.z - a.z * b.y,  a.z * b.x - a.x * b.z,  a.x * b.y - a.y * b.x), and a
+ * vector line is meant componentwise.
+ * Per vertex i of body b: a, t, d_i and w_i = c + d_i exactly as ocean_body_buoyancy defines them for a probe's
+ * (rx, ry, rz); rec = the 8-float record of ocean_query_surface for the point (w.x, w.z) with K iterations, bit for bit;
+ *       z_i = rec[0] - w_i.y          (the depth of the vertex, positive when submerged)
+ *       r_i = rec[3]
+ * Per triangle (i0, i1, i2): P_k = d_ik (positions relative to the body origin), z_k the depths.  A vertex is wet iff
+ * z > 0 (so z = +0 and z = -0 are dry), and m is the number of wet vertices.
+ *       m = 0: nothing.
+ *       m = 3: one piece (P0, P1, P2; z0, z1, z2).
+ *       m = 1: (A, B, C) = (P0, P1, P2), (P1, P2, P0) or (P2, P0, P1), whichever has the wet vertex first;
+ *              AB = A + (zA / (zA - zB)) * (B - A),   AC = A + (zA / (zA - zC)) * (C - A);
+ *              one piece (A, AB, AC; zA, 0, 0).
+ *       m = 2: (A, B, C) = (P0, P1, P2), (P1, P2, P0) or (P2, P0, P1), whichever has the dry vertex last;
+ *              BC = B + (zB / (zB - zC)) * (C - B),   CA = A + (zA / (zA - zC)) * (C - A);
+ *              two pieces, (A, B, BC; zA, zB, 0) and then (A, BC, CA; zA, 0, 0).
+ *       (X + (zX / (zX - zY)) * (Y - X) is, per component, X.x + t * (Y.x - X.x) with t = zX / (zX - zY) formed once;
+ *        zX > 0 >= zY whenever it is formed, so the divisor is positive.)
+ * Per piece (Q0, Q1, Q2; y0, y1, y2):
+ *       Av = 0.5f * ((Q1 - Q0) x (Q2 - Q0))                          (the area vector, outward)
+ *       S  = (y0 + y1) + y2,   p = S / 3
+ *       F  = -(p * Av)                                                (the integral of -depth n dA)
+ *       Mo = ((Q0 * (y0 + S) + Q1 * (y1 + S)) + Q2 * (y2 + S)) / 12   (the integral of depth r dA, over the area)
+ *       Tq = -(Mo x Av)                                               (the integral of r x (-depth n) dA)
+ *       ar = sqrtf((Av.x * Av.x + Av.y * Av.y) + Av.z * Av.z)
+ *       G  = ar * (((Q0 + Q1) + Q2) / 3)
+ * The sums are defined exactly.  There are 256 lanes.  Lane l accumulates each term from +0, t_l = t_l + term, over its
+ * triangles k = l, l + 256, ... in ascending order, within a triangle piece 1 and then piece 2; the vertex maxima and
+ * the vertex count run over i = l, l + 256, ... alike.  Then for s = 128, 64, ..., 1: t_l = t_l + t_(l xor s) for every
+ * l (fmaxf for the maxima); the result is t_0.  (In numpy: fold the upper half of t onto the lower half until one is
+ * left, as for ocean_body_buoyancy but always over 256 lanes.)
+ *       out[16b + 0..2]   = sum F           (times rho g: the hydrostatic force)
+ *       out[16b + 3]      = sum ar          (the wetted area)
+ *       out[16b + 4..6]   = sum Tq          (times rho g: the torque about the body origin c)
+ *       out[16b + 7]      = fmaxf over the vertices of r_i, from 0
+ *       out[16b + 8..10]  = sum G           (the wetted area's first moment about c)
+ *       out[16b + 11]     = the number of triangles with m > 0
+ *       out[16b + 12]     = fmaxf over the vertices of z_i, from 0        (the draught)
+ *       out[16b + 13]     = the number of wet vertices
+ *       out[16b + 14]     = sum Av.y        (its negative is the waterplane area of a closed hull)
+ *       out[16b + 15]     = 0
+ * The two counts are exact (at most 4096 < 2^24).  For a closed hull under flat water sum F = (0, V, 0) with V the
+ * submerged volume (Archimedes), and sum Tq = (the centre of buoyancy - c) x sum F.  Under waves sum F.x and sum F.z are
+ * the Froude-Krylov surge and sway.  Heave stiffness is rho g times the waterplane area, -out[14].
+ * The library does not inspect vertex or body values: non-finite inputs give unspecified numbers (never an access
+ * outside the textures or the vertex array).  A degenerate triangle adds zero to every sum.  Before the first
+ * ocean_step the water is flat at 0 and the entry is valid; OCEAN_F_DISPLACEMENT_ONLY contexts are valid (only DISP is
+ * read).
+ *
+ * The three forms are those of ocean_body_buoyancy.  ocean_body_hydrostatics takes host buffers and blocks.
+ * ocean_body_hydrostatics_device takes device pointers (vertices, triangles and bodies 4-B aligned, out 16-B aligned,
+ * else OCEAN_E_INVALID_ARG), is async on the ctx stream and bounds count by OCEAN_BODY_MAX_SAMPLES alone; it cannot see
+ * the indices, so its kernel clamps each index into [0, nverts) and never reads outside the vertex array.
+ * ocean_body_hydrostatics_async consumes its three arrays before it returns, runs behind the steps queued so far and
+ * lands count x 64 B in `out` through the readback slots, with the same ocean_readback_status / _wait / _release /
+ * _copy_ms.  *req is NULL after every failure.
+ * All three: OCEAN_E_INVALID_ARG, checked before any device call, the entry's own arguments first and then the context
+ * (as ocean_body_step): a null vertices, triangles, bodies, out or req, iterations outside [0, 16], nverts outside
+ * [1, OCEAN_HULL_MAX_VERTICES], ntris outside [1, OCEAN_HULL_MAX_TRIANGLES], count < 0, count > OCEAN_BODY_MAX_BODIES
+ * (host and async forms, which stage the bodies), count * nverts > OCEAN_BODY_MAX_SAMPLES (in 64 bits), a misaligned
+ * device pointer, in the host and async forms an index outside [0, nverts), a null ctx, a tile out of range; then
+ * OCEAN_E_STATE before ocean_init_spectrum and OCEAN_E_UNSUPPORTED on a column-parity context (as the queries).
+ * count = 0 is a no-op in the blocking and device forms and OCEAN_E_INVALID_ARG in the async form.  The launch counts
+ * as kind 2 of ocean_kernel_stats / ocean_kernel_name. */
+#define OCEAN_HULL_MAX_VERTICES 2048
+#define OCEAN_HULL_MAX_TRIANGLES 4096
+#define OCEAN_HULL_RECORD_FLOATS 16
+int ocean_body_hydrostatics(ocean_ctx *ctx, int tile, int iterations, const float *vertices, int nverts,
+                            const void *triangles, int ntris, const float *bodies, int count, float *out);
+int ocean_body_hydrostatics_device(ocean_ctx *ctx, int tile, int iterations, const float *vertices, int nverts,
+                                   const void *triangles, int ntris, const float *bodies, int count, float *out);
+int ocean_body_hydrostatics_async(ocean_ctx *ctx, int tile, int iterations, const float *vertices, int nverts,
+                                  const void *triangles, int ntris, const float *bodies, int count, float *out,
+                                  ocean_readback **req);
 
 /* The atmosphere: the sky a sea picture reflects, and the colour of the light on it.  In the reference scene the
  * water's environment term (Water.shader:181-187) reads a reflection probe of the skybox, which is Atmosphere.shader

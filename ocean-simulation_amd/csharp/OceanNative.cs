@@ -247,6 +247,19 @@ namespace OceanHip
         public static extern OceanStatus ocean_camera_scene_device(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, [In] float[] box, [In] float[] paint, [In] float[] optics, IntPtr bodies, int stride, int count, IntPtr output, UIntPtr bytes);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern OceanStatus ocean_camera_scene_async(IntPtr ctx, int tile, int mode, int iterations, int steps, int refine, [In] float[] camera, [In] float[] material, int width, int height, [In] float[] box, [In] float[] paint, [In] float[] optics, [In] float[] bodies, int stride, int count, IntPtr dst, UIntPtr bytes, out IntPtr request);
+        // Mesh hulls (added within ABI 4 in the same way): the hydrostatic pressure over the wetted triangles of a mesh
+        // shared by the bodies.  vertices [nverts][3] in the body frame, triangles int [ntris][3] wound counter-clockwise
+        // seen from outside (the header declares them `const void *`: pass the address of a pinned int[]), bodies
+        // [count][10] as the buoyant bodies; 16 floats per body: sum F xyz, wetted area, sum Tq xyz about the origin, worst
+        // residual, the wetted area's first moment xyz, wet triangles, draught, wet vertices, sum Av.y, 0.  Always in
+        // surface mode.
+        public const int HullMaxVertices = 2048, HullMaxTriangles = 4096, HullRecordFloats = 16;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_hydrostatics(IntPtr ctx, int tile, int iterations, [In] float[] vertices, int nverts, IntPtr triangles, int ntris, [In] float[] bodies, int count, [Out] float[] output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_hydrostatics_device(IntPtr ctx, int tile, int iterations, IntPtr vertices, int nverts, IntPtr triangles, int ntris, IntPtr bodies, int count, IntPtr output);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern OceanStatus ocean_body_hydrostatics_async(IntPtr ctx, int tile, int iterations, [In] float[] vertices, int nverts, IntPtr triangles, int ntris, [In] float[] bodies, int count, IntPtr dst, out IntPtr request);
         // The atmosphere (added within ABI 4 in the same way; ocean.h "The atmosphere"): the three look-up tables of
         // AtmosphereController.cs, owned by the context.  `parameters` = 32 floats (ocean.h names them); the six sizes all 0
         // select the reference's.  ocean_sky_update is the per-frame call; CameraColor | CameraSkyLut then shades the

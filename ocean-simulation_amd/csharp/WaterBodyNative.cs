@@ -233,6 +233,28 @@ namespace OceanHip
             return output;
         }
 
+        // The hydrostatic pressure over the wetted triangles of a mesh shared by M bodies (ocean.h ocean_body_hydrostatics):
+        // vertices [V][3] in the body frame, triangles [T][3] wound counter-clockwise seen from outside, bodies [M][10] as
+        // Buoyancy takes them; per body 16 floats: sum F, wetted area, sum Tq about the origin, worst residual, the wetted
+        // area's first moment, wet triangles, draught, wet vertices, sum Av.y, 0.  Force rho g out[0..2], torque
+        // rho g out[4..6], heave stiffness rho g (-out[14]).  The reference has no counterpart.
+        public float[] Hydrostatics(float[] vertices, int[] triangles, float[] bodies, int iterations = 4)
+        {
+            var output = new float[bodies.Length / 10 * OceanNative.HullRecordFloats];
+            var pin = System.Runtime.InteropServices.GCHandle.Alloc(triangles, System.Runtime.InteropServices.GCHandleType.Pinned);
+            try
+            {
+                OceanNative.Check(OceanNative.ocean_body_hydrostatics(ctx, 0, iterations, vertices, vertices.Length / 3,
+                                                                      pin.AddrOfPinnedObject(), triangles.Length / 3, bodies,
+                                                                      bodies.Length / 10, output), "ocean_body_hydrostatics");
+            }
+            finally
+            {
+                pin.Free();
+            }
+            return output;
+        }
+
         // Buoyancy's records with the drag against the water's own velocity beside them (ocean.h ocean_body_dynamics;
         // `velocity` set before Awake): motion is [M][6] = (world linear velocity of the body origin, world angular
         // velocity); per body 16 floats: Buoyancy's 8, then sum F, sum T about the origin, the largest relative speed

@@ -1,5 +1,5 @@
 // C-ABI layer of liboceanhip.so, the point consumers (ocean.h): surface and velocity queries, surface grids,
-// buoyant bodies, body dynamics, body steps, ray casts, whitecap emitters, spray particles and camera views (without
+// buoyant bodies, body dynamics, body steps, mesh hulls, ray casts, whitecap emitters, spray particles and camera views (without
 // the bodies, with them, and with the water seeing them), each in a _device, a blocking host
 // and an _async form; and world sampling and the surface bounds, which keep bodies of their own.
 //
@@ -342,6 +342,72 @@ struct BodyStep : BodyBuoyancy {
                      "body_step");
     }
 };
+
+// Mesh hulls: bodies float[count][10], vertices float[nverts][3] and triangles int[ntris][3] -> records
+// float[count][16]; always in surface mode.  Its own arguments first, none of which needs the context (as the body
+// steps': a host learns of a bad argument whatever its context is), the _device form's alignment and the staged forms'
+// look at the indices among them; then the context and the tile.  At the limits the staged forms carry 320 KiB of
+// bodies, 24 KiB of vertices and 48 KiB of indices in, and 512 KiB of records out: the point queries' place in a slot.
+struct BodyHydrostatics {
+    ocean_ctx* ctx;
+    int tile, iterations;
+    const float* vertices;
+    int nverts;
+    const int* triangles;
+    int ntris;
+    const float* bodies;
+    int count;
+    float* out;
+
+    int check(Form form) const {
+        if (!vertices || !triangles || !bodies || !out)
+            return fail(OCEAN_E_INVALID_ARG, "null vertices, triangles, bodies or output");
+        if (int r = check_iterations(iterations)) return r;
+        if (nverts < 1 || nverts > OCEAN_HULL_MAX_VERTICES)
+            return fail(OCEAN_E_INVALID_ARG, "nverts = " + std::to_string(nverts) + " outside [1, OCEAN_HULL_MAX_VERTICES]");
+        if (ntris < 1 || ntris > OCEAN_HULL_MAX_TRIANGLES)
+            return fail(OCEAN_E_INVALID_ARG, "ntris = " + std::to_string(ntris) + " outside [1, OCEAN_HULL_MAX_TRIANGLES]");
+        if (count < 0) return fail(OCEAN_E_INVALID_ARG, "negative body count");
+        if (form != Form::Device && count > OCEAN_BODY_MAX_BODIES)
+            return fail(OCEAN_E_INVALID_ARG, "body count " + std::to_string(count) + " > OCEAN_BODY_MAX_BODIES");
+        const uint64_t samples = (uint64_t)count * (uint64_t)nverts;
+        if (samples > (uint64_t)OCEAN_BODY_MAX_SAMPLES)
+            return fail(OCEAN_E_INVALID_ARG, "count * nverts = " + std::to_string(samples) + " > OCEAN_BODY_MAX_SAMPLES");
+        if (form == Form::Device) {
+            if (int r = check_aligned(state().entry, inputs(), out)) return r;
+        } else {  // the staged forms see the indices; the device form's kernel clamps them
+            for (size_t k = 0; k < (size_t)ntris * 3; ++k)
+                if (triangles[k] < 0 || triangles[k] >= nverts)
+                    return fail(OCEAN_E_INVALID_ARG, "triangles[" + std::to_string(k / 3) + "][" + std::to_string(k % 3) +
+                                                         "] = " + std::to_string(triangles[k]) + " outside [0, nverts)");
+        }
+        if (!ctx) return fail(OCEAN_E_INVALID_ARG, "null context");
+        return check_tile(ctx, tile);
+    }
+    StateRule state() const { return {"ocean_body_hydrostatics", "hydrostatics on"}; }
+    StagedInputs inputs() const {
+        return {"vertices, triangles and bodies",
+                3,
+                {{bodies, (size_t)count * 10 * 4}, {vertices, (size_t)nverts * 3 * 4}, {triangles, (size_t)ntris * 3 * 4}}};
+    }
+    size_t out_bytes() const { return (size_t)count * OCEAN_HULL_RECORD_FLOATS * 4; }
+    const char* lacks() const { return count == 0 ? "bodies" : nullptr; }
+    int launch(const float* const* in, float* d_out) const {
+        const ocean::DevView v = ctx->view();
+        return timed(ctx, 2,
+                     [&] {
+                         return ocean::launch_body_hydrostatics(v, tile, iterations, in[1], nverts,
+                                                                reinterpret_cast<const int*>(in[2]), ntris, in[0], count,
+                                                                d_out, ctx->stream);
+                     },
+                     "body_hydrostatics");
+    }
+};
+static_assert((size_t)OCEAN_BODY_MAX_BODIES * 10 * 4 + (size_t)OCEAN_HULL_MAX_VERTICES * 3 * 4 +
+                      (size_t)OCEAN_HULL_MAX_TRIANGLES * 3 * 4 <= kQuerySlotBytes - kQueryPointsOffset,
+              "a slot's pinned input copy holds every hydrostatics request");
+static_assert((size_t)OCEAN_BODY_MAX_BODIES * OCEAN_HULL_RECORD_FLOATS * 4 <= kQueryPointsOffset,
+              "the records end before the inputs");
 
 // Tile `tile`'s bounds records on the device, float[C][8], current on the ctx stream once this returns: the
 // two bounds launches (kind 2 of ocean_kernel_stats) are enqueued unless the cached records still match DISP.
@@ -809,6 +875,26 @@ int ocean_body_step_async(ocean_ctx* ctx, int tile, int mode, int iterations, in
                           const float* hull, int probes, const float* props, const float* state, int count, float* out,
                           ocean_readback** req) {
     return async_form(BodyStep{{ctx, tile, mode, iterations, hull, probes, state, count, out}, law, substeps, step, props},
+                      req);
+}
+
+int ocean_body_hydrostatics_device(ocean_ctx* ctx, int tile, int iterations, const float* vertices, int nverts,
+                                   const void* triangles, int ntris, const float* bodies, int count, float* out) {
+    return device_form(BodyHydrostatics{ctx, tile, iterations, vertices, nverts, static_cast<const int*>(triangles), ntris,
+                                        bodies, count, out});
+}
+
+int ocean_body_hydrostatics(ocean_ctx* ctx, int tile, int iterations, const float* vertices, int nverts,
+                            const void* triangles, int ntris, const float* bodies, int count, float* out) {
+    return host_form(BodyHydrostatics{ctx, tile, iterations, vertices, nverts, static_cast<const int*>(triangles), ntris,
+                                      bodies, count, out});
+}
+
+int ocean_body_hydrostatics_async(ocean_ctx* ctx, int tile, int iterations, const float* vertices, int nverts,
+                                  const void* triangles, int ntris, const float* bodies, int count, float* out,
+                                  ocean_readback** req) {
+    return async_form(BodyHydrostatics{ctx, tile, iterations, vertices, nverts, static_cast<const int*>(triangles), ntris,
+                                       bodies, count, out},
                       req);
 }
 

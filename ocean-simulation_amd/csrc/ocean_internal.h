@@ -196,6 +196,12 @@ struct BodyStepParams {
 hipError_t launch_body_step(const DevView& v, const float4* vel, int tile, int mode, int iterations, int law, int substeps,
                             const BodyStepParams& sp, const float* hull, int probes, const float* props,
                             const float* state, int count, float* out, hipStream_t s);
+// hull.hip: hydrostatic pressure over the wetted triangles of a mesh hull (ocean_body_hydrostatics*), device pointers:
+// vertices float[nverts][3], triangles int[ntris][3] (an index outside [0, nverts) is clamped into it), bodies
+// float[count][10], out float[count][16]
+hipError_t launch_body_hydrostatics(const DevView& v, int tile, int iterations, const float* vertices, int nverts,
+                                    const int* triangles, int ntris, const float* bodies, int count, float* out,
+                                    hipStream_t s);
 // velocity.hip: surface velocity (OCEAN_F_VELOCITY).  `scratch` is the context's two velocity planes, float2
 // [2][U][N][N] plane-major: launch_evolve_velocity writes the packed planes of dh/dt at t there (from v.h0 and
 // v.waves), the operator IFFT transforms them in place as 2 U unit-planes, launch_pack_velocity interleaves them

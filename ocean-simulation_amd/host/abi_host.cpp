@@ -4,7 +4,7 @@
 // -> OnDisable.  tests/test_gpu_host.py runs it and checks every number it writes
 // against the same sequence through the Python binding and against the oracle.
 //
-//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|camera_bodies|camera_scene|sky|step|spray]
+//   abi_host <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|camera_bodies|camera_scene|sky|step|spray|hydrostatics]
 //
 // With step the host plays F frames on a velocity context and, behind each, advances a fleet of six boxes of 4 x 3
 // probes by 4 substeps of 1/240 s through one WaterBody::StepBodies in its async form (surface mode, 4 steps,
@@ -54,6 +54,10 @@
 // boxes of 4 x 3 probes (surface mode, 4 steps) and writes hull.bin (float32 [12][5]), bodies.bin (float32
 // [5][10]) and buoyancy.bin (float32 [5][8]); the summary line carries the records too ("records", %.9g: exact
 // for fp32); tests/test_gpu_body_host.py checks them.
+// With hydrostatics the host reads nothing back per frame: it runs F steps, then one WaterBody::Hydrostatics for five
+// boxes of the mesh of the box 2 x 1 x 3 (8 vertices, 12 triangles; 4 steps) and writes vertices.bin (float32 [8][3]),
+// triangles.bin (int32 [12][3]), bodies.bin (float32 [5][10]) and hydrostatics.bin (float32 [5][16]); the summary line
+// carries the records too ("records", %.9g: exact for fp32); tests/test_gpu_hull_host.py checks them.
 // With probes the host reads no slice back: it sets five probes, runs F Updates (one surface query per
 // frame, water_body.h Readback::Probes) and writes probe_heights.bin (float32 [F][5]: ProbeHeights after
 // each Update, zeros before any query has landed), probe_results.bin (float32 [5][8]: the last query,
@@ -85,14 +89,14 @@ void write_bin(const std::string& path, const float* data, size_t count) {
 
 int main(int argc, char** argv) {
     if (argc != 5 && argc != 6) {
-        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|camera_bodies|camera_scene|sky|step|spray]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <outdir> <n> <cascades> <frames> [height|rgba|probes|buoyancy|velocity|rays|dynamics|whitecaps|camera|camera_bodies|camera_scene|sky|step|spray|hydrostatics]\n", argv[0]);
         return 2;
     }
     const std::string mode = argc == 6 ? argv[5] : "height";
     if (mode != "height" && mode != "rgba" && mode != "probes" && mode != "buoyancy" && mode != "velocity" &&
         mode != "rays" && mode != "dynamics" && mode != "whitecaps" && mode != "camera" && mode != "camera_bodies" &&
-        mode != "camera_scene" && mode != "sky" && mode != "step" && mode != "spray") {
-        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps, camera, camera_bodies, camera_scene, sky, step or spray\n");
+        mode != "camera_scene" && mode != "sky" && mode != "step" && mode != "spray" && mode != "hydrostatics") {
+        std::fprintf(stderr, "usage: readback mode must be height, rgba, probes, buoyancy, velocity, rays, dynamics, whitecaps, camera, camera_bodies, camera_scene, sky, step, spray or hydrostatics\n");
         return 2;
     }
     const std::string out = argv[1];
@@ -148,6 +152,42 @@ int main(int argc, char** argv) {
             write_bin(out + (dynamics ? "/dynamics.bin" : "/buoyancy.bin"), rec.data(), rec.size());
             std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"probes\": %zu, \"bodies\": %zu, \"records\": [", F, n,
                         (int)wb.cascades.size(), hull.size() / 5, bodies.size() / 10);
+            for (size_t i = 0; i < rec.size(); ++i) std::printf("%s%.9g", i ? ", " : "", rec[i]);
+            std::printf("]}\n");
+            wb.OnDisable();
+            return 0;
+        }
+        if (mode == "hydrostatics") {
+            // the box 2 x 1 x 3 as a closed mesh: corner ix + 2 iy + 4 iz, each face two triangles wound outward
+            std::vector<float> vertices;
+            for (int k = 0; k < 8; ++k) {
+                const float corner[3] = {(k & 1) ? 1.0f : -1.0f, (k & 2) ? 0.5f : -0.5f, (k & 4) ? 1.5f : -1.5f};
+                vertices.insert(vertices.end(), corner, corner + 3);
+            }
+            const int faces[6][4] = {{0, 4, 6, 2}, {1, 3, 7, 5}, {0, 1, 5, 4}, {2, 6, 7, 3}, {0, 2, 3, 1}, {4, 5, 7, 6}};
+            std::vector<int> triangles;
+            for (const auto& q : faces) {
+                const int two[6] = {q[0], q[1], q[2], q[0], q[2], q[3]};
+                triangles.insert(triangles.end(), two, two + 6);
+            }
+            // five boxes across the surface: origin, body -> world quaternion (x, y, z, w), scale
+            const std::vector<float> bodies = {
+                0.0f,    0.0f,   0.0f,     0.0f,  0.0f,  0.0f,  1.0f,  1.0f, 1.0f,  1.0f,
+                37.5f,   0.25f,  -12.25f,  0.5f,  0.5f,  0.5f,  0.5f,  1.5f, 2.0f,  0.5f,
+                -410.0f, -0.5f,  250.75f,  0.0f,  0.0f,  0.6f,  0.8f,  2.0f, 1.5f,  1.0f,
+                1e4f,    0.125f, -3333.0f, 0.28f, 0.0f,  0.0f,  0.96f, 1.0f, 0.75f, 2.0f,
+                -0.5f,   -0.25f, (float)n, 0.0f,  -0.6f, 0.0f,  0.8f,  0.5f, 3.0f,  1.0f};
+            wb.readback = ocean_host::Readback::Probes;  // with no probes set, Update requests nothing
+            wb.Awake();
+            for (int f = 0; f < F; ++f) wb.Update((float)f / 60.0f);
+            const std::vector<float> rec = wb.Hydrostatics(vertices, triangles, bodies);
+            write_bin(out + "/vertices.bin", vertices.data(), vertices.size());
+            static_assert(sizeof(int) == sizeof(float), "triangles.bin is written as 4-byte words");
+            write_bin(out + "/triangles.bin", reinterpret_cast<const float*>(triangles.data()), triangles.size());
+            write_bin(out + "/bodies.bin", bodies.data(), bodies.size());
+            write_bin(out + "/hydrostatics.bin", rec.data(), rec.size());
+            std::printf("{\"frames\": %d, \"n\": %d, \"cascades\": %d, \"vertices\": %zu, \"triangles\": %zu, \"bodies\": %zu, \"records\": [",
+                        F, n, (int)wb.cascades.size(), vertices.size() / 3, triangles.size() / 3, bodies.size() / 10);
             for (size_t i = 0; i < rec.size(); ++i) std::printf("%s%.9g", i ? ", " : "", rec[i]);
             std::printf("]}\n");
             wb.OnDisable();

@@ -20,6 +20,7 @@
 //   raycast <iterations> <steps> <refine> <rays.bin>
 //   body_buoyancy <mode> <iterations> <hull.bin> <bodies.bin>
 //   body_dynamics <mode> <iterations> <law> <hull.bin> <bodies.bin> <motion.bin>
+//   body_hydrostatics <iterations> <vertices.bin> <triangles.bin> <bodies.bin>    (triangles.bin holds int32)
 //   sample_world <points.bin>
 //   surface_bounds
 //   read <texture> <cascade>                                                ocean_read of tile 0
@@ -65,7 +66,7 @@ struct OpShape {
 };
 const OpShape kOps[] = {{"step", 1},          {"grid", 9},          {"camera", 8},        {"whitecaps", 9},
                         {"query_surface", 3}, {"query_velocity", 2}, {"raycast", 4},       {"body_buoyancy", 4},
-                        {"body_dynamics", 6}, {"sample_world", 1},  {"surface_bounds", 0}, {"read", 2},
+                        {"body_dynamics", 6}, {"body_hydrostatics", 4}, {"sample_world", 1},  {"surface_bounds", 0}, {"read", 2},
                         {"read_height_async", 1}, {"grid_async", 9}, {"wait", 0}};
 
 int usage(const char* argv0, const std::string& why) {
@@ -339,6 +340,13 @@ int main(int argc, char** argv) {
                     res.rc = ocean_body_dynamics(ctx, 0, integer(a[0]), integer(a[1]), integer(a[2]), hull.data(),
                                                  (int)(hull.size() / 5), bodies.data(), motion.data(),
                                                  (int)(bodies.size() / 10), out.data());
+                } else if (op.name == "body_hydrostatics") {
+                    // the indices travel as the bytes the file holds: `file` reads 4-byte words and changes none
+                    const std::vector<float> vertices = file(a[1]), triangles = file(a[2]), bodies = file(a[3]);
+                    prepare(bodies.size() / 10 * OCEAN_HULL_RECORD_FLOATS);
+                    res.rc = ocean_body_hydrostatics(ctx, 0, integer(a[0]), vertices.data(), (int)(vertices.size() / 3),
+                                                     triangles.data(), (int)(triangles.size() / 3), bodies.data(),
+                                                     (int)(bodies.size() / 10), out.data());
                 } else if (op.name == "sample_world") {
                     const std::vector<float> points = file(a[0]);
                     prepare(points.size() / 3 * 12);

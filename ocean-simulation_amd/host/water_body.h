@@ -212,6 +212,20 @@ public:
         return out;
     }
 
+    // The hydrostatic pressure over the wetted triangles of a mesh shared by M bodies (ocean.h ocean_body_hydrostatics):
+    // vertices [V][3] in the body frame, triangles [T][3] wound counter-clockwise seen from outside, bodies [M][10] as
+    // Buoyancy takes them -> 16 floats per body: sum F, wetted area, sum Tq about the origin, worst residual, the wetted
+    // area's first moment, wet triangles, draught, wet vertices, sum Av.y, 0.  Force rho g out[0..2], torque
+    // rho g out[4..6], heave stiffness rho g (-out[14]).  The reference has no counterpart.
+    std::vector<float> Hydrostatics(const std::vector<float>& vertices, const std::vector<int>& triangles,
+                                    const std::vector<float>& bodies, int iterations = 4) const {
+        std::vector<float> out(bodies.size() / 10 * OCEAN_HULL_RECORD_FLOATS);
+        check(ocean_body_hydrostatics(ctx_, 0, iterations, vertices.data(), (int)(vertices.size() / 3), triangles.data(),
+                                      (int)(triangles.size() / 3), bodies.data(), (int)(bodies.size() / 10), out.data()),
+              "ocean_body_hydrostatics");
+        return out;
+    }
+
     // Buoyancy's records with the drag against the water's own velocity beside them (ocean.h ocean_body_dynamics;
     // `velocity` set before Awake): motion [M][6] = (world linear velocity of the body origin, world angular
     // velocity) -> 16 floats per body: Buoyancy's 8, then sum F, sum T about the origin, the largest relative speed

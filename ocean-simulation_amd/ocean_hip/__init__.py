@@ -79,6 +79,7 @@ EXPORTED_SYMBOLS = (
     "ocean_spray_step", "ocean_spray_step_device", "ocean_spray_step_async",
     "ocean_camera_bodies", "ocean_camera_bodies_device", "ocean_camera_bodies_async",
     "ocean_camera_scene", "ocean_camera_scene_device", "ocean_camera_scene_async",
+    "ocean_body_hydrostatics", "ocean_body_hydrostatics_device", "ocean_body_hydrostatics_async",
 )
 
 # ocean_query_surface* modes and limits (ocean.h)
@@ -132,6 +133,10 @@ BODY_STRIDE_MIN, BODY_STRIDE_MAX = 10, 64
 # size of its optics array (ocean.h)
 CAMERA_LINKS = 3
 SCENE_OPTICS_FLOATS = 6
+# ocean_body_hydrostatics*: the mesh's limits and the record's size (ocean.h); the body limits are the bodies'
+HULL_MAX_VERTICES = 2048
+HULL_MAX_TRIANGLES = 4096
+HULL_RECORD_FLOATS = 16
 
 
 class OceanError(RuntimeError):
@@ -246,6 +251,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "ocean_camera_scene": ([P, i, i, i, i, i, P, P, i, i, P, P, P, P, i, i, P, sz], i),
         "ocean_camera_scene_device": ([P, i, i, i, i, i, P, P, i, i, P, P, P, P, i, i, P, sz], i),
         "ocean_camera_scene_async": ([P, i, i, i, i, i, P, P, i, i, P, P, P, P, i, i, P, sz, ctypes.POINTER(P)], i),
+        "ocean_body_hydrostatics": ([P, i, i, P, i, P, i, P, i, P], i),
+        "ocean_body_hydrostatics_device": ([P, i, i, P, i, P, i, P, i, P], i),
+        "ocean_body_hydrostatics_async": ([P, i, i, P, i, P, i, P, i, P, ctypes.POINTER(P)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -1108,6 +1116,88 @@ class OceanContext:
                "ocean_body_step_device")
 
     @staticmethod
+    def _mesh_args(vertices, triangles, bodies):
+        v = np.ascontiguousarray(vertices, np.float32)
+        t = np.ascontiguousarray(triangles, np.int32)
+        b = np.ascontiguousarray(bodies, np.float32)
+        if v.ndim != 2 or v.shape[1] != 3:
+            raise ValueError(f"vertices must be float32[V][3] in the body frame, got {v.shape}")
+        if t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError(f"triangles must be int32[T][3], counter-clockwise seen from outside, got {t.shape}")
+        if b.ndim != 2 or b.shape[1] != 10:
+            raise ValueError(f"bodies must be float32[M][10] = (c, quaternion xyzw, scale), got {b.shape}")
+        return v, t, b
+
+    def body_hydrostatics(self, vertices, triangles, bodies, iterations: int = 4, tile: int = 0) -> np.ndarray:
+        """Mesh hulls on the device (ocean.h ocean_body_hydrostatics), blocking: vertices float[V][3] in the body frame
+        and triangles int[T][3] (outward-wound), shared by the bodies float[M][10] as body_buoyancy takes them ->
+        float32[M][16]: (sum F xyz, wetted area, sum Tq xyz about the origin, worst residual, the wetted area's first
+        moment xyz, wet triangles, draught, wet vertices, sum Av.y, 0).  rho g times out[0:3] and out[4:7] are the
+        hydrostatic force and torque; -out[14] is the waterplane area of a closed hull."""
+        v, t, b = self._mesh_args(vertices, triangles, bodies)
+        out = np.empty((b.shape[0], HULL_RECORD_FLOATS), np.float32)
+        _check(self.lib.ocean_body_hydrostatics(self._h, tile, iterations, v.ctypes.data, v.shape[0], t.ctypes.data,
+                                                t.shape[0], b.ctypes.data, b.shape[0], out.ctypes.data),
+               "ocean_body_hydrostatics")
+        return out
+
+    def body_hydrostatics_async(self, vertices, triangles, bodies, iterations: int = 4, tile: int = 0,
+                                buf: "PinnedBuffer" = None) -> "Readback":
+        """The per-frame form (ocean_body_hydrostatics_async), as body_buoyancy_async: float32[M][16] lands in pinned
+        host memory; the three arrays are consumed by the call.  `buf`: a caller-owned pinned slot of at least
+        M x 64 B."""
+        v, t, b = self._mesh_args(vertices, triangles, bodies)
+        return Readback(self, (b.shape[0], HULL_RECORD_FLOATS), b.shape[0] * HULL_RECORD_FLOATS * 4,
+                        "ocean_body_hydrostatics_async",
+                        lambda dst, req: self.lib.ocean_body_hydrostatics_async(self._h, tile, iterations, v.ctypes.data,
+                                                                                v.shape[0], t.ctypes.data, t.shape[0],
+                                                                                b.ctypes.data, b.shape[0], dst, req), buf)
+
+    def body_hydrostatics_device(self, vertices_ptr: int, nverts: int, triangles_ptr: int, ntris: int, bodies_ptr: int,
+                                 count: int, out_ptr: int, iterations: int = 4, tile: int = 0) -> None:
+        """The device-pointer form (ocean_body_hydrostatics_device): vertices float[nverts][3], triangles int[ntris][3],
+        bodies float[count][10] and out float[count][16] live on this context's device (inputs 4-B, out 16-B aligned);
+        async on the context's stream, after the queued steps.  The kernel clamps each index into [0, nverts)."""
+        vp = ctypes.c_void_p
+        _check(self.lib.ocean_body_hydrostatics_device(self._h, tile, iterations, vp(vertices_ptr), nverts,
+                                                       vp(triangles_ptr), ntris, vp(bodies_ptr), count, vp(out_ptr)),
+               "ocean_body_hydrostatics_device")
+
+    @staticmethod
+    def box_mesh(sx: float, sy: float, sz: float, nx: int = 1, ny: int = 1, nz: int = 1):
+        """The box [-sx/2, sx/2] x [-sy/2, sy/2] x [-sz/2, sz/2] as a closed triangle mesh, each face cut into a
+        lattice of nx, ny, nz cells along x, y, z and every cell into two triangles: (vertices float32[V][3],
+        triangles int32[T][3]), wound counter-clockwise seen from outside.  The lattice points on edges and corners are
+        shared: V = 2 (nx ny + ny nz + nz nx) + 2 and T = 4 (nx ny + ny nz + nz nx); (1, 1, 1) is 8 and 12."""
+        if nx < 1 or ny < 1 or nz < 1:
+            raise ValueError("nx, ny and nz must be at least 1")
+        n = (nx, ny, nz)
+        size = (float(sx), float(sy), float(sz))
+        ids, verts, tris = {}, [], []
+
+        def vertex(g):
+            if g not in ids:
+                ids[g] = len(verts)
+                verts.append([size[a] * (g[a] / n[a] - 0.5) for a in range(3)])
+            return ids[g]
+
+        for axis in range(3):
+            u, w = (axis + 1) % 3, (axis + 2) % 3  # e_u x e_w = e_axis
+            for side in (0, 1):
+                for j in range(n[w]):
+                    for i in range(n[u]):
+                        def at(di, dj):
+                            g = [0, 0, 0]
+                            g[axis], g[u], g[w] = side * n[axis], i + di, j + dj
+                            return vertex(tuple(g))
+                        q = (at(0, 0), at(1, 0), at(1, 1), at(0, 1))  # counter-clockwise seen from +axis
+                        if side == 0:
+                            q = q[::-1]
+                        tris.append([q[0], q[1], q[2]])
+                        tris.append([q[0], q[2], q[3]])
+        return np.asarray(verts, np.float32), np.asarray(tris, np.int32)
+
+    @staticmethod
     def box_hull(nx: int, nz: int, ny: int = 1) -> np.ndarray:
         """The unit box [-1/2, 1/2]^3 cut into nx x ny x nz cells, as a hull float32[nx * ny * nz][5]: each
         probe is its cell's centre ((i + 1/2) / n - 1/2 along each axis), h = 1 / ny, v = 1 / (nx ny nz); x
@@ -1572,6 +1662,12 @@ class WaterBody:
         """BuoyantObject.FixedUpdate's lookup for M bodies of P probes each (OceanContext.body_buoyancy): the
         displaced volume, where it acts and the water plane under every hull, float32[M][8]."""
         return self.ctx.body_buoyancy(hull, bodies, iterations, mode, tile)
+
+    def Hydrostatics(self, vertices, triangles, bodies, iterations: int = 4, tile: int = 0) -> np.ndarray:
+        """The hydrostatic force, torque, wetted and waterplane area of M bodies that share a triangle mesh
+        (OceanContext.body_hydrostatics), float32[M][16].  The reference has no counterpart: its BuoyantObject is one
+        probe."""
+        return self.ctx.body_hydrostatics(vertices, triangles, bodies, iterations, tile)
 
     def Dynamics(self, hull, bodies, motion, iterations: int = 4, mode: int = QUERY_SURFACE, law: int = DRAG_LINEAR,
                  tile: int = 0) -> np.ndarray:
