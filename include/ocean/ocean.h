@@ -125,7 +125,8 @@ enum ocean_texture {
     OCEAN_TEX_PLANE3 = 6, /* _DxxDzzTextures */
     OCEAN_TEX_DISP = 7,   /* _DisplacementsTextures        ResultTexturesFiller.compute:7 */
     OCEAN_TEX_DERIV = 8,  /* _DerivativesTextures          ResultTexturesFiller.compute:8 */
-    OCEAN_TEX_TURB = 9,   /* _TurbulenceTextures (foam state) ResultTexturesFiller.compute:9 */
+    OCEAN_TEX_TURB = 9,   /* _TurbulenceTextures (foam state) ResultTexturesFiller.compute:9; the array may be
+                             written on demand from the 4-byte state (ocean_step, "Deferred TURB") */
     OCEAN_TEX_NORMAL = 10, /* derived: normalize(-Dyx/(1+Dxx), 1, -Dyz/(1+Dzz)), w = 0 */
     OCEAN_TEX_VELOCITY = 11 /* derived: d/dt of DISP.xyz, and dDxz/dt in .w (OCEAN_F_VELOCITY only;
                                E_INVALID_ARG on any other context; written like OCEAN_TEX_NORMAL) */
@@ -204,7 +205,18 @@ int ocean_reset_foam(ocean_ctx *ctx);
 /* Replaces CalculateWavesTexturesAtTime(time) (WaterBody.cs:180-193, minus
  * GenerateMips): evolve -> 2D IFFT of every plane -> fill/foam for all tiles
  * and cascades.  Async on the ctx stream.  Fused 2-kernel schedule by default;
- * OCEAN_F_UNFUSED selects the reference-shaped one (same results to rounding). */
+ * OCEAN_F_UNFUSED selects the reference-shaped one (same results to rounding).
+ *
+ * Deferred TURB.  TURB is (f, f, f, f) of the 4-byte foam state f the step keeps beside it, and every consumer
+ * in this library reads .x alone.  A frame whose column passes are all pass BQ (N = 512 or 1024, full outputs,
+ * h0 from ocean_init_spectrum, whole column band, fused schedule) therefore stores the foam state only: the
+ * consumers of the finished textures (ocean_sample_world, the queries, grids, bodies, ray casts, whitecaps, spray,
+ * cameras) tap the state as TURB's level 0, bit-identical to tapping the array, and OCEAN_F_MIPS chains are boxed
+ * from the state as always.  The float4 array is written from the state, by one kernel of kind 2 on the ctx stream,
+ * when an entry shows the array itself: ocean_read, ocean_read_mip level 0 and ocean_read_async of OCEAN_TEX_TURB,
+ * ocean_write of it (before the upload, so that the other slices hold), ocean_set_column_band of a band narrower than N, and
+ * ocean_get_device_ptr (below).  What these entries return is what a context that writes TURB every frame returns.
+ * OCEAN_DEFER_TURB=0 makes every frame write the array. */
 int ocean_step(ocean_ctx *ctx, float time);
 
 /* Column band for splitting one (tile, cascade) unit over several GPUs (SURVEY.md 8e,
@@ -261,7 +273,11 @@ int ocean_read(ocean_ctx *ctx, int texture, int tile, int cascade, void *dst, si
 int ocean_write(ocean_ctx *ctx, int texture, int tile, int cascade, const void *src, size_t bytes);
 
 /* Zero-copy access for same-process consumers: base device pointer and total
- * byte size of a texture (all tiles and cascades). */
+ * byte size of a texture (all tiles and cascades).
+ * OCEAN_TEX_TURB: the call writes the array from the foam state if a deferred frame (ocean_step) has left it
+ * stale, stream-ordered, and from then on every ocean_step of this context writes TURB, for the life of the
+ * context: a reader through the pointer cannot be seen.  A renderer takes the pointer once, before its first
+ * frame, and then runs the frames this library ran before TURB could be deferred. */
 int ocean_get_device_ptr(ocean_ctx *ctx, int texture, void **ptr, size_t *bytes);
 
 /* The ctx's hipStream_t (as void*), for callers that order their own work. */

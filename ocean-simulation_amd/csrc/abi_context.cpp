@@ -49,6 +49,15 @@ void* tex_ptr(ocean_ctx* ctx, int tex, size_t* elem_bytes, size_t* slices) {
 
 }  // namespace
 
+int materialise_turb(ocean_ctx* ctx) {
+    if (!ctx->turb_stale) return OCEAN_OK;
+    const ocean::DevView v = ctx->view();
+    if (int r = timed(ctx, 2, [&] { return ocean::launch_turb_materialise(v, ctx->stream); }, "turb_materialise"))
+        return r;
+    ctx->turb_stale = false;
+    return OCEAN_OK;
+}
+
 int slice_ptr(ocean_ctx* ctx, int tex, int tile, int cascade, size_t bytes, char** out) {
     size_t eb = 0, slices = 0;
     void* base = tex_ptr(ctx, tex, &eb, &slices);
@@ -340,6 +349,7 @@ int ocean_init_spectrum(ocean_ctx* ctx) {
 int ocean_reset_foam(ocean_ctx* ctx) {
     OCEAN_ENTER(ctx);
     if (ctx->turb) OCEAN_HIP(hipMemsetAsync(ctx->turb, 0, ctx->texels() * ctx->units() * 16, ctx->stream));
+    ctx->turb_stale = false;  // deferred TURB: the array and the foam state are both zero, so the array is whole
     if (ctx->foam) OCEAN_HIP(hipMemsetAsync(ctx->foam, 0, ctx->texels() * ctx->units() * 4, ctx->stream));
     if (ctx->turb_mips) OCEAN_HIP(hipMemsetAsync(ctx->turb_mips, 0, ctx->mip_chain * ctx->units() * 16, ctx->stream));
     return OCEAN_OK;
@@ -350,6 +360,8 @@ int ocean_read(ocean_ctx* ctx, int texture, int tile, int cascade, void* dst, si
     if (!dst) return fail(OCEAN_E_INVALID_ARG, "null destination");
     char* src = nullptr;
     if (int r = slice_ptr(ctx, texture, tile, cascade, bytes, &src)) return r;
+    if (texture == OCEAN_TEX_TURB)  // deferred TURB: the array from the foam state first
+        if (int r = materialise_turb(ctx)) return r;
     OCEAN_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     OCEAN_HIP(hipStreamSynchronize(ctx->stream));
     return OCEAN_OK;
@@ -408,6 +420,8 @@ int ocean_write(ocean_ctx* ctx, int texture, int tile, int cascade, const void* 
                                          "OCEAN_F_UNFUSED to drive ocean_step from uploaded wave data");
     char* dst = nullptr;
     if (int r = slice_ptr(ctx, texture, tile, cascade, bytes, &dst)) return r;
+    if (texture == OCEAN_TEX_TURB)  // deferred TURB: the other slices are whole before the import below reads them
+        if (int r = materialise_turb(ctx)) return r;
     OCEAN_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     OCEAN_HIP(hipStreamSynchronize(ctx->stream));
     if (texture == OCEAN_TEX_NOISE) ctx->noise_set[tile] = true;
@@ -431,6 +445,13 @@ int ocean_get_device_ptr(ocean_ctx* ctx, int texture, void** ptr, size_t* bytes)
     void* base = tex_ptr(ctx, texture, &eb, &slices);
     if (!base) return fail(OCEAN_E_INVALID_ARG, "texture not allocated for this context's flags");
     if (texture == OCEAN_TEX_DISP) ctx->disp_exposed = true;  // a foreign writer: the surface bounds are not cached
+    if (texture == OCEAN_TEX_TURB) {
+        // a foreign reader: the array is made whole now (stream-ordered, like the frames), and from here on every
+        // frame writes it (frame_plan.h defer_turb), for the life of the context
+        OCEAN_ENTER(ctx);
+        if (int r = materialise_turb(ctx)) return r;
+        ctx->turb_exposed = true;
+    }
     *ptr = base;
     *bytes = ctx->texels() * eb * slices;
     return OCEAN_OK;
@@ -460,6 +481,10 @@ int ocean_set_column_band(ocean_ctx* ctx, int x_begin, int x_count) {
                                              std::to_string(g));
     if (x_count != n && (ctx->flags & (OCEAN_F_UNFUSED | OCEAN_F_MIPS)))
         return fail(OCEAN_E_UNSUPPORTED, "a column band needs the fused schedule and no mip chains");
+    // deferred TURB: a band's frames write their own columns of TURB only, so the rest is made whole first (the
+    // whole band keeps deferring: nothing to write)
+    if (x_count != n)
+        if (int r = materialise_turb(ctx)) return r;
     drop_bounds(ctx);
     ctx->band_x0 = x_begin;
     ctx->band_nx = x_count;
@@ -472,6 +497,9 @@ int ocean_set_column_parity(ocean_ctx* ctx, int parity) {
     if ((ctx->flags & OCEAN_F_VELOCITY) && parity != -1)
         return fail(OCEAN_E_UNSUPPORTED, "a velocity context (OCEAN_F_VELOCITY) takes no column parity");
     if (parity < -1 || parity > 1) return fail(OCEAN_E_INVALID_ARG, "parity must be -1 (off), 0 or 1");
+    // deferred TURB: as ocean_set_column_band (a parity is built for N = 4096, whose frames never defer, so this
+    // launches nothing today)
+    if (int r = materialise_turb(ctx)) return r;
     drop_bounds(ctx);
     if (parity < 0) {
         ctx->col_par = -1;

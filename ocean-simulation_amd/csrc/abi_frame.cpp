@@ -93,7 +93,9 @@ int ocean_fill(ocean_ctx* ctx) {
     OCEAN_ENTER(ctx);
     drop_bounds(ctx);
     const ocean::DevView v = ctx->view();
-    return timed(ctx, 2, [&] { return ocean::launch_fill(v, ctx->stream); }, "fill");
+    if (int r = timed(ctx, 2, [&] { return ocean::launch_fill(v, ctx->stream); }, "fill")) return r;
+    if (ctx->P == 4) ctx->turb_stale = false;  // deferred TURB: the fill wrote every texel of TURB from the foam state
+    return OCEAN_OK;
 }
 
 namespace {
@@ -167,11 +169,16 @@ int step_fused(ocean_ctx* ctx, float time) {
     if (ctx->col_par >= 0 && !ocean::use_q(in))
         return fail(OCEAN_E_STATE, "a column parity needs the three-plane frame (h0 from ocean_init_spectrum)");
     const hipStream_t s = ctx->stream;
+    // deferred TURB: a deferred frame leaves the float4 array stale; a frame that writes TURB starts from a whole
+    // array (it may write a part of it only), which costs a launch on the first such frame after deferred ones
+    if (ocean::defer_turb(in)) ctx->turb_stale = true;
+    else if (int r = materialise_turb(ctx)) return r;
     return ocean::plan_frame(in, [&](const ocean::FrameStep& st) {
         ocean::DevView c = sub_view(v, st.u0, st.nu, st.inter_u0);
         c.x0 = st.x0;
         c.nx = st.nx;
         c.disp_cached = st.disp_cached;
+        c.turb_defer = st.defer_turb;
         // band-limited cascades: the step's live items and the extents of its units
         ocean::PruneView pv{};
         if (st.pruned) pv = {ctx->prune_dev + ctx->units() + st.first, st.items, st.ubase, ctx->prune_dev + st.u0};

@@ -140,6 +140,7 @@ struct ocean_options {
     long op_chunk_mib = 0;  // OCEAN_OP_CHUNK_MIB: MiB of unit-planes per chunk of ocean_ifft2d (0: auto)
     int tile_w = 0;         // OCEAN_TILE_W: column-tile width of the fused path at N = 128..1024 (0: auto)
     int disp_cached = -1;   // OCEAN_DISP_CACHED: 0 / 1 force pass BQ's DISP store policy (disp_fits_cache); -1 auto
+    int defer_turb = 1;     // OCEAN_DEFER_TURB=0: pass BQ writes TURB every frame (frame_plan.h defer_turb; A/B)
     int grid_tile = 0;      // OCEAN_GRID_TILE: nodes along x of the grid kernel's workgroup tile, 64 / 32 / 16 (0: kept)
     int vel_nt = 0;         // OCEAN_VEL_NT=1: the velocity pack kernel writes VEL with nontemporal stores
     int prune = 1;          // OCEAN_PRUNE=0: passes AQ / BQ run every row of a band-limited cascade (dense schedule)
@@ -158,6 +159,7 @@ struct ocean_options {
         if (const char* e = std::getenv("OCEAN_OP_CHUNK_MIB")) o.op_chunk_mib = std::max(0L, std::atol(e));
         if (const char* e = std::getenv("OCEAN_TILE_W")) o.tile_w = std::max(0, std::atoi(e));
         if (const char* e = std::getenv("OCEAN_DISP_CACHED")) o.disp_cached = std::strcmp(e, "auto") ? std::atoi(e) != 0 : -1;
+        if (const char* e = std::getenv("OCEAN_DEFER_TURB")) o.defer_turb = std::atoi(e) != 0;
         if (const char* e = std::getenv("OCEAN_GRID_TILE")) o.grid_tile = std::atoi(e);
         if (const char* e = std::getenv("OCEAN_VEL_NT")) o.vel_nt = std::atoi(e) != 0;
         if (const char* e = std::getenv("OCEAN_PRUNE")) o.prune = std::atoi(e);
@@ -212,6 +214,12 @@ struct ocean_ctx {
     DeviceScratch bounds_dev;
     std::vector<bool> bounds_valid;
     bool disp_exposed = false;
+    // deferred TURB (frame_plan.h defer_turb).  turb_stale: a deferred frame has run since the float4 array was
+    // last whole, so the foam state is TURB's level 0 and the array waits for materialise_turb.  turb_exposed:
+    // ocean_get_device_ptr has handed TURB out, a foreign reader cannot be seen, so every frame writes it, for
+    // the life of the context.
+    bool turb_stale = false;
+    bool turb_exposed = false;
     // whitecap emitters (whitecaps.hip): the ballot masks and per-chunk counts of the largest grid, allocated by the
     // first ocean_whitecaps* call and reused by every later one
     DeviceScratch whitecap_dev;
@@ -265,8 +273,8 @@ struct ocean_ctx {
     // what the frame schedule reads of a context (frame_plan.h)
     ocean::FrameInputs frame_inputs() const {
         return {{n, C, T, P, inter_units, band_x0, band_nx, col_par},
-                {opt.q, opt.a4, opt.chunk_mib, opt.c4_bands, opt.disp_cached},
-                {h0k != nullptr, qside != nullptr, h0k_valid, h0_conj, prune_ready, &prune}};
+                {opt.q, opt.a4, opt.chunk_mib, opt.c4_bands, opt.disp_cached, opt.defer_turb},
+                {h0k != nullptr, qside != nullptr, h0k_valid, h0_conj, prune_ready, &prune, turb_exposed}};
     }
 
     ocean::DevView view() const {
@@ -304,6 +312,7 @@ struct ocean_ctx {
         v.nx = band_nx;
         v.xstr = col_par >= 0 ? 2 : 1;
         v.xpar = col_par >= 0 ? col_par : 0;
+        v.turb_foam = turb_stale;
         return v;
     }
 
@@ -383,6 +392,11 @@ int timed(ocean_ctx* ctx, int kind, F&& launch, const char* what) {
 
 // Every entry that writes DISP drops the cached surface bounds (ocean.h ocean_surface_bounds).
 inline void drop_bounds(ocean_ctx* ctx) { ctx->bounds_valid.assign(ctx->bounds_valid.size(), false); }
+
+// Deferred TURB: the float4 array from the foam state when a deferred frame has left it stale, one launch of
+// kind 2 on the context's stream; nothing otherwise (abi_context.cpp).  Every entry that reads, writes or hands
+// out the array itself calls it first.
+int materialise_turb(ocean_ctx* ctx);
 
 // The address of slice (tile, cascade) of a texture, which must hold `bytes` (abi_context.cpp).
 int slice_ptr(ocean_ctx* ctx, int tex, int tile, int cascade, size_t bytes, char** out);

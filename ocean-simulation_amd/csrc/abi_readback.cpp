@@ -202,6 +202,8 @@ int ocean_read_async(ocean_ctx* ctx, int texture, int tile, int cascade, void* d
     if (!dst) return fail(OCEAN_E_INVALID_ARG, "null destination");
     char* src = nullptr;
     if (int r = slice_ptr(ctx, texture, tile, cascade, bytes, &src)) return r;
+    if (texture == OCEAN_TEX_TURB)  // deferred TURB: the array from the foam state first
+        if (int r = materialise_turb(ctx)) return r;
     return start_readback(
         ctx, dst, bytes,
         [&](StageSlot* sl) -> int {

@@ -7,7 +7,7 @@
 //   - three-plane or four-plane frame (use_q, q_planes) and the row pass of the four-plane one;
 //   - unit chunks (chunk_units) and where a chunk's intermediate sits (inter_at_base);
 //   - column bands of the N >= 2048 column passes (c4_bands);
-//   - pass BQ's DISP store policy (disp_fits_cache);
+//   - pass BQ's DISP store policy (disp_fits_cache), and whether it writes TURB at all (defer_turb);
 //   - pruned or dense kernels per chunk (prune_pays), and no pass A for a chunk with no live item.
 // Per chunk of units: pass A (mirror-pair rows where h0k is valid and the size has them, else per-texel rows),
 // then pass B (column tiles, N <= 1024) or the four-step column passes (N >= 2048), those per (unit, column
@@ -39,6 +39,7 @@ struct FrameKnobs {
     long chunk_mib;   // OCEAN_CHUNK_MIB
     int c4_bands;     // OCEAN_C4_BANDS, 0 = auto
     int disp_cached;  // OCEAN_DISP_CACHED, -1 = auto
+    int defer_turb;   // OCEAN_DEFER_TURB: 0 = every frame writes TURB
 };
 struct FrameState {
     bool h0k, qside;    // allocated
@@ -46,6 +47,7 @@ struct FrameState {
     bool h0_conj;       // h0.zw = conj h0(-k)
     bool prune_ready;   // `prune` was built from the spectrum in h0k
     const PruneItems* prune;
+    bool turb_exposed;  // ocean_get_device_ptr has handed TURB out: every frame writes it
 };
 struct FrameInputs {
     FrameShape shape;
@@ -130,6 +132,20 @@ inline bool disp_fits_cache(const FrameInputs& in, bool q, int chunk) {
     return bytes <= ((size_t)224 << 20);
 }
 
+// Deferred TURB: TURB is the broadcast RGBA image of the foam state, 16 B per texel-cascade written to carry
+// the 4 B that pass BQ stores one line earlier, and every consumer inside the library reads .x alone.  A frame
+// whose column passes are all k_pass_bq (N = 512 / 1024, three-plane, whole column band, no parity) may leave the
+// float4 array as it is: the foam state is then TURB's level 0, the point consumers tap it (sample_filter.h), and
+// the entries that show the array itself materialise it first (abi_context.cpp materialise_turb).  Never deferred:
+// four-plane frames (after an H0 upload, OCEAN_Q=0, OCEAN_A4=0), N >= 2048, bands and parities, and a context
+// whose TURB pointer ocean_get_device_ptr has handed out.  Unfused and displacement-only contexts plan no such
+// frame (P = 2 fails pass_q_supported; ocean_step does not plan an unfused one).
+inline bool defer_turb(const FrameInputs& in) {
+    if (!in.knobs.defer_turb || in.state.turb_exposed) return false;
+    if (in.shape.n > 1024 || in.shape.band_nx != in.shape.n || in.shape.col_par >= 0) return false;
+    return use_q(in);
+}
+
 // Band-limited cascades: a context keeps live extents and an item table (prune_items.h) where passes AQ / BQ
 // can run pruned: the side arrays and h0k exist, N <= 1024, and a unit index fits the packed item.
 inline bool prune_tables(const FrameInputs& in) {
@@ -159,6 +175,7 @@ struct FrameStep {
     bool disp_cached;    // DevView::disp_cached
     bool pruned;         // passes AQ / BQ over the live rows: items [first, first + items) of the table are the
     int first, items, ubase;  // step's, and its unit 0 is context unit ubase
+    bool defer_turb;     // DevView::turb_defer: pass BQ stores no TURB (the same for every step of a frame)
 };
 
 // Calls step(const FrameStep&) once per timed launch of the frame, in launch order; stops at the first non-zero
@@ -175,7 +192,8 @@ int plan_frame(const FrameInputs& in, F&& step) {
     for (int u0 = 0; u0 < U; u0 += K) {
         const int nu = std::min(K, U - u0), slot = at_base ? 0 : u0;
         FrameStep st{q ? FramePass::A_Q : a4 ? FramePass::A_V4 : FramePass::A_V3, 0, "pass_a", u0, nu, at_base, slot,
-                     sh.band_x0, sh.band_nx, disp_fits_cache(in, q, K), prunable && sh.band_nx == sh.n, 0, 0, u0};
+                     sh.band_x0, sh.band_nx, disp_fits_cache(in, q, K), prunable && sh.band_nx == sh.n, 0, 0, u0,
+                     defer_turb(in)};
         if (st.pruned) {
             in.state.prune->chunk(u0, nu, &st.first, &st.items);
             st.pruned = prune_pays(st.items, (long)nu * (sh.n / 2 + 1));

@@ -95,6 +95,12 @@ struct DevView {
     // Infinity Cache and is written back while the next pass A runs, when HBM has headroom.  Set by the host
     // where the frame's re-read set plus DISP fits the cache (frame_plan.h disp_fits_cache).
     bool disp_cached;
+    // Deferred TURB (frame_plan.h defer_turb).  turb_defer: pass BQ does not store TURB; the foam state alone
+    // carries the frame's foam (host only: it selects the kernel).  turb_foam: the float4 array is stale, so the
+    // level-0 TURB taps of the point consumers read the foam state (sample_filter.h).  Both lie in the padding
+    // after disp_cached.
+    bool turb_defer;
+    bool turb_foam;
 };
 
 static_assert(sizeof(DevView) == 240, "DevView is a kernel argument: a new field changes every kernel's argument layout");
@@ -137,6 +143,8 @@ hipError_t launch_conjugate(const DevView& v, hipStream_t s);
 hipError_t launch_evolve(const DevView& v, float t, hipStream_t s);
 hipError_t launch_fill(const DevView& v, hipStream_t s);
 hipError_t launch_foam_import(const DevView& v, hipStream_t s);
+// TURB <- (f, f, f, f) of the foam state, every unit (deferred TURB: the float4 array when an entry needs it)
+hipError_t launch_turb_materialise(const DevView& v, hipStream_t s);
 hipError_t launch_noise(const DevView& v, uint64_t seed, hipStream_t s);
 // h0k = h0.xy (a context whose h0k is allocated after its spectrum: ocean_set_column_parity)
 hipError_t launch_h0k_extract(const DevView& v, hipStream_t s);

@@ -75,6 +75,58 @@ __device__ __forceinline__ float4 tri(const float4* tex0, const float4* chain, s
     return lerp4(a, b, f);
 }
 
+// The .x channel of tap / tri alone: the same texels, weights and operations on that channel, 4 B per texel.
+__device__ __forceinline__ float tap_x(const float4* __restrict__ t, int m, const Bil& b) {
+    const float t00 = t[(size_t)b.y0 * m + b.x0].x, t10 = t[(size_t)b.y0 * m + b.x1].x;
+    const float t01 = t[(size_t)b.y1 * m + b.x0].x, t11 = t[(size_t)b.y1 * m + b.x1].x;
+    const float a = t00 + b.fx * (t10 - t00), c = t01 + b.fx * (t11 - t01);
+    return a + b.fy * (c - a);
+}
+
+__device__ __forceinline__ float tri_x(const float4* tex0, const float4* chain, size_t chain_len, int slice, int n,
+                                       int logn, float u, float v, float lod) {
+    if (!chain || !(lod > 0.0f)) return tap_x(tex0 + (size_t)slice * n * n, n, bil(u, v, n));
+    const float lc = fminf(lod, (float)logn);
+    const int l0 = (int)floorf(lc), l1 = min(l0 + 1, logn);
+    const float f = lc - (float)l0;
+    const int m0 = n >> l0, m1 = n >> l1;
+    const float a = tap_x(level_ptr(tex0, chain, chain_len, slice, n, l0), m0, bil(u, v, m0));
+    const float b = tap_x(level_ptr(tex0, chain, chain_len, slice, n, l1), m1, bil(u, v, m1));
+    return a + f * (b - a);
+}
+
+// Deferred TURB (DevView::turb_foam): the float4 array is stale and the foam state is TURB's level 0, so tap_x's
+// four texels come from the state, one slice of which is column-tile-major [N/W][N][W] (W = DevView::tile_w;
+// spectrum.hip tiled_index): texel (y, x) sits at ((x / W) N + y) W + x % W.  The same values as TURB.x, the same
+// weights and operations: bit-identical to tap_x on the materialised array.
+__device__ __forceinline__ float tap_foam(const float* __restrict__ t, int n, int w, const Bil& b) {
+    // W is a power of two (inter_w(N), or 4) and a slice has at most 2^24 texels: shifts and masks on 32-bit indices
+    // (a division by a runtime W per tap measured 3-6 us on a 2^20-node whitecap count, docs/MEASUREMENTS.md section 33)
+    const int sh = __ffs(w) - 1;
+    auto at = [&](int y, int x) { return t[((((x >> sh) * n + y) << sh) | (x & (w - 1)))]; };
+    const float t00 = at(b.y0, b.x0), t10 = at(b.y0, b.x1);
+    const float t01 = at(b.y1, b.x0), t11 = at(b.y1, b.x1);
+    const float a = t00 + b.fx * (t10 - t00), c = t01 + b.fx * (t11 - t01);
+    return a + b.fy * (c - a);
+}
+
+// TURB.x of slice `slice` at (u, w, lod), tri_x's result bit for bit (and tri's .x: the same operations on that
+// channel).  While the array is stale, level 0 is tapped from the foam state; levels >= 1 are the mip chain's
+// (mips.hip boxes level 1 from the foam state in either mode) and l1 >= 1 always (N >= 16).
+__device__ __forceinline__ float turb_x(const DevView& v, int slice, float u, float w, float lod) {
+    if (!v.turb_foam) return tri_x(v.turb, v.turb_mips, v.mip_chain, slice, v.n, v.logn, u, w, lod);
+    const float* f0 = v.foam + (size_t)slice * v.n * v.n;
+    if (!v.turb_mips || !(lod > 0.0f)) return tap_foam(f0, v.n, v.tile_w, bil(u, w, v.n));
+    const float lc = fminf(lod, (float)v.logn);
+    const int l0 = (int)floorf(lc), l1 = min(l0 + 1, v.logn);
+    const float f = lc - (float)l0;
+    const int m0 = v.n >> l0, m1 = v.n >> l1;
+    const float a = l0 == 0 ? tap_foam(f0, v.n, v.tile_w, bil(u, w, m0))
+                            : tap_x(level_ptr(v.turb, v.turb_mips, v.mip_chain, slice, v.n, l0), m0, bil(u, w, m0));
+    const float b = tap_x(level_ptr(v.turb, v.turb_mips, v.mip_chain, slice, v.n, l1), m1, bil(u, w, m1));
+    return a + f * (b - a);
+}
+
 // What Water.shader reads at world (x, z) of tile `tile`, summed over the cascades in order from 0:
 // DISP at level 0, DERIV and 1 - saturate(TURB.x) at `lod` (zero on DISPLACEMENT_ONLY contexts).
 struct WorldSample {
@@ -94,7 +146,9 @@ __device__ __forceinline__ WorldSample sample_cascades(const DevView& v, int til
         s.disp = add4(s.disp, tap(v.disp + (size_t)slice * v.n * v.n, v.n, bil(u, w, v.n)));  // no mips (:325)
         if (v.deriv) {
             s.deriv = add4(s.deriv, tri(v.deriv, v.deriv_mips, v.mip_chain, slice, v.n, v.logn, u, w, lod));
-            const float tb = tri(v.turb, v.turb_mips, v.mip_chain, slice, v.n, v.logn, u, w, lod).x;
+            // (a stale array, deferred TURB: the same value from the foam state, turb_x)
+            const float tb = v.turb_foam ? turb_x(v, slice, u, w, lod)
+                                         : tri(v.turb, v.turb_mips, v.mip_chain, slice, v.n, v.logn, u, w, lod).x;
             s.turb = s.turb + (1.0f - fminf(fmaxf(tb, 0.0f), 1.0f));  // 1 - saturate(.x) (:343)
         }
     }
@@ -145,26 +199,6 @@ __device__ __forceinline__ void sample_cascades_vel(const DevView& v, const floa
     }
 }
 
-// The .x channel of tap / tri alone: the same texels, weights and operations on that channel, 4 B per texel.
-__device__ __forceinline__ float tap_x(const float4* __restrict__ t, int m, const Bil& b) {
-    const float t00 = t[(size_t)b.y0 * m + b.x0].x, t10 = t[(size_t)b.y0 * m + b.x1].x;
-    const float t01 = t[(size_t)b.y1 * m + b.x0].x, t11 = t[(size_t)b.y1 * m + b.x1].x;
-    const float a = t00 + b.fx * (t10 - t00), c = t01 + b.fx * (t11 - t01);
-    return a + b.fy * (c - a);
-}
-
-__device__ __forceinline__ float tri_x(const float4* tex0, const float4* chain, size_t chain_len, int slice, int n,
-                                       int logn, float u, float v, float lod) {
-    if (!chain || !(lod > 0.0f)) return tap_x(tex0 + (size_t)slice * n * n, n, bil(u, v, n));
-    const float lc = fminf(lod, (float)logn);
-    const int l0 = (int)floorf(lc), l1 = min(l0 + 1, logn);
-    const float f = lc - (float)l0;
-    const int m0 = n >> l0, m1 = n >> l1;
-    const float a = tap_x(level_ptr(tex0, chain, chain_len, slice, n, l0), m0, bil(u, v, m0));
-    const float b = tap_x(level_ptr(tex0, chain, chain_len, slice, n, l1), m1, bil(u, v, m1));
-    return a + f * (b - a);
-}
-
 // The TURB taps of sample_cascades alone (a context with TURB: not DISPLACEMENT_ONLY): the same operations on
 // the same texels, so the result is bit-identical to sample_cascades(...).turb, with mip chains and lod > 0 too.
 __device__ __forceinline__ float sample_foam(const DevView& v, int tile, float x, float z, float lod) {
@@ -172,7 +206,7 @@ __device__ __forceinline__ float sample_foam(const DevView& v, int tile, float x
     for (int c = 0; c < v.C; ++c) {
         const float L = v.casc[c * 5];
         const float u = x / L, w = z / L;
-        const float tb = tri_x(v.turb, v.turb_mips, v.mip_chain, tile * v.C + c, v.n, v.logn, u, w, lod);
+        const float tb = turb_x(v, tile * v.C + c, u, w, lod);
         turb = turb + (1.0f - fminf(fmaxf(tb, 0.0f), 1.0f));
     }
     return turb;

@@ -176,6 +176,19 @@ __global__ __launch_bounds__(256) void k_foam_import(DevView v) {
         v.foam[tiled_index(i, v.n, v.tile_w)] = v.turb[i].x;
 }
 
+// TURB <- the broadcast image of the foam state (deferred TURB, frame_plan.h defer_turb: pass BQ left the float4
+// array as it was).  A lane writes one texel, so a wave stores 1 KiB of a texture row; the array is not read
+// again by this library, so the stores are nontemporal.
+__global__ __launch_bounds__(256) void k_turb_materialise(DevView v) {
+    using f32x4 = __attribute__((__vector_size__(4 * sizeof(float)))) float;
+    const size_t total = (size_t)v.n * v.n * v.units;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const float f = v.foam[tiled_index(i, v.n, v.tile_w)];
+        const f32x4 o = {f, f, f, f};
+        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(v.turb + i));
+    }
+}
+
 // Device noise (ocean_generate_noise_device): a counter-based stream per texel so
 // every texel is independent work.  Texel (x, y) of tile t draws its k-th uniform
 // from h_k = mix(key + (k + 1) * 0x9E3779B97F4A7C15), key = mix(seed + t) ^ (y * N + x)
@@ -265,6 +278,12 @@ hipError_t launch_evolve(const DevView& v, float t, hipStream_t s) {
 
 hipError_t launch_foam_import(const DevView& v, hipStream_t s) {
     launch(k_foam_import, dim3(grid_for((size_t)v.n * v.n * v.units)), dim3(256), 0, s, v);
+    return hipGetLastError();
+}
+
+hipError_t launch_turb_materialise(const DevView& v, hipStream_t s) {
+    if (!v.turb || !v.foam) return hipErrorInvalidValue;
+    launch(k_turb_materialise, dim3(grid_for((size_t)v.n * v.n * v.units)), dim3(256), 0, s, v);
     return hipGetLastError();
 }
 
